@@ -1,19 +1,23 @@
 #!/usr/bin/env python
 """bench.py -- CTR samples/sec of the HIP forward on synthetic MovieLens-20M-shaped batches.
 
-    python bench.py --gpus N --steps K --warmup W [--workload NAME]
+    python bench.py --gpus N --steps K --warmup W [--workload NAME] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path over one batch (ids + dense already resident in HBM -> scores in HBM); at N>1
 every rank scores its own B-row shard (weak scaling: global batch N*B) and its score slices are all-gathered over RCCL,
---gather-group steps per collective on a second stream (every step's scores have been exchanged on every rank when a
+--gather-group steps per collective on a second stream (every step's scores have been exchanged on every rank when the
 timed region ends).  Rank 0 prints ONE JSON line.
 
-How the K steps are timed.  A 65 536-row forward takes single-digit microseconds, so K = 20 steps are ~100 us of GPU work
--- less than one host synchronisation.  The timed REGION is therefore R back-to-back repetitions of the K-step block,
-R chosen (after the warm-up) so that a region lasts >= --min-region-ms (50 ms); a region is bracketed by barrier +
-torch.cuda.synchronize() on both sides and timed with the host clock (max over ranks); --regions (5) regions are timed
-and `ms_per_step` = median region / (R*K).  `config.repeats` = R.  The warm-up runs W steps AND at least --settle-ms of
-work, so clocks have settled whatever W is.
+How the K steps are timed.  The warm-up runs W steps AND at least --settle-ms of work, so clocks have settled whatever W
+is.  Then exactly K steps run as ONE region, bracketed by barrier + torch.cuda.synchronize() on both sides and timed with
+the host clock (max over ranks): `ms_per_step` = region / K, `value` = samples of the region / region.  A 65 536-row
+forward takes single-digit microseconds, so K should be large enough for the region to out-last a host synchronisation
+(tens of microseconds) many times over.  --dump-outputs DIR writes the last timed step's scores (dump_outputs()).
+
+A plain run does nothing else.  --full then adds, after the timed steps: the oracle check of the outputs; the
+repeated-regions figure (R back-to-back repetitions of the K-step block, R chosen so that a region lasts >= --min-region-ms,
+--regions of them, median: `value_repeated_regions`, `config.repeats` = R); the strict-order roofline blocks; the side
+workloads; the CPU baseline; the hardware block.
 
 --gpus N without a launcher (no RANK in the environment) starts the N ranks itself, one process per GPU.
 
@@ -646,8 +650,9 @@ def main():
     ap.add_argument("--no-check", action="store_true", help="skip the oracle spot check of the outputs")
     ap.add_argument("--no-hardware-probe", action="store_true", help="skip the device facts / measured copy bandwidth block")
     ap.add_argument("--min-region-ms", type=float, default=50.0,
-                    help="a timed region = R back-to-back repetitions of the K-step block, R chosen so that it lasts at least this long")
-    ap.add_argument("--regions", type=int, default=5, help="timed regions; ms_per_step is the median region / (R*K)")
+                    help="--full's repeated-regions figure: a region = R back-to-back repetitions of the K-step block, R chosen so that it "
+                         "lasts at least this long")
+    ap.add_argument("--regions", type=int, default=5, help="--full's repeated-regions figure: regions timed; its ms_per_step is the median region / (R*K)")
     ap.add_argument("--settle-ms", type=float, default=40.0, help="the warm-up lasts at least this long, whatever --warmup says")
     ap.add_argument("--gather-group", type=int, default=64,
                     help="N>1: batches whose score slices share one RCCL all-gather (overlapped with the next group)")
@@ -688,6 +693,13 @@ def main():
     ap.add_argument("--shard-tables", action="store_true",
                     help="deepfm_c4 / deepfm_v2_c4: the 27 M-row item table(s) ROW-SHARDED over the ranks (BASELINE config 4's wording) instead of "
                          "replicated: sparrowrecsys_amd.dist.ShardedTable, peers' rows loaded over xGMI by the unchanged fused kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else: the oracle check, the repeated-regions figure, the "
+                         "strict-order roofline and its MFMA / HBM-resident / variant blocks, the side workloads, the CPU baseline, the hardware "
+                         "block.  Off: set-up, warm-up, the --steps timed steps, --dump-outputs, the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the scores of the last timed step as DIR/scores.npy (float32; inputs are seeded: the same arguments give "
+                         "the same inputs)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU, no kernels: the launcher / process-group / grouped all-gather / timing plumbing with a stand-in "
                          "forward on CPU tensors (gloo).  For the CPU test of `--gpus N` self-spawning; the line says dry_run")
@@ -778,6 +790,13 @@ def main():
 
     group_run = [None, None]
     prepared = {}
+    last_out = [None]                      # the score buffer the most recent step wrote (what --dump-outputs writes)
+
+    def prepare(count):
+        if count not in prepared:
+            idx = [i % NB for i in range(count)]
+            prepared[count] = eng.prepare_many([batches[j][0] for j in idx], [batches[j][1] for j in idx], [outs[j] for j in idx], ws)
+        return prepared[count]
 
     def run_steps(first, count):
         """`count` steps starting at step index `first`.  One sprk_forward_many call enqueues a run of
@@ -790,11 +809,9 @@ def main():
             return
         if gs is None:
             # the marshalled (and validated) pointer arrays of a `count`-step run are built once, OUTSIDE any timed region
-            # (prime() below), and replayed: a run always starts at input batch 0
-            if count not in prepared:
-                idx = [i % NB for i in range(count)]
-                prepared[count] = eng.prepare_many([batches[j][0] for j in idx], [batches[j][1] for j in idx], [outs[j] for j in idx], ws)
-            prepared[count]()
+            # (prepare()), and replayed: a run always starts at input batch 0
+            prepare(count)()
+            last_out[0] = outs[(count - 1) % NB]
             return
         i = first
         while i < first + count:
@@ -806,12 +823,15 @@ def main():
                     idx = [j % NB for j in range(gs.G)]
                     group_run[slot] = eng.prepare_many([batches[j][0] for j in idx], [batches[j][1] for j in idx], outs_g, ws)
                 group_run[slot](stream=torch.cuda.current_stream().cuda_stream)
+                last_out[0] = outs_g[-1]
                 gs.commit()
                 i += gs.G
                 continue
             n = min(gs.G - gs.fill, first + count - i)
             idx = [j % NB for j in range(i, i + n)]
-            eng.forward_many([batches[j][0] for j in idx], [batches[j][1] for j in idx], [gs.out() for _ in idx], ws)
+            outs_p = [gs.out() for _ in idx]
+            eng.forward_many([batches[j][0] for j in idx], [batches[j][1] for j in idx], outs_p, ws)
+            last_out[0] = outs_p[-1]
             i += n
             if gs.full():
                 gs.commit()
@@ -825,14 +845,17 @@ def main():
             torch.cuda.synchronize()
 
     K = args.steps
+    if K < 1:
+        raise SystemExit("--steps must be at least 1")
     timer = Timer(run_steps, fence, dist_on, True)
-    # ---- warm-up: W steps as asked, then K-step blocks until --settle-ms have passed (clocks, caches, RCCL channels) ----
+    # ---- warm-up: W steps as asked, then short blocks until --settle-ms have passed (clocks, caches, RCCL channels) ----
     t_w = time.perf_counter()
     fence()
     run_steps(0, args.warmup)
     fence()
     timer.step = args.warmup
     settle = torch.tensor([0.0], dtype=torch.float64, device="cuda")
+    settle_steps = min(K, 128)             # (bounded: a long --steps must not make the warm-up long)
     while True:
         el = time.perf_counter() - t_w
         if dist_on:                        # every rank must take the same number of blocks
@@ -841,9 +864,63 @@ def main():
             el = float(settle.item())
         if el * 1e3 >= args.settle_ms:
             break
-        timer.region(K)
+        timer.region(settle_steps)
     eng.check_ids()
-    # ---- calibration: one K-step block -> R (second pass: the first builds the block's prepared launch list) ----
+    # ---- the timed steps: exactly --steps of them, ONE region bracketed by fence() on both sides ----
+    if gs is None:
+        prepare(K)                         # the K-step launch list is built outside the region
+    wall_k, ev_k = timer.region(K)
+    value = B * world * K / wall_k
+    ms_per_step = wall_k * 1e3 / K
+    dumped = dump_outputs(args.dump_outputs, last_out[0], dist_on, args.backend, rank, world) if args.dump_outputs else None
+    line = None
+    if rank == 0:
+        table_mb = getattr(eng, "table_bytes", lambda: 0)() / 1e6
+        line = {
+            "metric": "ctr_samples_per_sec", "value": value, "unit": "samples/s", "n_gpus": world,
+            "steps": K, "warmup": args.warmup, "ms_per_step": ms_per_step,
+            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "dtype_detail": "fp32 in, fp32 out, fp32 accumulation; contractions of finalize-bounded operands (table rows x weights) run on "
+                            "v_mfma_f32_16x16x32_f16 with split operands hi + lo = 22 significand bits (narrower than fp32's 24: measured |err| vs the "
+                            "fp64 oracle <= 5e-7 on the checked rows, bar 1e-4); the all-f32-MFMA variant is SPRK_V2_HALF=0 / SPRK_DIN_HALF=0 / SPRK_DYN_F16=0",
+            "config": {"workload": "%s: %s" % (args.workload, desc), "batch_per_gpu": B, "global_batch": B * world,
+                       "id_distribution": args.dist, "input_batches_cycled": NB,
+                       "timed": "one region of the %d steps after the warm-up, barrier + synchronize on both sides, host clock, max over "
+                                "ranks; ms_per_step = region / %d; value = samples of the region / region" % (K, K),
+                       "ms_per_step_hip_events": ev_k * 1e3 / K,
+                       "collective": None if not dist_on else ("sprk_comm_allgather_scores (RCCL behind the C ABI)" if args.collective == "sprk"
+                                                                 else "sprk_peer_allgather_scores (direct peer writes, IPC-mapped receive buffers)" if args.collective == "peer"
+                                                                 else "torch.distributed.all_gather_into_tensor (%s)" % ("RCCL" if args.backend == "nccl" else "gloo: functional run only")),
+                       "parallelism": ("rows sharded over %d GPU(s), tables replicated, all-gather of scores" % world)
+                                      + ("" if world == 1 else " (one collective per %d steps, overlapped)" % gs.G),
+                       "tables_row_sharded": ("%d table(s) of %d rows row-sharded over %d rank(s), one virtual range per rank (sprk_vtable_*), peers' rows "
+                                              "loaded by the fused kernel" % (len(_SHARDED_TABLES), CONFIG4_ROWS, world)) if _SHARDED_TABLES else None,
+                       "launch_overlap_streams": fan, "batches_per_launch": lb,
+                       "tables": "%.0f MB of device tables: %s" % (table_mb, (("%d of the %d algorithmic bytes per sample are rows of the table(s) beyond the 256 MB Infinity Cache "
+                                                                                 "(HBM-side rate: roofline.hbm_side_GBps); the other tables fit the cache" % (ws_info["hbm_side_bytes_per_sample"], roof["bytes_per_sample"]))
+                                                                                if ws_info else "beyond the 256 MB Infinity Cache (HBM-resident gather)") if table_mb > 512
+                                                                      else "resident in the 256 MB Infinity Cache -- `roofline` is a fabric/cache-side rate for this "
+                                                                           "config; see roofline_hbm_resident") if table_mb else None,
+                       "kernel": eng.kernel_name(),
+                       "arithmetic": "fp32 semantics; contractions whose operands are bounded at finalize (table rows x weights) run on "
+                                     "v_mfma_f32_16x16x32_f16 with split operands hi + lo (22 significand bits) and f32 accumulation -- "
+                                     "fp32-class error, tests/test_gpu_parity.py::test_deepfm_v2_split_f16_is_fp32_class; everything else "
+                                     "on f32 MFMA / VALU (SPRK_V2_HALF=0 / SPRK_DIN_HALF=0 force f32 MFMA throughout)"},
+            "full": bool(args.full),
+        }
+        if dumped:
+            line["outputs"] = dumped
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the outputs -- nothing else (every other block is --full's)
+        if rank == 0:
+            emit(line)
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ======== --full: every other measurement and check, after the timed steps ========
+    # ---- the repeated-regions figure: one K-step block -> R (second pass: the first builds the block's prepared launch list) ----
     timer.region(K)
     _, blk = timer.region(K)
     if dist_on:
@@ -869,7 +946,7 @@ def main():
             mult = lb // math.gcd(K, lb)
             R = int(math.ceil(R / mult) * mult)
         timer.region(R * K)                    # (builds the new list)
-    # ---- timed regions ----
+    # ---- repeated regions (R back-to-back K-step blocks each, >= --min-region-ms; the headline of rounds 1-6) ----
     walls, evs = [], []
     for _ in range(max(1, args.regions)):
         w, e = timer.region(R * K)
@@ -984,7 +1061,6 @@ def main():
                         "latency_us": lat * 1e6, "samples_per_s": B_global / lat, "rows_per_rank": B,
                         "gathered_scores_oracle_check_max_abs_err": chk1}
     if rank == 0:
-        value = B * world * n_region / elapsed
         region = "strict-order one-batch-per-launch loop after the timed regions (%d launches over %d input batches, median of 3 loops)" % (n_strict, NBS)
         legacy_din = env("SPRK_DIN_LEGACY") == "1"
         extra = {}
@@ -1068,43 +1144,19 @@ def main():
             except Exception:
                 traffic = None
         rl["traffic"] = traffic
-        table_mb = getattr(eng, "table_bytes", lambda: 0)() / 1e6
-        line = {
-            "metric": "ctr_samples_per_sec", "value": value, "unit": "samples/s", "n_gpus": world,
-            "steps": K, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / n_region,
-            "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "dtype_detail": "fp32 in, fp32 out, fp32 accumulation; contractions of finalize-bounded operands (table rows x weights) run on "
-                            "v_mfma_f32_16x16x32_f16 with split operands hi + lo = 22 significand bits (narrower than fp32's 24: measured |err| vs the "
-                            "fp64 oracle <= 5e-7 on the checked rows, bar 1e-4); the all-f32-MFMA variant is SPRK_V2_HALF=0 / SPRK_DIN_HALF=0 / SPRK_DYN_F16=0",
-            "value_one_batch_per_launch": B * world / fwd_s,
-            "config": {"workload": "%s: %s" % (args.workload, desc), "batch_per_gpu": B, "global_batch": B * world,
-                       "id_distribution": args.dist, "input_batches_cycled": NB,
-                       "repeats": R, "regions": len(walls), "region_ms": [round(w * 1e3, 3) for w in walls],
-                       "timed": "each region = %d back-to-back repetitions of the %d-step block (>= %.0f ms), barrier + synchronize on both "
-                                "sides, host clock, max over ranks; ms_per_step = median region / %d; value = the same region" % (R, K, args.min_region_ms, n_region),
-                       "ms_per_step_hip_events": ev_region * 1e3 / n_region,
-                       "collective": None if not dist_on else ("sprk_comm_allgather_scores (RCCL behind the C ABI)" if args.collective == "sprk"
-                                                                 else "sprk_peer_allgather_scores (direct peer writes, IPC-mapped receive buffers)" if args.collective == "peer"
-                                                                 else "torch.distributed.all_gather_into_tensor (%s)" % ("RCCL" if args.backend == "nccl" else "gloo: functional run only")),
-                       "parallelism": ("rows sharded over %d GPU(s), tables replicated, all-gather of scores" % world)
-                                      + ("" if world == 1 else " (one collective per %d steps, overlapped; %d collectives per region)"
-                                         % (gs.G, (n_region + gs.G - 1) // gs.G)),
-                       "oracle_check_max_abs_err": check,
-                       "tables_row_sharded": ("%d table(s) of %d rows row-sharded over %d rank(s), one virtual range per rank (sprk_vtable_*), peers' rows "
-                                              "loaded by the fused kernel" % (len(_SHARDED_TABLES), CONFIG4_ROWS, world)) if _SHARDED_TABLES else None,
-                       "launch_overlap_streams": fan, "batches_per_launch": lb,
-                       "tables": "%.0f MB of device tables: %s" % (table_mb, (("%d of the %d algorithmic bytes per sample are rows of the table(s) beyond the 256 MB Infinity Cache "
-                                                                                 "(HBM-side rate: roofline.hbm_side_GBps); the other tables fit the cache" % (ws_info["hbm_side_bytes_per_sample"], roof["bytes_per_sample"]))
-                                                                                if ws_info else "beyond the 256 MB Infinity Cache (HBM-resident gather)") if table_mb > 512
-                                                                      else "resident in the 256 MB Infinity Cache -- `roofline` is a fabric/cache-side rate for this "
-                                                                           "config; see roofline_hbm_resident") if table_mb else None,
-                       "kernel": eng.kernel_name(),
-                       "arithmetic": "fp32 semantics; contractions whose operands are bounded at finalize (table rows x weights) run on "
-                                     "v_mfma_f32_16x16x32_f16 with split operands hi + lo (22 significand bits) and f32 accumulation -- "
-                                     "fp32-class error, tests/test_gpu_parity.py::test_deepfm_v2_split_f16_is_fp32_class; everything else "
-                                     "on f32 MFMA / VALU (SPRK_V2_HALF=0 / SPRK_DIN_HALF=0 force f32 MFMA throughout)"},
-            "roofline": rl,
-        }
+        line["value_one_batch_per_launch"] = B * world / fwd_s
+        line["value_repeated_regions"] = B * world * n_region / elapsed
+        line["config"].update({
+            "repeated_regions": "each region = %d back-to-back repetitions of the %d-step block (>= %.0f ms), barrier + synchronize on both sides, "
+                                "host clock, max over ranks; ms_per_step_repeated_regions = median region / %d; value_repeated_regions = the "
+                                "same region" % (R, K, args.min_region_ms, n_region),
+            "repeats": R, "regions": len(walls), "region_ms": [round(w * 1e3, 3) for w in walls],
+            "ms_per_step_repeated_regions": elapsed * 1e3 / n_region,
+            "ms_per_step_repeated_regions_hip_events": ev_region * 1e3 / n_region,
+            "oracle_check_max_abs_err": check})
+        if world > 1:
+            line["config"]["parallelism"] += " (%d collectives per repeated region)" % ((n_region + gs.G - 1) // gs.G)
+        line["roofline"] = rl
         line["value_one_batch_per_launch_note"] = ("B x n_gpus / the strict-order per-launch time of `roofline` (%.2f us): the north star's "
                                                    "'at batch %d' figure; `value` scores %d batch(es) per launch" % (fwd_s * 1e6, B, lb))
         if fan2_s is not None:
@@ -1207,18 +1259,59 @@ def main():
             line["cpu_baseline"] = cpu_baseline(args.workload, model, feats, args.cpu_seconds)
         if not args.no_hardware_probe:
             line["hardware"] = hardware_block(torch, torch.device("cuda", local_dev))
-        # RCCL prints a version banner through C stdio, which (stdout being a pipe) would otherwise be flushed at exit,
-        # AFTER this line: flush it first so the JSON is the last line of output
-        try:
-            import ctypes
-            ctypes.CDLL(None).fflush(None)
-        except Exception:
-            pass
-        sys.stdout.flush()
-        print(json.dumps(line), flush=True)
+        emit(line)
     if dist_on:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def emit(line):
+    """Print the result line.  RCCL prints a version banner through C stdio, which (stdout being a pipe) would otherwise be
+    flushed at exit, AFTER this line: flush it first so the JSON is the last line of output."""
+    try:
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+    except Exception:
+        pass
+    sys.stdout.flush()
+    print(json.dumps(line), flush=True)
+
+
+DUMP_CAP_VALUES = 4 << 20      # scores --dump-outputs writes at most (16 MB of float32 + 32 MB of float64 index when sampled)
+
+
+def dump_outputs(out_dir, last, dist_on, backend, rank, world):
+    """--dump-outputs DIR: the scores the timed path computed in its LAST step -- what a caller receives: the batch's B scores at
+    N = 1, the all-gathered N x B at N > 1 (rank order) -- as DIR/scores.npy (float32).  An output of more than DUMP_CAP_VALUES
+    values is written as the values at a fixed, seeded, sorted sample of its indices (DIR/scores_index.npy, float64, says which).
+    Collective at N > 1: every rank calls it.  Returns what was written (rank 0) or None."""
+    import torch
+    if last is None:
+        raise SystemExit("--dump-outputs: no step has run")
+    if dist_on:
+        import torch.distributed as dist
+        t = last.detach().reshape(-1)
+        if backend == "gloo":
+            t = t.cpu()
+        parts = [torch.empty_like(t) for _ in range(world)]
+        dist.all_gather(parts, t)
+        scores = torch.cat(parts)
+    else:
+        scores = last.detach().reshape(-1)
+    if rank != 0:
+        return None
+    scores = scores.float().cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if scores.size > DUMP_CAP_VALUES:
+        index = np.sort(np.random.default_rng(20240611).choice(scores.size, DUMP_CAP_VALUES, replace=False))
+        arrays["scores_index"] = index.astype(np.float64)
+        scores = scores[index]
+    arrays["scores"] = np.ascontiguousarray(scores, dtype=np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": {name: {"shape": list(a.shape), "dtype": str(a.dtype)} for name, a in arrays.items()},
+            "what": "the scores of the last timed step" + (" (all ranks, gathered)" if dist_on else "")}
 
 
 # MFMA instructions each fused kernel ISSUES per 16-sample task (or per sample for the wave-per-sample attention kernel), by

@@ -9,8 +9,8 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r06_prof
 mkdir -p $O
 rocminfo | grep -E "Marketing Name|gfx|Compute Unit" | head -6 > $O/rocminfo.txt 2>&1
-STRICT="--cpu-seconds 0 --no-check --launch-batches 1 --overlap-streams 0 --hbm-resident 0 --side-workloads= --no-hardware-probe"
-MANY="--cpu-seconds 0 --no-check --hbm-resident 0 --side-workloads= --no-hardware-probe --variants 0"
+STRICT="--full --cpu-seconds 0 --no-check --launch-batches 1 --overlap-streams 0 --hbm-resident 0 --side-workloads= --no-hardware-probe"
+MANY="--full --cpu-seconds 0 --no-check --hbm-resident 0 --side-workloads= --no-hardware-probe --variants 0"
 declare -A WL
 WL[c2]="--steps 400 --warmup 40 --input-batches 32"
 WL[c2_hbm]="--steps 400 --warmup 40 --big-vocab 8388608 --input-batches 32"
@@ -45,7 +45,7 @@ done
 export SPRK_V2_HALF=1
 if has c2; then
 # the driver's launch shape (64 batches per launch) under the tracer, EVERY launch of the multi-batch kernel a full one
-SPRK_BENCH_SKIP_16=1 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_drv -o t -- python $R/bench.py --steps 64 --warmup 64 --cpu-seconds 0 --no-check --hbm-resident 0 --side-workloads= --no-hardware-probe > $O/c2_driver.log 2>&1
+SPRK_BENCH_SKIP_16=1 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_drv -o t -- python $R/bench.py --full --steps 64 --warmup 64 --cpu-seconds 0 --no-check --hbm-resident 0 --side-workloads= --no-hardware-probe > $O/c2_driver.log 2>&1
 grep '^{"metric"' $O/c2_driver.log | tail -1 > $O/c2_driver_bench.json
 f=$(find $O/trace_drv -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/c2_driver_kernel_stats.csv; rm -rf $O/trace_drv
 fi
@@ -86,5 +86,5 @@ PY
 rm -rf $O/pmc_*/
 # the GPU suite and the driver's command on this build
 timeout 1800 python -m pytest tests -m gpu -q 2>&1 | grep -v -E "^(HIP|ROCm|Hostname|Librccl|RCCL|$)" | tail -6 | tee $O/pytest_gpu.log
-timeout 600 python bench.py --steps 20 --warmup 5 2>/dev/null | grep '^{"metric"' | tail -1 > $O/bench_driver_command.json
+timeout 600 python bench.py --full --steps 20 --warmup 5 2>/dev/null | grep '^{"metric"' | tail -1 > $O/bench_driver_command.json
 ls $O | wc -l

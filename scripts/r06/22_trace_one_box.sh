@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/r06_prof
 mkdir -p $O
 TAG=${1:-b}
-STRICT="--cpu-seconds 0 --no-check --launch-batches 1 --overlap-streams 0 --hbm-resident 0 --side-workloads= --no-hardware-probe"
+STRICT="--full --cpu-seconds 0 --no-check --launch-batches 1 --overlap-streams 0 --hbm-resident 0 --side-workloads= --no-hardware-probe"
 cd /tmp && export TMPDIR=/tmp
 for w in ${WORKLOADS:-c2 c2_hbm c3}; do          # (WORKLOADS="c5": config 5 after round 6's k_mlp_rows change)
   X="--steps 400 --warmup 40 --input-batches 32"; [ $w = c2_hbm ] && X="$X --big-vocab 8388608"; [ $w = c3 ] && X="--steps 60 --warmup 6 --workload din_c3"

@@ -410,7 +410,7 @@ def _slow_stub_factory():
     return m
 
 
-def test_engine_survives_a_front_that_dies_with_a_request_in_flight(tmp_path):
+def test_engine_survives_a_front_that_dies_with_a_request_in_flight():
     """[r6, ADVICE r05] The engine process against raw connections (no HTTP): three fronts send requests that merge into one forward; one of them
     closes its connection before the answer.  Round 5's blanket handler then answered every member a SECOND time -- live fronts were one reply out
     of step for ever (same candidate counts: nothing to notice it by) -- and the dead connection's second failure killed the engine loop.  Now: each
@@ -421,7 +421,8 @@ def test_engine_survives_a_front_that_dies_with_a_request_in_flight(tmp_path):
     from sparrowrecsys_amd.serving import _engine_main
     ctx = mp.get_context("fork")
     ready, stop = ctx.Queue(), ctx.Event()
-    address = str(tmp_path / "engine.sock")
+    # an abstract-namespace socket: no file, so no limit from how deep the temporary directory lies (AF_UNIX paths stop at 107 bytes)
+    address = "\0sprk_engine_test_%d_%d" % (os.getpid(), time.monotonic_ns())
     eng = ctx.Process(target=_engine_main, args=(_slow_stub_factory, (), address, ready, stop), daemon=True)
     eng.start()
     try:
