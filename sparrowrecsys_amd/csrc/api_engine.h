@@ -351,7 +351,7 @@ int sprk_finalize(sprk_handle h) {
             // first-order weight blocks back to back
             HIP_TRY(hipMalloc((void**)&h->v2_fo_all, h->v2_fo_floats * sizeof(float)));
             for (int g = 0; g < vv.g_emb; ++g)
-                HIP_TRY(hipMemcpy(h->v2_fo_all + h->v2run.fo_off[g], h->v2.w1[g], ((size_t)h->v2run.vocab[g] + 1) * sizeof(float), hipMemcpyDeviceToDevice));
+                HIP_TRY(hipMemcpy(h->v2_fo_all + h->v2run.fo_off[g], h->v2_w1_grp[g], ((size_t)h->v2run.vocab[g] + 1) * sizeof(float), hipMemcpyDeviceToDevice));
             h->v2run.fo_all = h->v2_fo_all;
             {
                 const int KP = vv.kpc * 16;
@@ -363,7 +363,7 @@ int sprk_finalize(sprk_handle h) {
                     long long blocks = (rows + 3) / 4;
                     if (blocks > 65536) blocks = 65536;
                     hipLaunchKernelGGL(k_v2_fold, dim3((unsigned)blocks), dim3(256), 0, 0, h->v2.table[g], h->v2.ldp_emb,
-                                       h->v2.Wp[g], h->v2.ldp_emb, h->v2.bp[g], h->v2.w1[g], h->v2.hfm, h->v2.n_hfm, h->v2.h0w,
+                                       h->v2.Wp[g], h->v2.ldp_emb, h->v2.bp[g], h->v2_w1_grp[g], h->v2.hfm, h->v2.n_hfm, h->v2.h0w,
                                        h->v2_folded + (size_t)h->v2run.rowbase[g] * (KP + 16), KP, rows);
                     HIP_TRY(hipGetLastError());
                 }

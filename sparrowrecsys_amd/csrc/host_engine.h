@@ -72,7 +72,8 @@ struct sprk_engine {
     // register-chained fast path (k_deepfm_v2_chain); -1 = use the tile interpreter
     int v2_variant = -1;
     bool v2_rows_ok = false;       // [r6] the parsed DeepFM_v2 plan also fits k_rows_chain (where it goes when the joint set-up refuses it)
-    V2Args v2;
+    V2Args v2;                     // (w1[] in first-order order, the order of fo_col[] / fo_vocab[], wherever it is read)
+    const float* v2_w1_grp[V2_MAX_FIELDS] = {};   // the same first-order weights in embedding-group order (host only: the folded set-up)
     V2Run v2run;
     size_t v2_lds_bytes = 0;
     int v2_grid_cap = 0;

@@ -180,13 +180,13 @@ bool match_v2_chain(sprk_engine* h) {
                 fo_floats += (size_t)a.emb_vocab[g] + 1;
             }
             if (fo_floats >= ((size_t)1 << 31)) return false;
-            // w1 pointers in embedding-group order
-            const float* w1g[V2_MAX_FIELDS];
+            // w1 pointers in embedding-group order, kept apart: a.w1 stays in first-order order with a.fo_col / a.fo_vocab, so that
+            // setup_rows_v2 (where finalize sends the model when the joint set-up refuses it) matches the columns itself once
             for (int g = 0; g < g_emb; ++g) {
+                h->v2_w1_grp[g] = nullptr;
                 for (int i = 0; i < n_fo; ++i)
-                    if (a.fo_col[i] == a.emb_col[g] && a.fo_vocab[i] == a.emb_vocab[g]) w1g[g] = a.w1[i];
+                    if (a.fo_col[i] == a.emb_col[g] && a.fo_vocab[i] == a.emb_vocab[g]) h->v2_w1_grp[g] = a.w1[i];
             }
-            for (int g = 0; g < g_emb; ++g) a.w1[g] = w1g[g];
             run.F = a.F; run.ND = a.ND; run.n_num = a.n_num;
             run.h0w = a.h0w; run.fo_bias = a.fo_bias; run.head_bias = a.head_bias;
             h->v2run = run;
