@@ -86,39 +86,49 @@ static int launch_din_fused(sprk_handle h, const int32_t* ids, const float* dens
     return SPRK_OK;
 }
 
+// the history stage (h->stage): DIEN's sequence stage (GRU -> attention gate -> AUGRU), DIN's attention + weighted-sum pooling
 static int launch_din(sprk_handle h, const int32_t* ids, float* pooled, float* att, int32_t B, hipStream_t st) {
-    if (h->plan.din.enabled == 2) {                               // DIEN: GRU -> attention gate -> AUGRU, one lane per sample
-        if (att) return fail(SPRK_EINVAL, "DIEN stage has no attention output");
-        if (h->dien_frag) {
-            DienRun run = h->dien_run;
-            run.image = h->dien_frag;
-            const int ntiles = (B + 15) / 16;
-            int gridm = (ntiles + DM_WAVES - 1) / DM_WAVES;
-            if (gridm > h->num_cus * 8) gridm = h->num_cus * 8;
-            const size_t lds10 = DienFrag<10, 32>::total_pad * sizeof(float), lds16 = DienFrag<16, 32>::total_pad * sizeof(float);
-            if (h->plan.din.emb_dim == 10)
-                hipLaunchKernelGGL((k_dien_seq_mfma<10, 32>), dim3(gridm), dim3(DM_WAVES * 64), lds10, st, run, ids, pooled, B, h->dev_err);
-            else
-                hipLaunchKernelGGL((k_dien_seq_mfma<16, 32>), dim3(gridm), dim3(DM_WAVES * 64), lds16, st, run, ids, pooled, B, h->dev_err);
-            HIP_TRY(hipGetLastError());
-            return SPRK_OK;
-        }
+    if (att && (h->stage == Stage::DienSeq || h->stage == Stage::DienSeqMfma)) return fail(SPRK_EINVAL, "DIEN stage has no attention output");
+    switch (h->stage) {
+    case Stage::DinFusedAttn: return launch_din_fused(h, ids, nullptr, pooled, att, B, nullptr, false, st);
+    case Stage::DinCols: return launch_din_cols(h, ids, pooled, att, B, nullptr, st);
+    case Stage::DinPool: {
+        const int nchunks = (B + h->din_ms - 1) / h->din_ms;
+        const int grid = nchunks < h->din_grid_cap ? nchunks : h->din_grid_cap;
+        hipLaunchKernelGGL(k_din_pool, dim3(grid), dim3(256), h->din_lds_bytes, st, h->dev_plan, ids, pooled, att, B, h->din_ms, h->dev_err);
+        break;
+    }
+    case Stage::DienSeqMfma: {                                    // sixteen samples per MFMA tile
+        DienRun run = h->dien_run;
+        run.image = h->dien_frag;
+        const int ntiles = (B + 15) / 16;
+        int gridm = (ntiles + DM_WAVES - 1) / DM_WAVES;
+        if (gridm > h->num_cus * 8) gridm = h->num_cus * 8;
+        const size_t lds10 = DienFrag<10, 32>::total_pad * sizeof(float), lds16 = DienFrag<16, 32>::total_pad * sizeof(float);
+        if (h->plan.din.emb_dim == 10)
+            hipLaunchKernelGGL((k_dien_seq_mfma<10, 32>), dim3(gridm), dim3(DM_WAVES * 64), lds10, st, run, ids, pooled, B, h->dev_err);
+        else
+            hipLaunchKernelGGL((k_dien_seq_mfma<16, 32>), dim3(gridm), dim3(DM_WAVES * 64), lds16, st, run, ids, pooled, B, h->dev_err);
+        break;
+    }
+    case Stage::DienSeq: {                                        // one lane per sample
         int grid = (B + 63) / 64;
         if (grid > h->num_cus * 8) grid = h->num_cus * 8;
         if (h->plan.din.emb_dim == 10)
             hipLaunchKernelGGL((k_dien_seq<10, 32>), dim3(grid), dim3(64), 0, st, h->dien_run, ids, pooled, B, h->dev_err);
         else
             hipLaunchKernelGGL((k_dien_seq<16, 32>), dim3(grid), dim3(64), 0, st, h->dien_run, ids, pooled, B, h->dev_err);
-        HIP_TRY(hipGetLastError());
-        return SPRK_OK;
+        break;
     }
-    if (h->din_variant >= 0 && h->din_cols && h->din_fused_attn) return launch_din_fused(h, ids, nullptr, pooled, att, B, nullptr, false, st);
-    if (h->din_variant >= 0 && h->din_cols) return launch_din_cols(h, ids, pooled, att, B, nullptr, st);
-    const int nchunks = (B + h->din_ms - 1) / h->din_ms;
-    const int grid = nchunks < h->din_grid_cap ? nchunks : h->din_grid_cap;
-    hipLaunchKernelGGL(k_din_pool, dim3(grid), dim3(256), h->din_lds_bytes, st, h->dev_plan, ids, pooled, att, B, h->din_ms, h->dev_err);
+    case Stage::None: return fail(SPRK_EKIND, "handle has no DIN stage");
+    }
     HIP_TRY(hipGetLastError());
     return SPRK_OK;
+}
+
+// waves per workgroup of the k_din_tail form finalize chose (16 with raw embedding rows for emb_dim <= 16)
+static int din_tail_waves(sprk_handle h) {
+    return h->din_tail_run.e_unscale != 0.f ? dt_waves_unf(kDinTailVariants[h->din_tail_variant].kpc) : DT_WAVES;
 }
 
 int sprk_din_pool(sprk_handle h, const int32_t* ids, float* pooled, float* att, int32_t B, void* stream) {
@@ -149,16 +159,16 @@ int sprk_forward(sprk_handle h, const int32_t* ids, const float* dense, float* o
         // 8-wave workgroup per CU carries the tail's weights: up to ONE round of workgroups (16 rows x 8 waves x CUs = 32 768 rows on an
         // MI355X: BASELINE config 3, and every latency-bound request below it) a wave owns one task; a larger batch goes to the
         // persistent form (a "several batches" launch of one batch: every wave walks its tasks, tables staged once)
-        // (this branch must stay UNCONDITIONAL on din_fused: forward_many hands it the caller's whole workspace, not a per-stream slice)
-        if (h->plan.din.enabled == 1 && h->din_fused) {
+        // (this branch must stay UNCONDITIONAL on the route: forward_many hands it the caller's whole workspace, not a per-stream slice)
+        if (h->route == Route::DinFused) {
             if ((long long)((B + 15) / 16) <= (long long)h->num_cus * DF_WAVES) return launch_din_fused(h, ids, dense, out, nullptr, B, nullptr, true, st);
             DinFusedMany fm;
             memset(&fm, 0, sizeof(fm));
             fm.n = 1; fm.ids[0] = ids; fm.dense[0] = dense; fm.out[0] = out;
             return launch_din_fused(h, nullptr, nullptr, nullptr, nullptr, B, &fm, true, st);
         }
-        // DIEN in one launch (k_dien_fused): as above, the workspace is not touched and the branch is unconditional on dien_fused
-        if (h->plan.din.enabled == 2 && h->dien_fused) {
+        // DIEN in one launch (k_dien_fused): as above, the workspace is not touched and the branch is unconditional on the route
+        if (h->route == Route::DienFused) {
             DienRun run = h->dien_run;
             run.image = h->dien_frag;
             const int ntiles = (B + 15) / 16;
@@ -173,82 +183,111 @@ int sprk_forward(sprk_handle h, const int32_t* ids, const float* dense, float* o
             HIP_TRY(hipGetLastError());
             return SPRK_OK;
         }
-        int rc = launch_din(h, ids, (float*)workspace, nullptr, B, st);
-        if (rc) return rc;
+        SPRK_TRY(launch_din(h, ids, (float*)workspace, nullptr, B, st));
         aux = (const float*)workspace;
     }
-    if (h->v2_variant >= 0) {
-        const int ntasks = (B + 15) / 16;
+    const int ntasks = (B + 15) / 16;
+    const int unaligned = (((uintptr_t)ids | (uintptr_t)dense) & 15) ? 1 : 0;   // unaligned inputs: element-wise staging
+    switch (h->route) {
+    case Route::V2Joint: {
+        const V2JVariant& jv = kV2JVariants[h->v2j_variant];
+        V2JRun jr = h->v2j_run;
+        jr.flags = unaligned;
+        const V2J1Variant* one = nullptr;                          // one strict launch of one batch: one task per wave, four waves per SIMD (k_chain_v2j1.h)
+        if (h->v2j1_image && ntasks <= V2J1_MAX_TASKS)
+            for (const V2J1Variant& v : kV2J1Variants)
+                if (!one && v.g_big == jv.g_big && v.njf == jv.njf) one = &v;
+        if (one) {
+            (h->v2j1_hoist ? one->launch_h : one->launch)(jr, ids, dense, out, B, h->dev_err, h->v2j1_image, (ntasks + h->v2j1_waves - 1) / h->v2j1_waves,
+                                                          h->v2j1_lds_bytes, st);
+            break;
+        }
         int grid = (ntasks + V2_WAVES - 1) / V2_WAVES;
         if (grid > h->v2_grid_cap) grid = h->v2_grid_cap;
-        {                                                          // ([r6] a DeepFM_v2 handle always has a joint form: finalize routes the others elsewhere)
-            V2JRun jr = h->v2j_run;
-            jr.flags = (((uintptr_t)ids | (uintptr_t)dense) & 15) ? 1 : 0;  // unaligned inputs: element-wise staging
-            if (h->v2j1_image && ntasks <= V2J1_MAX_TASKS) {
-                // one strict launch of one batch: one task per wave, four waves per SIMD (k_chain_v2j1.h)
-                for (size_t v = 0; v < sizeof(kV2J1Variants) / sizeof(kV2J1Variants[0]); ++v)
-                    if (kV2J1Variants[v].g_big == kV2JVariants[h->v2j_variant].g_big && kV2J1Variants[v].njf == kV2JVariants[h->v2j_variant].njf) {
-                        (h->v2j1_hoist ? kV2J1Variants[v].launch_h : kV2J1Variants[v].launch)(jr, ids, dense, out, B, h->dev_err, h->v2j1_image,
-                                                                                                (ntasks + h->v2j1_waves - 1) / h->v2j1_waves, h->v2j1_lds_bytes, st);
-                        HIP_TRY(hipGetLastError());
-                        return SPRK_OK;
-                    }
-            }
-            kV2JVariants[h->v2j_variant].launch(jr, ids, dense, out, B, h->dev_err, h->v2_image, grid, h->v2j_lds_bytes, st);
-            HIP_TRY(hipGetLastError());
-            return SPRK_OK;
-        }
+        jv.launch(jr, ids, dense, out, B, h->dev_err, h->v2_image, grid, h->v2j_lds_bytes, st);
+        break;
     }
-    if (h->rows_variant >= 0) {
-        const int ntasks = (B + 15) / 16;
+    case Route::Rows: {
         int grid = (ntasks + RC_WAVES - 1) / RC_WAVES;
         if (grid > h->num_cus) grid = h->num_cus;                  // one 8-wave workgroup per CU (2 waves per SIMD)
         RowsRun rr = h->rows_run;
-        rr.flags = (((uintptr_t)ids | (uintptr_t)dense) & 15) ? 1 : 0;
+        rr.flags = unaligned;
         if (h->rows_one && ntasks <= V2J1_MAX_TASKS)
             kRowsVariants[h->rows_variant].launch_one(rr, ids, dense, out, B, h->dev_err, h->rows_image, (ntasks + RC_WAVES - 1) / RC_WAVES,
                                                       h->rows_lds_bytes, st);
         else
             kRowsVariants[h->rows_variant].launch(rr, ids, dense, out, B, h->dev_err, h->rows_image, grid, h->rows_lds_bytes, st);
-        HIP_TRY(hipGetLastError());
-        return SPRK_OK;
+        break;
     }
-    if (h->v1_variant >= 0) {
-        const int ntasks = (B + 15) / 16;
+    case Route::Pairs: {
         int grid = (ntasks + V1_WAVES - 1) / V1_WAVES;
         if (grid > h->num_cus) grid = h->num_cus;                  // one 8-wave workgroup per CU (2 waves per SIMD; 3 per SIMD measured slower at B = 65 536)
         if (h->v1_one && ntasks <= V1_ONE_MAX_TASKS)
             kV1Variants[h->v1_variant].launch_one(h->v1_run, ids, dense, out, B, h->dev_err, (ntasks + V1_WAVES - 1) / V1_WAVES, st);
         else
             kV1Variants[h->v1_variant].launch(h->v1_run, ids, dense, out, B, h->dev_err, grid, st);
-        HIP_TRY(hipGetLastError());
-        return SPRK_OK;
+        break;
     }
-    if (h->mlp_rows_nbig >= 0) {
-        const int ntasks = (B + 15) / 16;
+    case Route::MlpRows: {
         int grid = (ntasks + MR_WAVES - 1) / MR_WAVES;
         if (grid > h->num_cus) grid = h->num_cus;                  // one 8-wave workgroup per CU (the LDS holds weights + genre tables)
         MlpRowsRun rr = h->mlp_rows_run;
-        rr.flags = (rr.flags & ~1) | ((((uintptr_t)ids | (uintptr_t)dense) & 15) ? 1 : 0);
+        rr.flags = (rr.flags & ~1) | unaligned;
         hipLaunchKernelGGL(h->mlp_rows_kernel, dim3(grid), dim3(MR_WAVES * 64), h->mlp_rows_lds, st, rr, ids, dense, out, B, h->dev_err, (const float*)h->mlp_rows_image);
-        HIP_TRY(hipGetLastError());
-        return SPRK_OK;
+        break;
     }
-    if (h->din_tail_variant >= 0) {
-        const int ntasks = (B + 15) / 16;
-        const int tw = h->din_tail_run.e_unscale != 0.f ? dt_waves_unf(kDinTailVariants[h->din_tail_variant].kpc) : DT_WAVES;
+    case Route::DinTail: {
+        const int tw = din_tail_waves(h);
         int grid = (ntasks + tw - 1) / tw;
         if (grid > h->num_cus) grid = h->num_cus;                  // one workgroup per CU (8 waves, or 16 with raw embedding rows)
         kDinTailVariants[h->din_tail_variant].launch(h->din_tail_run, ids, dense, aux, out, B, h->dev_err, h->din_tail_image, grid, st);
-        HIP_TRY(hipGetLastError());
-        return SPRK_OK;
+        break;
     }
-    const int ntiles = (B + SPRK_TILE_M - 1) / SPRK_TILE_M;
-    const int grid = ntiles < h->tile_grid_cap ? ntiles : h->tile_grid_cap;
-    hipLaunchKernelGGL(k_tile_forward, dim3(grid), dim3(256), h->tile_lds_bytes, st, h->dev_plan, ids, dense, aux, out, B, h->dev_err);
+    default: {                                                     // Route::Tile (the one-launch DIN / DIEN routes returned above)
+        const int ntiles = (B + SPRK_TILE_M - 1) / SPRK_TILE_M;
+        const int grid = ntiles < h->tile_grid_cap ? ntiles : h->tile_grid_cap;
+        hipLaunchKernelGGL(k_tile_forward, dim3(grid), dim3(256), h->tile_lds_bytes, st, h->dev_plan, ids, dense, aux, out, B, h->dev_err);
+    }
+    }
     HIP_TRY(hipGetLastError());
     return SPRK_OK;
 }
+
+// sprk_forward_many's helper streams: streams 0 .. S-1 wait for what `st` holds so far (fork); `st` waits for all their work (join)
+static int fork_helpers(sprk_handle h, int S, hipStream_t st) {
+    HIP_TRY(hipEventRecord(h->many_fork, st));
+    for (int s = 0; s < S; ++s) HIP_TRY(hipStreamWaitEvent(h->many_stream[s], h->many_fork, 0));
+    return SPRK_OK;
+}
+static int join_helpers(sprk_handle h, int S, hipStream_t st) {
+    for (int s = 0; s < S; ++s) {
+        HIP_TRY(hipEventRecord(h->many_join[s], h->many_stream[s]));
+        HIP_TRY(hipStreamWaitEvent(st, h->many_join[s], 0));
+    }
+    return SPRK_OK;
+}
+
+// n_batches batches in launches of at most `per`: group g's *Many struct (count, per-batch pointers; dense = NULL: none) goes to launch(m, g)
+extern "C++" {
+template <class Many, class Launch>
+static int launch_groups(int32_t n_batches, int per, const int32_t* const* ids, const float* const* dense, float* const* out, Launch launch) {
+    int g = 0;
+    for (int32_t i0 = 0; i0 < n_batches; i0 += per, ++g) {
+        Many m;
+        memset(&m, 0, sizeof(m));
+        m.n = n_batches - i0 < per ? n_batches - i0 : per;
+        for (int j = 0; j < m.n; ++j) { m.ids[j] = ids[i0 + j]; m.dense[j] = dense ? dense[i0 + j] : nullptr; m.out[j] = out[i0 + j]; }
+        SPRK_TRY(launch(m, g));
+        HIP_TRY(hipGetLastError());
+    }
+    return SPRK_OK;
+}
+template <class Ok> static bool every_batch(int32_t n_batches, Ok ok) {
+    for (int32_t i = 0; i < n_batches; ++i)
+        if (!ok(i)) return false;
+    return true;
+}
+}  // extern "C++"
 
 // `many_batches` / `many_streams`: batches per launch and helper streams of THIS call (the handle itself is not touched)
 static int forward_many_impl(sprk_handle h, int32_t n_batches, const int32_t* const* ids, const float* const* dense,
@@ -262,159 +301,97 @@ static int forward_many_impl(sprk_handle h, int32_t n_batches, const int32_t* co
     // a model with a workspace (DIN: attention kernel -> pooled vectors -> tail kernel) needs one workspace slice per
     // stream; with a single slice its forwards stay in strict order
     const size_t ws_need = (sprk_workspace_bytes(h, B) + 255) & ~(size_t)255;
-    const bool ws_untouched = h->finalized && ((h->plan.din.enabled == 1 && h->din_fused) || (h->plan.din.enabled == 2 && h->dien_fused));   // (sprk_forward's k_din_fused branch: unconditional, see there)
+    const bool ws_untouched = h->finalized && (h->route == Route::DinFused || h->route == Route::DienFused);   // (sprk_forward's one-launch branches: unconditional, see there)
     if (S >= 2 && ws_need > 0 && !ws_untouched) {
         while (S >= 2 && (!workspace || workspace_bytes < (size_t)S * ws_need)) --S;
         if (S < 2) S = 0;
     }
-    // several batches per launch (sprk_set_many_batches): the fused DeepFM_v2 kernel takes up to V2J_MB batches' buffers
-    // and walks their tasks as one grid; everything else (other models, unaligned buffers, tracing) goes batch by batch
-    if (h->finalized && many_batches > 1 && n_batches > 1 && h->v2_variant >= 0 && h->v2j_variant >= 0 &&
-        B > 0 && ids && dense) {
-        bool ok = true;
-        for (int32_t i = 0; i < n_batches && ok; ++i)
-            ok = ids[i] && dense[i] && out[i] && !(((uintptr_t)ids[i] | (uintptr_t)dense[i]) & 15);
-        if (ok) {
-            const int ntpb = (B + 15) / 16;
-            const V2JVariant& jv = kV2JVariants[h->v2j_variant];
-            V2JRun jr = h->v2j_run;
-            jr.flags = 0;
-            for (int32_t i0 = 0; i0 < n_batches; i0 += many_batches) {
-                V2JMany m;
-                memset(&m, 0, sizeof(m));
-                m.n = n_batches - i0 < many_batches ? n_batches - i0 : many_batches;
-                m.ntpb = ntpb;
-                for (int j = 0; j < m.n; ++j) { m.ids[j] = ids[i0 + j]; m.dense[j] = dense[i0 + j]; m.out[j] = out[i0 + j]; }
-                const long long ntasks = (long long)m.n * ntpb;
-                long long grid = (ntasks + V2_WAVES - 1) / V2_WAVES;
-                if (grid > h->v2_grid_cap) grid = h->v2_grid_cap;
-                jv.launch_many(jr, m, B, h->dev_err, h->v2_image, (int)grid, h->v2j_lds_bytes, (hipStream_t)stream);
-                HIP_TRY(hipGetLastError());
-            }
+    hipStream_t st = (hipStream_t)stream;
+    // several batches per launch (sprk_set_many_batches): the fused kernels take up to their *_MB batches' buffers and walk their tasks
+    // as one grid; everything else (other models, unaligned buffers, tracing) goes batch by batch at the end
+    const bool grouped = h->finalized && many_batches > 1 && n_batches > 1 && B > 0 && ids;
+    const int ntpb = (B + 15) / 16;
+    auto aligned = [&](int32_t i, const float* d) { return !(((uintptr_t)ids[i] | (uintptr_t)d) & 15); };
+    auto present = [&](int32_t i) { return ids[i] && dense[i] && out[i]; };
+    if (grouped && dense && h->route == Route::V2Joint && every_batch(n_batches, [&](int32_t i) { return present(i) && aligned(i, dense[i]); })) {
+        const V2JVariant& jv = kV2JVariants[h->v2j_variant];
+        V2JRun jr = h->v2j_run;
+        jr.flags = 0;
+        return launch_groups<V2JMany>(n_batches, many_batches, ids, dense, out, [&](V2JMany& m, int) {
+            m.ntpb = ntpb;
+            long long grid = ((long long)m.n * ntpb + V2_WAVES - 1) / V2_WAVES;
+            if (grid > h->v2_grid_cap) grid = h->v2_grid_cap;
+            jv.launch_many(jr, m, B, h->dev_err, h->v2_image, (int)grid, h->v2j_lds_bytes, st);
             return SPRK_OK;
-        }
+        });
     }
     // k_rows_chain: up to RC_MB batches per launch
-    if (h->finalized && many_batches > 1 && n_batches > 1 && h->rows_variant >= 0 && B > 0 && ids && (dense || h->plan.n_dense == 0)) {
-        bool ok = true;
-        for (int32_t i = 0; i < n_batches && ok; ++i)
-            ok = ids[i] && out[i] && (h->plan.n_dense == 0 || dense[i]) && !(((uintptr_t)ids[i] | (uintptr_t)(h->plan.n_dense ? dense[i] : nullptr)) & 15);
-        if (ok) {
-            const int per = many_batches < RC_MB ? many_batches : RC_MB;
-            const int ntpb = (B + 15) / 16;
-            RowsRun rr = h->rows_run;
-            rr.flags = 0;
-            for (int32_t i0 = 0; i0 < n_batches; i0 += per) {
-                RowsMany m;
-                memset(&m, 0, sizeof(m));
-                m.n = n_batches - i0 < per ? n_batches - i0 : per;
-                m.ntpb = ntpb;
-                for (int j = 0; j < m.n; ++j) { m.ids[j] = ids[i0 + j]; m.dense[j] = h->plan.n_dense ? dense[i0 + j] : nullptr; m.out[j] = out[i0 + j]; }
-                long long grid = ((long long)m.n * ntpb + RC_WAVES - 1) / RC_WAVES;
-                if (grid > h->num_cus) grid = h->num_cus;
-                kRowsVariants[h->rows_variant].launch_many(rr, m, B, h->dev_err, h->rows_image, (int)grid, h->rows_lds_bytes, (hipStream_t)stream);
-                HIP_TRY(hipGetLastError());
-            }
+    const float* const* rows_dense = h->plan.n_dense ? dense : nullptr;
+    if (grouped && (dense || h->plan.n_dense == 0) && h->route == Route::Rows &&
+        every_batch(n_batches, [&](int32_t i) { return ids[i] && out[i] && (!rows_dense || rows_dense[i]) && aligned(i, rows_dense ? rows_dense[i] : nullptr); })) {
+        const RowsVariant& rv = kRowsVariants[h->rows_variant];
+        RowsRun rr = h->rows_run;
+        rr.flags = 0;
+        return launch_groups<RowsMany>(n_batches, many_batches < RC_MB ? many_batches : RC_MB, ids, rows_dense, out, [&](RowsMany& m, int) {
+            m.ntpb = ntpb;
+            long long grid = ((long long)m.n * ntpb + RC_WAVES - 1) / RC_WAVES;
+            if (grid > h->num_cus) grid = h->num_cus;
+            rv.launch_many(rr, m, B, h->dev_err, h->rows_image, (int)grid, h->rows_lds_bytes, st);
             return SPRK_OK;
-        }
+        });
     }
     // [r6] k_mlp_rows (EmbeddingMLP / Wide&Deep): up to MR_MB batches per launch
-    if (h->finalized && many_batches > 1 && n_batches > 1 && h->mlp_rows_nbig >= 0 && h->mlp_rows_many_kernel && B > 0 && ids && dense) {
-        bool ok = true;
-        for (int32_t i = 0; i < n_batches && ok; ++i)
-            ok = ids[i] && dense[i] && out[i] && !(((uintptr_t)ids[i] | (uintptr_t)dense[i]) & 15);
-        if (ok) {
-            const int per = many_batches < MR_MB ? many_batches : MR_MB;
-            const int ntpb = (B + 15) / 16;
-            MlpRowsRun rr = h->mlp_rows_run;
-            rr.flags &= ~1;
-            for (int32_t i0 = 0; i0 < n_batches; i0 += per) {
-                MlpRowsMany m;
-                memset(&m, 0, sizeof(m));
-                m.n = n_batches - i0 < per ? n_batches - i0 : per;
-                for (int j = 0; j < m.n; ++j) { m.ids[j] = ids[i0 + j]; m.dense[j] = dense[i0 + j]; m.out[j] = out[i0 + j]; }
-                long long grid = ((long long)m.n * ntpb + MR_WAVES - 1) / MR_WAVES;
-                if (grid > h->num_cus) grid = h->num_cus;
-                hipLaunchKernelGGL(h->mlp_rows_many_kernel, dim3((int)grid), dim3(MR_WAVES * 64), h->mlp_rows_lds, (hipStream_t)stream, rr, m, B, h->dev_err,
-                                   (const float*)h->mlp_rows_image);
-                HIP_TRY(hipGetLastError());
-            }
+    if (grouped && dense && h->route == Route::MlpRows && h->mlp_rows_many_kernel &&
+        every_batch(n_batches, [&](int32_t i) { return present(i) && aligned(i, dense[i]); })) {
+        MlpRowsRun rr = h->mlp_rows_run;
+        rr.flags &= ~1;
+        return launch_groups<MlpRowsMany>(n_batches, many_batches < MR_MB ? many_batches : MR_MB, ids, dense, out, [&](MlpRowsMany& m, int) {
+            long long grid = ((long long)m.n * ntpb + MR_WAVES - 1) / MR_WAVES;
+            if (grid > h->num_cus) grid = h->num_cus;
+            hipLaunchKernelGGL(h->mlp_rows_many_kernel, dim3((int)grid), dim3(MR_WAVES * 64), h->mlp_rows_lds, st, rr, m, B, h->dev_err,
+                               (const float*)h->mlp_rows_image);
             return SPRK_OK;
-        }
+        });
     }
     // the pairwise-dot DeepFM kernel: up to V1_MB batches per launch
-    if (h->finalized && many_batches > 1 && n_batches > 1 && h->v2_variant < 0 && h->v1_variant >= 0 && B > 0 && ids && dense) {
-        bool ok = true;
-        for (int32_t i = 0; i < n_batches && ok; ++i) ok = ids[i] && dense[i] && out[i];
-        if (ok) {
-            const int per = many_batches < V1_MB ? many_batches : V1_MB;
-            const int ntpb = (B + 15) / 16;
-            for (int32_t i0 = 0; i0 < n_batches; i0 += per) {
-                V1Many m;
-                memset(&m, 0, sizeof(m));
-                m.n = n_batches - i0 < per ? n_batches - i0 : per;
-                m.ntpb = ntpb;
-                for (int j = 0; j < m.n; ++j) { m.ids[j] = ids[i0 + j]; m.dense[j] = dense[i0 + j]; m.out[j] = out[i0 + j]; }
-                long long grid = ((long long)m.n * ntpb + V1_WAVES - 1) / V1_WAVES;
-                if (grid > h->num_cus) grid = h->num_cus;
-                kV1Variants[h->v1_variant].launch_many(h->v1_run, m, B, h->dev_err, (int)grid, (hipStream_t)stream);
-                HIP_TRY(hipGetLastError());
-            }
+    if (grouped && dense && h->route == Route::Pairs && every_batch(n_batches, present)) {
+        const V1Variant& vv = kV1Variants[h->v1_variant];
+        return launch_groups<V1Many>(n_batches, many_batches < V1_MB ? many_batches : V1_MB, ids, dense, out, [&](V1Many& m, int) {
+            m.ntpb = ntpb;
+            long long grid = ((long long)m.n * ntpb + V1_WAVES - 1) / V1_WAVES;
+            if (grid > h->num_cus) grid = h->num_cus;
+            vv.launch_many(h->v1_run, m, B, h->dev_err, (int)grid, st);
             return SPRK_OK;
-        }
+        });
     }
     // DIN on k_din_fused: up to DF_MB batches per launch, one PERSISTENT launch does everything (k_din_fused.h: tables staged once, the
     // waves walk the tasks on their own); groups alternate over the helper streams.  32.2 us per batch of BASELINE config 3 against
     // 33.4 for the two-launch pipeline below on the same box (profiles/r04; SPRK_DIN_FUSED_MB=0 brings the pipeline back)
-    if (h->finalized && many_batches > 1 && n_batches > 1 && h->plan.din.enabled == 1 && h->din_fused && h->tune.din_fused_mb && B > 0 && ids && dense) {
-        const int per = many_batches < DF_MB ? many_batches : DF_MB;
-        bool ok = true;
-        for (int32_t i = 0; i < n_batches && ok; ++i) ok = ids[i] && dense[i] && out[i];
-        if (ok) {
-            const int SG = S >= 2 ? S : 1;
-            if (SG >= 2) {
-                HIP_TRY(hipEventRecord(h->many_fork, (hipStream_t)stream));
-                for (int s = 0; s < SG; ++s) HIP_TRY(hipStreamWaitEvent(h->many_stream[s], h->many_fork, 0));
-            }
-            int g = 0;
-            for (int32_t i0 = 0; i0 < n_batches; i0 += per, ++g) {
-                DinFusedMany fm;
-                memset(&fm, 0, sizeof(fm));
-                fm.n = n_batches - i0 < per ? n_batches - i0 : per;
-                for (int j = 0; j < fm.n; ++j) { fm.ids[j] = ids[i0 + j]; fm.dense[j] = dense[i0 + j]; fm.out[j] = out[i0 + j]; }
-                const int rcf = launch_din_fused(h, nullptr, nullptr, nullptr, nullptr, B, &fm, true, SG >= 2 ? h->many_stream[g % SG] : (hipStream_t)stream);
-                if (rcf) return rcf;
-            }
-            if (SG >= 2) {
-                for (int s = 0; s < SG; ++s) {
-                    HIP_TRY(hipEventRecord(h->many_join[s], h->many_stream[s]));
-                    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, h->many_join[s], 0));
-                }
-            }
-            return SPRK_OK;
-        }
+    if (grouped && dense && h->route == Route::DinFused && h->tune.din_fused_mb && every_batch(n_batches, present)) {
+        const int SG = S >= 2 ? S : 1;
+        if (SG >= 2) SPRK_TRY(fork_helpers(h, SG, st));
+        SPRK_TRY(launch_groups<DinFusedMany>(n_batches, many_batches < DF_MB ? many_batches : DF_MB, ids, dense, out, [&](DinFusedMany& m, int g) {
+            return launch_din_fused(h, nullptr, nullptr, nullptr, nullptr, B, &m, true, SG >= 2 ? h->many_stream[g % SG] : st);
+        }));
+        if (SG >= 2) SPRK_TRY(join_helpers(h, SG, st));
+        return SPRK_OK;
     }
-    // DIN (k_din_attn -> pooled vectors -> k_din_tail): the attention launches of a group of batches, then ONE tail launch for
+    // DIN (k_din_attn_cols -> pooled vectors -> k_din_tail): the attention launches of a group of batches, then ONE tail launch for
     // the group; a workspace slice per batch of the group.  Groups alternate over the helper streams when there are slices for that.
-    if (h->finalized && many_batches > 1 && n_batches > 1 && h->plan.din.enabled == 1 && h->din_variant >= 0 &&
-        h->din_tail_variant >= 0 && B > 0 && ids && dense && workspace && ws_need > 0) {
+    const bool cols = h->stage == Stage::DinCols || h->stage == Stage::DinFusedAttn;
+    if (grouped && dense && workspace && ws_need > 0 && cols && (h->route == Route::DinTail || h->route == Route::DinFused)) {
         int per = many_batches < DIN_MB ? many_batches : DIN_MB;
         if ((size_t)per * ws_need > workspace_bytes) per = (int)(workspace_bytes / ws_need);
-        bool ok = per >= 2;
-        for (int32_t i = 0; i < n_batches && ok; ++i) ok = ids[i] && dense[i] && out[i];
-        if (ok) {
+        if (per >= 2 && every_batch(n_batches, present)) {
             int SG = S >= 2 ? S : 1;                                   // streams the groups alternate over
             while (SG > 1 && (size_t)SG * per * ws_need > workspace_bytes) --SG;
-            if (SG >= 2) {
-                HIP_TRY(hipEventRecord(h->many_fork, (hipStream_t)stream));
-                for (int s = 0; s < SG; ++s) HIP_TRY(hipStreamWaitEvent(h->many_stream[s], h->many_fork, 0));
-            }
+            if (SG >= 2) SPRK_TRY(fork_helpers(h, SG, st));
             const DinTailVariant& tv = kDinTailVariants[h->din_tail_variant];
-            const int ntpb = (B + 15) / 16;
+            const int tw = din_tail_waves(h);
             int g = 0;
             for (int32_t i0 = 0; i0 < n_batches; i0 += per, ++g) {
                 const int n = n_batches - i0 < per ? n_batches - i0 : per;
-                hipStream_t st = SG >= 2 ? h->many_stream[g % SG] : (hipStream_t)stream;
+                hipStream_t sg = SG >= 2 ? h->many_stream[g % SG] : st;
                 char* wbase = (char*)workspace + (size_t)(g % SG) * per * ws_need;
                 DinTailMany tm;
                 memset(&tm, 0, sizeof(tm));
@@ -423,55 +400,36 @@ static int forward_many_impl(sprk_handle h, int32_t n_batches, const int32_t* co
                     float* pooled = (float*)(wbase + (size_t)j * ws_need);
                     tm.ids[j] = ids[i0 + j]; tm.dense[j] = dense[i0 + j]; tm.aux[j] = pooled; tm.out[j] = out[i0 + j];
                 }
-                // ONE attention launch for the group (k_din_attn<..., MB = true>: no launch boundary and no partial last round of waves
-                // between the batches), then one tail launch
-                if (h->din_attn_many && n <= DC_MB) {                   // (din_variant >= 0 <=> k_din_attn_cols' tables exist)
+                // ONE attention launch for the group (k_din_attn_cols<..., MB = true>: no launch boundary and no partial last round of
+                // waves between the batches), then one tail launch
+                if (n <= DC_MB) {
                     DinColsMany cm;
                     memset(&cm, 0, sizeof(cm));
                     cm.n = n;
                     for (int j = 0; j < n; ++j) { cm.ids[j] = tm.ids[j]; cm.pooled[j] = const_cast<float*>(tm.aux[j]); }
-                    const int rcc = launch_din_cols(h, nullptr, nullptr, nullptr, B, &cm, st);
-                    if (rcc) return rcc;
+                    SPRK_TRY(launch_din_cols(h, nullptr, nullptr, nullptr, B, &cm, sg));
                 } else {
-                    for (int j = 0; j < n; ++j) {
-                        const int rcc = launch_din_cols(h, tm.ids[j], const_cast<float*>(tm.aux[j]), nullptr, B, nullptr, st);
-                        if (rcc) return rcc;
-                    }
+                    for (int j = 0; j < n; ++j) SPRK_TRY(launch_din_cols(h, tm.ids[j], const_cast<float*>(tm.aux[j]), nullptr, B, nullptr, sg));
                 }
-                const int tw = h->din_tail_run.e_unscale != 0.f ? dt_waves_unf(kDinTailVariants[h->din_tail_variant].kpc) : DT_WAVES;
                 long long tg = ((long long)n * ntpb + tw - 1) / tw;
                 if (tg > h->num_cus) tg = h->num_cus;
-                tv.launch_many(h->din_tail_run, tm, B, h->dev_err, h->din_tail_image, (int)tg, st);
+                tv.launch_many(h->din_tail_run, tm, B, h->dev_err, h->din_tail_image, (int)tg, sg);
                 HIP_TRY(hipGetLastError());
             }
-            if (SG >= 2) {
-                for (int s = 0; s < SG; ++s) {
-                    HIP_TRY(hipEventRecord(h->many_join[s], h->many_stream[s]));
-                    HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, h->many_join[s], 0));
-                }
-            }
+            if (SG >= 2) SPRK_TRY(join_helpers(h, SG, st));
             return SPRK_OK;
         }
     }
-    if (S >= 2) {
-        HIP_TRY(hipEventRecord(h->many_fork, (hipStream_t)stream));
-        for (int s = 0; s < S; ++s) HIP_TRY(hipStreamWaitEvent(h->many_stream[s], h->many_fork, 0));
-    }
+    if (S >= 2) SPRK_TRY(fork_helpers(h, S, st));
     for (int32_t i = 0; i < n_batches; ++i) {
         // (one workspace slice per stream -- except for the one-launch DIN, whose S was NOT reduced to the slices the buffer holds because
         //  its forward never touches the buffer: it gets the caller's buffer and size unchanged, never an offset past its end [ADVICE r04])
         const bool sliced = S >= 2 && ws_need > 0 && !ws_untouched;
         void* wsi = sliced ? (void*)((char*)workspace + (size_t)(i % S) * ws_need) : workspace;
-        const int rc = sprk_forward(h, ids ? ids[i] : nullptr, dense ? dense[i] : nullptr, out[i], B, wsi,
-                                    sliced ? ws_need : workspace_bytes, S >= 2 ? (void*)h->many_stream[i % S] : stream);
-        if (rc) return rc;
+        SPRK_TRY(sprk_forward(h, ids ? ids[i] : nullptr, dense ? dense[i] : nullptr, out[i], B, wsi,
+                              sliced ? ws_need : workspace_bytes, S >= 2 ? (void*)h->many_stream[i % S] : stream));
     }
-    if (S >= 2) {
-        for (int s = 0; s < S; ++s) {
-            HIP_TRY(hipEventRecord(h->many_join[s], h->many_stream[s]));
-            HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, h->many_join[s], 0));
-        }
-    }
+    if (S >= 2) SPRK_TRY(join_helpers(h, S, st));
     return SPRK_OK;
 }
 
@@ -526,35 +484,43 @@ int sprk_describe(sprk_handle h, char* buf, size_t buf_bytes) {
     if (!h || !buf || buf_bytes == 0) return fail(SPRK_EINVAL, "describe: NULL argument");
     if (!h->finalized) return fail(SPRK_ESTATE, "describe before finalize");
     char kern[160];
-    if (h->v2_variant >= 0 && h->v2j_variant >= 0) {
+    switch (h->route) {
+    case Route::V2Joint: {
         const V2JVariant& jv = kV2JVariants[h->v2j_variant];
         snprintf(kern, sizeof(kern), "k_deepfm_v2_joint<G_BIG=%d,NJF=%d,KPC=%d,%s>", jv.g_big, jv.njf, jv.kpc, jv.half ? "split-f16" : "f32");
-    } else if (h->v1_variant >= 0) {
+        break;
+    }
+    case Route::Pairs:
         snprintf(kern, sizeof(kern), "k_deepfm_pairs<NF=%d,NV=%d>", kV1Variants[h->v1_variant].nf, kV1Variants[h->v1_variant].nv);
-    } else if (h->rows_variant >= 0) {
+        break;
+    case Route::Rows: {
         const RowsVariant& rv = kRowsVariants[h->rows_variant];
         snprintf(kern, sizeof(kern), "k_rows_chain<KPC=%d,H0C=%d,H1C=%d,G_BIG=%d,NJF=%d%s>", rv.kpc, rv.h0c, rv.h1c, rv.g_big, rv.njf,
                  rv.unf ? ",UNF" : "");
-    } else if (h->mlp_rows_nbig >= 0) {
+        break;
+    }
+    case Route::MlpRows:
         snprintf(kern, sizeof(kern), "k_mlp_rows<8,8,NBIG=%d,NSMALL=%d>", h->mlp_rows_nbig, h->mlp_rows_run.n_small);
-    } else if (h->din_tail_variant >= 0) {
+        break;
+    case Route::DinTail: {
         const DinTailVariant& tv = kDinTailVariants[h->din_tail_variant];
         snprintf(kern, sizeof(kern), "k_din_tail<%d,%d,%d%s>", tv.n0c, tv.n1c, tv.kpc, h->din_tail_run.e_unscale != 0.f ? ",UNF" : "");
-    } else {
-        snprintf(kern, sizeof(kern), "k_tile_forward");
+        break;
     }
-    const char* stage = "";
-    if (h->plan.din.enabled == 2) stage = h->dien_frag ? "k_dien_seq_mfma" : "k_dien_seq";
-    else if (h->plan.din.enabled == 1) stage = h->din_variant < 0 ? "k_din_pool" : (h->din_fused_attn ? "k_din_fused" : "k_din_attn_cols");
-    if (h->plan.din.enabled == 1 && h->din_fused) snprintf(kern, sizeof(kern), "k_din_fused<KC=%d,tail 128/64>", h->din_cols_kc);
-    if (h->plan.din.enabled == 2 && h->dien_fused) snprintf(kern, sizeof(kern), "k_dien_fused<D=%d,tail 128/64>", h->plan.din.emb_dim);   // (stage: what sprk_din_pool runs)
+    case Route::DinFused: snprintf(kern, sizeof(kern), "k_din_fused<KC=%d,tail 128/64>", h->din_cols_kc); break;
+    case Route::DienFused: snprintf(kern, sizeof(kern), "k_dien_fused<D=%d,tail 128/64>", h->plan.din.emb_dim); break;
+    case Route::Tile: snprintf(kern, sizeof(kern), "k_tile_forward"); break;
+    }
+    // stage: what sprk_din_pool runs, in the order of enum Stage
+    static const char* const kStageName[] = {"", "k_din_pool", "k_din_attn_cols", "k_din_fused", "k_dien_seq", "k_dien_seq_mfma"};
+    const bool cols = h->stage == Stage::DinCols || h->stage == Stage::DinFusedAttn;
     size_t uploaded = 0;
     for (size_t b : h->slot_bytes) uploaded += b;
 #ifndef SPRK_BUILD_DEFINES_STR
 #define SPRK_BUILD_DEFINES_STR ""                             // (_lib.build_library passes the experiment defines of SPRK_BUILD_DEFINES; the product build has none)
 #endif
-    const int n = snprintf(buf, buf_bytes, "kernel=%s;stage=%s;stage_waves_per_workgroup=%d;fused=%d;uploaded_bytes=%zu;derived_bytes=%zu;first_dense_fold=%d;build_defines=%s", kern, stage,
-                           h->din_variant >= 0 ? DC_WAVES : 0, strcmp(kern, "k_tile_forward") != 0 ? 1 : 0, uploaded, h->derived_bytes, h->n_acc_folded, SPRK_BUILD_DEFINES_STR);
+    const int n = snprintf(buf, buf_bytes, "kernel=%s;stage=%s;stage_waves_per_workgroup=%d;fused=%d;uploaded_bytes=%zu;derived_bytes=%zu;first_dense_fold=%d;build_defines=%s", kern,
+                           kStageName[(int)h->stage], cols ? DC_WAVES : 0, h->route != Route::Tile ? 1 : 0, uploaded, h->derived_bytes, h->n_acc_folded, SPRK_BUILD_DEFINES_STR);
     if (n < 0 || (size_t)n >= buf_bytes) return fail(SPRK_EINVAL, "describe: buffer of %zu bytes is too small", buf_bytes);
     return SPRK_OK;
 }
@@ -604,35 +570,11 @@ void sprk_destroy(sprk_handle h) {
     }
 #endif
     if (!h) return;
-    for (size_t i = 0; i < h->slot_ptr.size(); ++i)
-        if (h->slot_ptr[i] && !h->slot_external[i]) (void)hipFree(h->slot_ptr[i]);
-    if (h->dev_plan) (void)hipFree(h->dev_plan);
-    if (h->v2_image) (void)hipFree(h->v2_image);
-    if (h->v2_fo_all) (void)hipFree(h->v2_fo_all);
-    table_free(h, h->v2_folded);
+    for (size_t i = 0; i < h->slot_ptr.size(); ++i) free_slot(h, i);
+    for (const sprk_engine::DevAlloc& a : h->allocs) release(a);
     if (h->v2j_tab) (void)hipFree(h->v2j_tab);
-    for (void* p : h->fold_bufs) if (p) (void)hipFree(p);
     for (int i = 0; i < 4; ++i) { if (h->many_stream[i]) (void)hipStreamDestroy(h->many_stream[i]); if (h->many_join[i]) (void)hipEventDestroy(h->many_join[i]); }
     if (h->many_fork) (void)hipEventDestroy(h->many_fork);
-    if (h->din_tail_image) (void)hipFree(h->din_tail_image);
-    if (h->din_fused_image) (void)hipFree(h->din_fused_image);
-    if (h->mlp_rows_image) (void)hipFree(h->mlp_rows_image);
-    if (h->mlp_rows_small) (void)hipFree(h->mlp_rows_small);
-    for (void* q : h->mlp_rows_bufs) table_free(h, q);
-    for (void* p : h->v1_bufs) table_free(h, p);
-    table_free(h, h->v2j_big);
-    if (h->v2j1_image) (void)hipFree(h->v2j1_image);
-    if (h->din_frag) (void)hipFree(h->din_frag);
-    if (h->dien_frag) (void)hipFree(h->dien_frag);
-    table_free(h, h->rows_tab);
-    if (h->rows_scal) (void)hipFree(h->rows_scal);
-    if (h->rows_small) (void)hipFree(h->rows_small);
-    if (h->rows_image) (void)hipFree(h->rows_image);
-    if (h->din_w12) (void)hipFree(h->din_w12);
-    if (h->din_w4) (void)hipFree(h->din_w4);
-    if (h->din_vc) (void)hipFree(h->din_vc);
-    if (h->din_tsplit) (void)hipFree(h->din_tsplit);
-    if (h->dev_err) (void)hipFree(h->dev_err);
     delete h;
 }
 

@@ -25,18 +25,24 @@ inline int fail(int code, const char* fmt, ...) {
         hipError_t e_ = (expr);                                                            \
         if (e_ != hipSuccess) return fail(SPRK_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+// a call that returns an SPRK_* code: hand a failure on
+#define SPRK_TRY(expr)                                                                     \
+    do {                                                                                   \
+        if (const int rc_ = (expr)) return rc_;                                            \
+    } while (0)
 
-// ---- roctx ranges around the C ABI's entry points (SURVEY.md section 5: "roctx ranges in the C-ABI") ----
-// A finalize-time probe buffer (an abs-max word, a flag): freed on EVERY way out of its scope, also when a HIP_TRY in between returns
-// (the early returns between hipMalloc and hipFree leaked it).
-struct DevProbe {
-    unsigned* p = nullptr;
-    ~DevProbe() { if (p) (void)hipFree(p); }
-    DevProbe() = default;
-    DevProbe(const DevProbe&) = delete;
-    DevProbe& operator=(const DevProbe&) = delete;
+// Scratch device memory of one finalize-time helper (an abs-max probe, a counter, a staging buffer): freed on EVERY way out of its
+// scope, also when a HIP_TRY in between returns (the early returns between hipMalloc and hipFree leaked it).
+template <class T> struct DevScratch {
+    T* p = nullptr;
+    DevScratch() = default;
+    ~DevScratch() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc((void**)&p, n * sizeof(T)); }
+    DevScratch(const DevScratch&) = delete;
+    DevScratch& operator=(const DevScratch&) = delete;
 };
 
+// ---- roctx ranges around the C ABI's entry points (SURVEY.md section 5: "roctx ranges in the C-ABI") ----
 // SPRK_ROCTX=1 binds rocprofiler-sdk's roctx at first use (dlopen: no link-time dependency) and every forward / ingest /
 // exchange call then shows up as a named range in `rocprofv3 --marker-trace`; otherwise the cost is one predictable branch.
 struct Roctx {
@@ -74,7 +80,7 @@ struct SprkTuning {
     bool force_interpreter = false;   // SPRK_FORCE_INTERPRETER=1   every plan on k_tile_forward
     bool v2_fold = true;              // SPRK_V2_FOLD=0             DeepFM_v2: projections computed per sample instead of folded tables
     bool v2_rows = false;             // SPRK_V2_ROWS=1             DeepFM_v2 on k_rows_chain even where k_deepfm_v2_joint fits
-    bool v2_joint = true;             // SPRK_V2_JOINT=0            no LDS-resident small fields (k_deepfm_v2_chain)
+    bool v2_joint = true;             // SPRK_V2_JOINT=0            no LDS-resident small fields: DeepFM_v2 on k_rows_chain or the interpreter
     bool v2_half = true;              // SPRK_V2_HALF=0             big fields on f32 MFMA instead of split f16
     bool v2j_one = true;              // SPRK_V2J_ONE=0             one-batch launches on the looped kernel, not k_deepfm_v2_joint1
     int v2j1_hoist = -1;              // SPRK_V2J1_HOIST=0|1        k_deepfm_v2_joint1's weight fragments read behind / in front of the gathers (default: by table size)

@@ -122,4 +122,17 @@ int validate_plan(const sprk_plan& p) {
     return SPRK_OK;
 }
 
+int need_bytes(const sprk_engine* h, int slot, size_t bytes, const char* what) {
+    if (!h->slot_ptr[slot]) return fail(SPRK_ESTATE, "%s: slot %d was never uploaded", what, slot);
+    if (h->slot_bytes[slot] < bytes) return fail(SPRK_EINVAL, "%s: slot %d holds %zu bytes, needs %zu", what, slot, h->slot_bytes[slot], bytes);
+    return SPRK_OK;
+}
+
+// grid cap of a kernel whose workgroups take `lds` bytes: as many per CU as 160 KB of LDS hold, 1 .. 8
+int lds_grid_cap(const sprk_engine* h, size_t lds) {
+    int per_cu = (int)(160 * 1024 / (lds ? lds : 1));
+    if (per_cu > 8) per_cu = 8;
+    if (per_cu < 1) per_cu = 1;
+    return h->num_cus * per_cu;
+}
 

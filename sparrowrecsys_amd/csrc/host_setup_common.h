@@ -1,4 +1,5 @@
-// host_setup_common.h -- the attention stage's shape table, the interpreter's first-Dense fold, the dynamic-range guard, split-f16 fragment packing.
+// host_setup_common.h -- the attention stage's shape table, the interpreter's first-Dense fold, the static split-f16 scales (max |x| on the
+// device, the dynamic-range guard, the power of two), split-f16 fragment packing.
 // Part of sparrow_hip.hip (one translation unit); included there, not compilable on its own.
 // ---- the attention shapes k_din_attn_cols / k_din_fused take ([r6] until round 6 the dispatch table of k_din_attn: k_din_attn.h) ----
 struct DinVariant { int kc, hc, max_t; };        // emb_dim in (16 (kc - 1), 16 kc], attention hidden 16 hc, history slots <= max_t
@@ -73,16 +74,14 @@ int fold_first_dense(sprk_engine* h, DevPlan* dp) {
     // W^T copy with the folded columns inside the hull zeroed; F tables
     const size_t wbytes = (size_t)op.N * op.ldw * sizeof(float);
     float* wcopy = nullptr;
-    HIP_TRY(hipMalloc((void**)&wcopy, wbytes + 16));
-    h->fold_bufs.push_back(wcopy);
+    SPRK_TRY(dev_alloc(h, &wcopy, wbytes + 16));
     HIP_TRY(hipMemcpy(wcopy, op.W, wbytes, hipMemcpyDeviceToDevice));
     bool first = true;
     for (int i : fold) {
         DevSeg& sg = dp->segs[i];
         float* F = nullptr;
-        HIP_TRY(hipMalloc((void**)&F, (size_t)sg.vocab * op.N * sizeof(float) + 16));
+        SPRK_TRY(dev_alloc(h, &F, (size_t)sg.vocab * op.N * sizeof(float) + 16));
         h->derived_bytes += (size_t)sg.vocab * op.N * sizeof(float);
-        h->fold_bufs.push_back(F);
         long long blocks = ((long long)sg.vocab * op.N + 255) / 256;
         if (blocks > 65536) blocks = 65536;
         hipLaunchKernelGGL(k_fold_dense_rows, dim3((unsigned)blocks), dim3(256), 0, 0, sg.table, (long long)sg.vocab, sg.row_stride,
@@ -121,19 +120,44 @@ int wide_dynamic_range(const float* rows, long long nrows, int row_floats, int n
     *wide = false;
     const bool guard_on = g_finalize_tune ? g_finalize_tune->half_range_guard : SprkTuning::from_env().half_range_guard;
     if (!guard_on || !(mx > 0.f) || nrows <= 0) return SPRK_OK;
-    unsigned long long* d_cnt = nullptr;
-    HIP_TRY(hipMalloc((void**)&d_cnt, 2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemset(d_cnt, 0, 2 * sizeof(unsigned long long)));
+    DevScratch<unsigned long long> d_cnt;
+    HIP_TRY(d_cnt.alloc(2));
+    HIP_TRY(hipMemset(d_cnt.p, 0, 2 * sizeof(unsigned long long)));
     long long blocks = (nrows * ncols + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(k_v2_count_small, dim3((unsigned)blocks), dim3(256), 0, 0, rows, nrows, row_floats, ncols, ldexpf(mx, -20), d_cnt);
+    hipLaunchKernelGGL(k_v2_count_small, dim3((unsigned)blocks), dim3(256), 0, 0, rows, nrows, row_floats, ncols, ldexpf(mx, -20), d_cnt.p);
     HIP_TRY(hipGetLastError());
     unsigned long long cnt[2] = {0, 0};
-    HIP_TRY(hipMemcpy(cnt, d_cnt, sizeof(cnt), hipMemcpyDeviceToHost));
-    (void)hipFree(d_cnt);
+    HIP_TRY(hipMemcpy(cnt, d_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost));
     *wide = cnt[0] * 1024ull > cnt[1];
     return SPRK_OK;
 }
+
+// A static split-f16 scale: the power of two that puts m * scale in [2^14, 2^15), the exponent clamped to +-60; 1 for m <= 0.
+float pow2_scale(float m) {
+    int e = 0;
+    if (m > 0.f) { (void)frexpf(m, &e); e = 15 - e; }
+    if (e > 60) e = 60;
+    if (e < -60) e = -60;
+    return ldexpf(1.f, e);
+}
+
+// max |x| over tables on the device (k_v2_absmax): job j reads the first `ncols` floats of `rows` rows `row_floats` apart with `grid`
+// workgroups and folds them into mx[j.slot]; mx[0 .. n_out) come back to the host.
+struct AbsmaxJob { const float* x; long long rows; int row_floats, ncols; unsigned grid; int slot; };
+int device_absmax(const std::vector<AbsmaxJob>& jobs, float* mx, int n_out) {
+    DevScratch<unsigned> d_max;
+    HIP_TRY(d_max.alloc(n_out));
+    HIP_TRY(hipMemset(d_max.p, 0, n_out * sizeof(unsigned)));
+    for (const AbsmaxJob& j : jobs)
+        hipLaunchKernelGGL(k_v2_absmax, dim3(j.grid), dim3(256), 0, 0, j.x, j.rows, j.row_floats, j.ncols, d_max.p + j.slot);
+    HIP_TRY(hipGetLastError());
+    static_assert(sizeof(unsigned) == sizeof(float), "k_v2_absmax keeps float bits in an unsigned word");
+    HIP_TRY(hipMemcpy(mx, d_max.p, n_out * sizeof(float), hipMemcpyDeviceToHost));
+    return SPRK_OK;
+}
+// the grid of one job over n floats: a workgroup per 256 floats, at most `cap`
+unsigned absmax_grid(long long n, long long cap) { const long long b = (n + 255) / 256; return (unsigned)(b < cap ? b : cap); }
 
 // A Dense layer's W^T [N][ld] (K columns) as split-f16 A fragments for the per-sample dynamic-scale path (dyn_split.h):
 // static power-of-two scale putting max |W| in [2^14, 2^15).  *frag stays NULL when switched off (SPRK_DYN_F16=0), when
@@ -143,26 +167,16 @@ int make_dyn_fragments(sprk_engine* h, const float* W, int ld, int N, int K, flo
     *frag = nullptr;
     if (kvalid < 0) kvalid = K;
     if (!h->tune.dyn_f16 || (N & 15) || (K & 31) || kvalid < 1 || kvalid > K) return SPRK_OK;
-    DevProbe d_max_probe;
-    unsigned*& d_max = d_max_probe.p;
-    HIP_TRY(hipMalloc((void**)&d_max, sizeof(unsigned)));
-    HIP_TRY(hipMemset(d_max, 0, sizeof(unsigned)));
-    hipLaunchKernelGGL(k_v2_absmax, dim3(8), dim3(256), 0, 0, W, (long long)N, ld, kvalid, d_max);
-    unsigned bits = 0;
-    HIP_TRY(hipMemcpy(&bits, d_max, sizeof(bits), hipMemcpyDeviceToHost));
-    float mx;
-    memcpy(&mx, &bits, sizeof(mx));
+    float mx = 0.f;
+    SPRK_TRY(device_absmax({{W, (long long)N, ld, kvalid, 8, 0}}, &mx, 1));
     if (!(mx < 3.0e38f)) return SPRK_OK;
     bool wide = false;
-    if (int rcw = wide_dynamic_range(W, (long long)N, ld, kvalid, mx, &wide)) return rcw;
+    SPRK_TRY(wide_dynamic_range(W, (long long)N, ld, kvalid, mx, &wide));
     if (wide) return SPRK_OK;
-    int e = 0;
-    float w_scale = 1.f;
-    if (mx > 0.f) { (void)frexpf(mx, &e); e = 15 - e; if (e > 60) e = 60; if (e < -60) e = -60; w_scale = ldexpf(1.f, e); }
+    const float w_scale = pow2_scale(mx);
     const size_t frag_floats = (size_t)(N / 16) * (K / 32) * 512;
     float* f = nullptr;
-    HIP_TRY(hipMalloc((void**)&f, frag_floats * sizeof(float)));
-    h->fold_bufs.push_back(f);
+    SPRK_TRY(dev_alloc(h, &f, frag_floats * sizeof(float)));
     hipLaunchKernelGGL(k_dyn_pack_w, dim3(32), dim3(256), 0, 0, W, ld, N, K, w_scale, reinterpret_cast<_Float16*>(f), kvalid);
     HIP_TRY(hipGetLastError());
     *frag = f;

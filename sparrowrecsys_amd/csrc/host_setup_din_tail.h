@@ -1,4 +1,5 @@
-// host_setup_din_tail.h -- DIN / DIEN tail: k_din_tail dispatch table and set-up -- closes the host helpers' anonymous namespace.
+// host_setup_din_tail.h -- DIN / DIEN tail: k_din_tail dispatch table and set-up, the tail of k_din_fused / k_dien_fused -- closes the host
+// helpers' anonymous namespace.
 // Part of sparrow_hip.hip (one translation unit); included there, not compilable on its own.
 // ---- dispatch table for k_din_tail<N0C, N1C, KPC, WAVES> ----
 constexpr int DT_WAVES = 8;
@@ -103,7 +104,7 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
         const DevSeg& sg = dp->segs[n_plain + g];
         r.col[g] = h->idc[sg.field]; r.vocab[g] = sg.vocab; r.Ftab[g] = sg.table;
     }
-    HIP_TRY(hipMalloc((void**)&h->din_tail_image, tv.lds_bytes));
+    SPRK_TRY(dev_alloc(h, &h->din_tail_image, tv.lds_bytes));
     // DYN: fc1's weights split into f16 hi / lo fragments with a static power-of-two scale
     float* w1frag = nullptr;
     {
@@ -139,28 +140,20 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
         // one static scale for all columns' rows; an outlier row keeps the folded tables
         float mx = 0.f;
         if (ok) {
-            DevProbe d_max_probe;
-            unsigned*& d_max = d_max_probe.p;
-            HIP_TRY(hipMalloc((void**)&d_max, sizeof(unsigned)));
-            HIP_TRY(hipMemset(d_max, 0, sizeof(unsigned)));
+            std::vector<AbsmaxJob> jobs;
             for (int g = 0; g < dp->n_acc; ++g)
-                hipLaunchKernelGGL(k_v2_absmax, dim3(256), dim3(256), 0, 0, (const float*)h->slot_ptr[raw[g]->slot], (long long)raw[g]->vocab,
-                                   raw[g]->row_stride, 4 * raw[g]->count, d_max);
-            HIP_TRY(hipGetLastError());
-            unsigned bits = 0;
-            HIP_TRY(hipMemcpy(&bits, d_max, sizeof(bits), hipMemcpyDeviceToHost));
-            memcpy(&mx, &bits, sizeof(mx));
+                jobs.push_back({(const float*)h->slot_ptr[raw[g]->slot], (long long)raw[g]->vocab, raw[g]->row_stride, 4 * raw[g]->count, 256, 0});
+            SPRK_TRY(device_absmax(jobs, &mx, 1));
             ok = mx < 3.0e38f;
             for (int g = 0; g < dp->n_acc && ok; ++g) {
                 bool wide = false;
-                if (int rcw = wide_dynamic_range((const float*)h->slot_ptr[raw[g]->slot], (long long)raw[g]->vocab, raw[g]->row_stride,
-                                                 4 * raw[g]->count, mx, &wide)) return rcw;
+                SPRK_TRY(wide_dynamic_range((const float*)h->slot_ptr[raw[g]->slot], (long long)raw[g]->vocab, raw[g]->row_stride,
+                                            4 * raw[g]->count, mx, &wide));
                 ok = !wide;
             }
         }
         if (ok) {
-            auto pow2_scale = [](float m, int top) { int e = 0; if (m > 0.f) { (void)frexpf(m, &e); e = top - e; } e = e > 60 ? 60 : (e < -60 ? -60 : e); return ldexpf(1.f, e); };
-            const float e_scale = pow2_scale(mx, 15);
+            const float e_scale = pow2_scale(mx);
             std::vector<float> W0h;
             int rcp = pull(W0h, W0full, (size_t)q0.N * q0.ldw);
             if (rcp) return rcp;
@@ -170,7 +163,7 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
                     for (int d = 0; d < 4 * raw[g]->count; ++d) amax = fmaxf(amax, fabsf(W0h[(size_t)n * q0.ldw + raw[g]->dst - q0.src_off + d]));
             ok = amax < 3.0e38f;
             if (ok) {
-                const float w_scale = pow2_scale(amax, 15);
+                const float w_scale = pow2_scale(amax);
                 std::vector<float> fr((size_t)n0c * nblk * 512, 0.f);
                 _Float16* fh = reinterpret_cast<_Float16*>(fr.data());
                 for (int nb = 0; nb < n0c; ++nb)
@@ -186,16 +179,14 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
                                 fh[base + ln * 8 + e] = hi;
                                 fh[base + 512 + ln * 8 + e] = (_Float16)(x - (float)hi);
                             }
-                HIP_TRY(hipMalloc((void**)&w0efrag, fr.size() * sizeof(float)));
-                h->fold_bufs.push_back(w0efrag);
+                SPRK_TRY(dev_alloc(h, &w0efrag, fr.size() * sizeof(float)));
                 HIP_TRY(hipMemcpy(w0efrag, fr.data(), fr.size() * sizeof(float), hipMemcpyHostToDevice));
                 for (int g = 0; g < DT_MAX_COLS; ++g) r.Etab[g] = nullptr;
                 for (int g = 0; g < dp->n_acc; ++g) {
                     const long long rows = (long long)raw[g]->vocab;
                     float* et = nullptr;
-                    HIP_TRY(hipMalloc((void**)&et, (size_t)(rows + 1) * 4 * epb));
+                    SPRK_TRY(dev_alloc(h, &et, (size_t)(rows + 1) * 4 * epb));
                     HIP_TRY(hipMemset(et, 0, (size_t)(rows + 1) * 4 * epb));
-                    h->fold_bufs.push_back(et);
                     h->derived_bytes += (size_t)(rows + 1) * 4 * epb;
                     long long nbk = (rows * epb + 255) / 256;
                     if (nbk > 65536) nbk = 65536;
@@ -242,7 +233,7 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
                     if (best >= 0) unf_g[n_unf++] = best;
                 }
             }
-            HIP_TRY(hipMalloc((void**)&h->din_fused_image, DinFusedImg::dma_floats * sizeof(float)));
+            SPRK_TRY(dev_alloc(h, &h->din_fused_image, DinFusedImg::dma_floats * sizeof(float)));
             hipLaunchKernelGGL(k_din_fused_pack, dim3(1), dim3(256), 0, 0, o0.W, o0.ldw, p_off, Dp, n_off, n_num, 1.0f / r.inv_w0p_scale, 4 * kc,
                                o0.bias, o0.alpha, w1frag, o1.bias, o1.alpha, tp.w, tp.len, h->din_fused_image, (const float*)w0efrag, n_unf, unf_g[0], unf_g[1], kc == 2 ? 4 : 2);
             HIP_TRY(hipGetLastError());
@@ -286,9 +277,16 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
     return SPRK_OK;
 }
 
-int need_bytes(const sprk_engine* h, int slot, size_t bytes, const char* what) {
-    if (!h->slot_ptr[slot]) return fail(SPRK_ESTATE, "%s: slot %d was never uploaded", what, slot);
-    if (h->slot_bytes[slot] < bytes) return fail(SPRK_EINVAL, "%s: slot %d holds %zu bytes, needs %zu", what, slot, h->slot_bytes[slot], bytes);
+// DIEN in one launch (k_dien_fused.h): the sequence stage on the matrix pipe AND DIN.py's 128 / 64 tail on raw split rows
+int setup_dien_fused(sprk_engine* h) {
+    if (h->plan.din.enabled != 2 || !h->dien_frag || !h->tune.dien_fused || h->din_tail_variant < 0) return SPRK_OK;
+    const DinTailVariant& tv = kDinTailVariants[h->din_tail_variant];
+    if (tv.n0c != 8 || tv.n1c != 4 || tv.kpc != 1 || h->din_tail_run.e_unscale == 0.f) return SPRK_OK;
+    const bool d10 = h->plan.din.emb_dim == 10;
+    h->dien_fused_lds = ((d10 ? DienFrag<10, 32>::total_pad : DienFrag<16, 32>::total_pad) + DinTailLds<8, 4, 1>::total_pad) * sizeof(float);
+    HIP_TRY(hipFuncSetAttribute(d10 ? reinterpret_cast<const void*>(&k_dien_fused<10, 32, 8, 4>) : reinterpret_cast<const void*>(&k_dien_fused<16, 32, 8, 4>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->dien_fused_lds));
+    h->dien_fused = true;
     return SPRK_OK;
 }
 

@@ -106,7 +106,7 @@ int setup_mlp_rows(sprk_engine* h) {
     const size_t lds = ((size_t)image_lds + small_floats + (size_t)MR_WAVES * MR_STAGE) * sizeof(float);
     if (lds > 160 * 1024) return SPRK_OK;
     const float* W0 = (const float*)h->slot_ptr[o0.w_slot];
-    HIP_TRY(hipMalloc((void**)&h->mlp_rows_small, small_floats * sizeof(float)));
+    SPRK_TRY(dev_alloc(h, &h->mlp_rows_small, small_floats * sizeof(float)));
     HIP_TRY(hipMemset(h->mlp_rows_small, 0, small_floats * sizeof(float)));
     auto fold = [&](const sprk_seg& sg, float* F) {
         long long blocks = ((long long)sg.vocab * N0 + 255) / 256;
@@ -116,29 +116,27 @@ int setup_mlp_rows(sprk_engine* h) {
     };
     {
         // small columns: fold into a scratch buffer, then into the padded LDS layout (k_mlp_rows.h)
-        float* tmp = nullptr;
-        HIP_TRY(hipMalloc((void**)&tmp, (size_t)32 * N0 * sizeof(float)));
+        DevScratch<float> tmp;
+        HIP_TRY(tmp.alloc((size_t)32 * N0));
         for (int f = 0; f < r.n_small; ++f) {
             r.s_col[f] = small_seg[f]->field; r.s_vocab[f] = small_seg[f]->vocab;
-            fold(*small_seg[f], tmp);
-            hipLaunchKernelGGL(k_mlp_rows_pad, dim3(4), dim3(256), 0, 0, tmp, h->mlp_rows_small + r.s_off[f], small_seg[f]->vocab);
+            fold(*small_seg[f], tmp.p);
+            hipLaunchKernelGGL(k_mlp_rows_pad, dim3(4), dim3(256), 0, 0, tmp.p, h->mlp_rows_small + r.s_off[f], small_seg[f]->vocab);
         }
         HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(tmp);
     }
     for (int b = 0; b < r.n_big; ++b) {
         const sprk_seg& sg = *big_seg[b];
         float* F = nullptr;
         const size_t bytes = ((size_t)sg.vocab + 1) * N0 * sizeof(float);
-        { const int rc_ = table_alloc(h, (void**)&F, bytes); if (rc_) return rc_; }
-        h->mlp_rows_bufs.push_back(F);
+        SPRK_TRY(table_alloc(h, &F, bytes));
         h->derived_bytes += bytes;
         HIP_TRY(hipMemset(F + (size_t)sg.vocab * N0, 0, N0 * sizeof(float)));        // the "no id" row
         fold(sg, F);
         r.big_col[b] = sg.field; r.big_vocab[b] = sg.vocab; r.big_tab[b] = F;
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMalloc((void**)&h->mlp_rows_image, (size_t)image_floats * sizeof(float)));
+    SPRK_TRY(dev_alloc(h, &h->mlp_rows_image, (size_t)image_floats * sizeof(float)));
     if (dyn)
         hipLaunchKernelGGL((k_mlp_rows_pack<8, 8, true>), dim3(1), dim3(256), 0, 0, W0, o0.ldw, num_dst - lo, r.n_num, (const float*)h->slot_ptr[o0.b_slot],
                            (const float*)h->slot_ptr[o1.w_slot], o1.ldw, (const float*)h->slot_ptr[o1.b_slot],

@@ -194,14 +194,12 @@ int setup_deepfm_pairs(sprk_engine* h) {
     const int PC = (Dp / 4 + 3) / 4;                          // 16-float chunks per embedding row
     const int KW = 16 * (V1_MAX_DEEP * PC + 1);
     float* w0p = nullptr;
-    HIP_TRY(hipMalloc((void**)&w0p, (size_t)H0 * KW * sizeof(float) + 16));
-    h->v1_bufs.push_back(w0p);
+    SPRK_TRY(dev_alloc(h, &w0p, (size_t)H0 * KW * sizeof(float) + 16));
     hipLaunchKernelGGL(k_v1_pack_w0, dim3(1), dim3(256), 0, 0, W0, o0.ldw, r.n_deep, deep_off[0], deep_off[1], Dp, num_dst - s0, r.n_num,
                        H0, PC, w0p);
     HIP_TRY(hipGetLastError());
     float* hd = nullptr;
-    HIP_TRY(hipMalloc((void**)&hd, (size_t)H1 * sizeof(float) + 16));
-    h->v1_bufs.push_back(hd);
+    SPRK_TRY(dev_alloc(h, &hd, (size_t)H1 * sizeof(float) + 16));
     HIP_TRY(hipMemset(hd, 0, (size_t)H1 * sizeof(float)));
     HIP_TRY(hipMemcpy(hd, h->slot_ptr[tdeep->w_slot], (size_t)tdeep->len * sizeof(float), hipMemcpyDeviceToDevice));
     HIP_TRY(hipDeviceSynchronize());
@@ -221,9 +219,8 @@ int setup_deepfm_pairs(sprk_engine* h) {
     }
     {
         float* img = nullptr;
-        HIP_TRY(hipMalloc((void**)&img, kV1Variants[variant].lds_bytes));
-        h->v1_bufs.push_back(img);
-        { const int rc3 = kV1Variants[variant].prepare(r, img); if (rc3) return rc3; }
+        SPRK_TRY(dev_alloc(h, &img, kV1Variants[variant].lds_bytes));
+        SPRK_TRY(kV1Variants[variant].prepare(r, img));
         HIP_TRY(hipDeviceSynchronize());
         r.image = img;
     }
@@ -231,31 +228,18 @@ int setup_deepfm_pairs(sprk_engine* h) {
     {
         // static scale for deep0's embedding block: max |E| over the deep fields' tables, unless a table has outlier rows
         if (r.w0frag) {
-            DevProbe d_max_probe;
-            unsigned*& d_max = d_max_probe.p;
-            HIP_TRY(hipMalloc((void**)&d_max, sizeof(unsigned)));
-            HIP_TRY(hipMemset(d_max, 0, sizeof(unsigned)));
-            bool wide = false;
+            std::vector<AbsmaxJob> jobs;
             for (int f = 0; f < r.n_deep; ++f) {
                 const long long rows = (long long)r.vocab[f] + 1;
-                long long blocks = (rows * Dp + 255) / 256;
-                if (blocks > 8192) blocks = 8192;
-                hipLaunchKernelGGL(k_v2_absmax, dim3((unsigned)blocks), dim3(256), 0, 0, deep_tables[f], rows, Dp, Dp, d_max);
+                jobs.push_back({deep_tables[f], rows, Dp, Dp, absmax_grid(rows * Dp, 8192), 0});
             }
-            HIP_TRY(hipGetLastError());
-            unsigned bits = 0;
-            HIP_TRY(hipMemcpy(&bits, d_max, sizeof(bits), hipMemcpyDeviceToHost));
-            float mx;
-            memcpy(&mx, &bits, sizeof(mx));
+            float mx = 0.f;
+            SPRK_TRY(device_absmax(jobs, &mx, 1));
+            bool wide = false;
             for (int f = 0; f < r.n_deep && !wide && mx > 0.f && mx < 3.0e38f; ++f)
-                if (int rcw = wide_dynamic_range(deep_tables[f], (long long)r.vocab[f] + 1, Dp, Dp, mx, &wide)) return rcw;
+                SPRK_TRY(wide_dynamic_range(deep_tables[f], (long long)r.vocab[f] + 1, Dp, Dp, mx, &wide));
             if (mx > 0.f && mx < 3.0e38f && !wide) {
-                int e = 0;
-                (void)frexpf(mx, &e);
-                e = 15 - e;
-                if (e > 60) e = 60;
-                if (e < -60) e = -60;
-                r.e_scale = ldexpf(1.f, e);
+                r.e_scale = pow2_scale(mx);
                 r.e_inv = r.inv_w0_scale / r.e_scale;
             }
         }
@@ -270,15 +254,13 @@ int setup_deepfm_pairs(sprk_engine* h) {
         if (sep && !pack) for (int d = 0; d < r.n_deep; ++d) rows += (size_t)r.vocab[d] + 1;
         if (rows * 128 < ((size_t)1 << 32)) {                     // 32-bit byte offsets
             float* tab = nullptr;
-            { const int rc_ = table_alloc(h, (void**)&tab, rows * 128); if (rc_) return rc_; }
-            h->v1_bufs.push_back(tab);
+            SPRK_TRY(table_alloc(h, &tab, rows * 128));
             h->derived_bytes += rows * 128;
             float* w1c = nullptr;
             if (pack == 64) {
                 size_t nw = 0;
                 for (int d = 0; d < r.n_deep; ++d) { r.w1cbase[d] = (unsigned)nw; nw += (size_t)r.vocab[d] + 1; }
-                HIP_TRY(hipMalloc((void**)&w1c, nw * sizeof(float) + 16));
-                h->v1_bufs.push_back(w1c);
+                SPRK_TRY(dev_alloc(h, &w1c, nw * sizeof(float) + 16));
                 for (int d = 0; d < r.n_deep; ++d)
                     HIP_TRY(hipMemcpy(w1c + r.w1cbase[d], r.w1[d], ((size_t)r.vocab[d] + 1) * sizeof(float), hipMemcpyDeviceToDevice));
             }

@@ -65,7 +65,7 @@ int pull(std::vector<float>& dst, const float* src, size_t n) {
     return SPRK_OK;
 }
 int rows_finish(sprk_engine* h, const RowsVariant& rv, const std::vector<float>& image, size_t small_floats) {
-    HIP_TRY(hipMalloc((void**)&h->rows_image, (size_t)rv.image_floats * sizeof(float)));
+    SPRK_TRY(dev_alloc(h, &h->rows_image, (size_t)rv.image_floats * sizeof(float)));
     HIP_TRY(hipMemcpy(h->rows_image, image.data(), (size_t)rv.image_floats * sizeof(float), hipMemcpyHostToDevice));
     h->rows_lds_bytes = ((size_t)rv.image_floats + RC_WAVES * 256 + small_floats) * sizeof(float);
     if (h->rows_lds_bytes > 160 * 1024) return fail(SPRK_EINVAL, "rows chain needs %zu bytes of LDS", h->rows_lds_bytes);
@@ -98,25 +98,18 @@ int setup_rows_v2(sprk_engine* h) {
     if (h->tune.rows_unf && h->tune.dyn_f16 && nbig <= 2 && Dp <= 16 && KP + H0 > 16) {
         const int vu = find_rows_variant(KP / 16, H0 / 16, H1 / 16, nbig, nsm, true, true);
         if (vu >= 0) {
-            DevProbe d_max_probe;
-            unsigned*& d_max = d_max_probe.p;
-            HIP_TRY(hipMalloc((void**)&d_max, sizeof(unsigned)));
-            HIP_TRY(hipMemset(d_max, 0, sizeof(unsigned)));
-            for (int b = 0; b < nbig; ++b)
-                hipLaunchKernelGGL(k_v2_absmax, dim3(1024), dim3(256), 0, 0, a.table[big[b]], (long long)a.emb_vocab[big[b]] + 1, Dp, Dp, d_max);
-            unsigned bits = 0;
-            HIP_TRY(hipMemcpy(&bits, d_max, sizeof(bits), hipMemcpyDeviceToHost));
-            float mx;
-            memcpy(&mx, &bits, sizeof(mx));
+            std::vector<AbsmaxJob> jobs;
+            for (int b = 0; b < nbig; ++b) jobs.push_back({a.table[big[b]], (long long)a.emb_vocab[big[b]] + 1, Dp, Dp, 1024, 0});
+            float mx = 0.f;
+            SPRK_TRY(device_absmax(jobs, &mx, 1));
             bool ok = mx < 3.0e38f;
             for (int b = 0; ok && b < nbig; ++b) {
                 bool wide = false;
-                if (int rcw = wide_dynamic_range(a.table[big[b]], (long long)a.emb_vocab[big[b]] + 1, Dp, Dp, mx, &wide)) return rcw;
+                SPRK_TRY(wide_dynamic_range(a.table[big[b]], (long long)a.emb_vocab[big[b]] + 1, Dp, Dp, mx, &wide));
                 if (wide) ok = false;                              // an outlier row: its neighbours' lo halves would be subnormal
             }
             if (ok) {
-                int e = 0;
-                if (mx > 0.f) { (void)frexpf(mx, &e); e = 15 - e; if (e > 60) e = 60; if (e < -60) e = -60; p_scale = ldexpf(1.f, e); }
+                p_scale = pow2_scale(mx);
                 variant = vu;
             }
         }
@@ -149,12 +142,12 @@ int setup_rows_v2(sprk_engine* h) {
         small_floats += ((size_t)a.emb_vocab[sm[f]] + 1) * rv.ss;
     }
     small_floats = (small_floats + 255) & ~(size_t)255;
-    { const int rc_ = table_alloc(h, (void**)&h->rows_tab, big_rows * rv.rb + 64); if (rc_) return rc_; }
+    SPRK_TRY(table_alloc(h, &h->rows_tab, big_rows * rv.rb + 64));
     HIP_TRY(hipMemset(h->rows_tab, 0, big_rows * rv.rb + 64));
-    HIP_TRY(hipMalloc((void**)&h->rows_scal, big_rows * sizeof(float) + 16));
+    SPRK_TRY(dev_alloc(h, &h->rows_scal, big_rows * sizeof(float) + 16));
     h->derived_bytes += big_rows * rv.rb + big_rows * sizeof(float);
     if (small_floats) {
-        HIP_TRY(hipMalloc((void**)&h->rows_small, small_floats * sizeof(float)));
+        SPRK_TRY(dev_alloc(h, &h->rows_small, small_floats * sizeof(float)));
         HIP_TRY(hipMemset(h->rows_small, 0, small_floats * sizeof(float)));
     }
     auto build = [&](int g, float* out, int out_stride, float* scal_out) {
@@ -181,21 +174,19 @@ int setup_rows_v2(sprk_engine* h) {
                            reinterpret_cast<_Float16*>(reinterpret_cast<char*>(h->rows_tab) + (size_t)r.big_rowbase[b] * 64));
         std::vector<float> ident((size_t)(Dp + 1) * Dp, 0.f);
         for (int d = 0; d < Dp; ++d) ident[(size_t)d * Dp + d] = 1.f;
-        float *d_id = nullptr, *d_out = nullptr;
+        DevScratch<float> d_id, d_out;
         const int W = KP + H0;
-        HIP_TRY(hipMalloc((void**)&d_id, ident.size() * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&d_out, (size_t)(Dp + 1) * W * sizeof(float)));
-        HIP_TRY(hipMemcpy(d_id, ident.data(), ident.size() * sizeof(float), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_rows_build, dim3(4), dim3(256), 0, 0, (const float*)d_id, Dp, (long long)Dp, a.Wp[g], a.ldp_emb, (const float*)nullptr, KP,
-                           a.W0, d0.ldw, g * KP, H0, KP, (const float*)nullptr, (const float*)nullptr, a.hfm, 0, 0.f, d_out, W, (float*)nullptr, 0);
-        hipLaunchKernelGGL(k_rows_build, dim3(1), dim3(256), 0, 0, (const float*)(d_id + (size_t)Dp * Dp), Dp, 1ll, a.Wp[g], a.ldp_emb, a.bp[g], KP,
-                           a.W0, d0.ldw, g * KP, H0, KP, (const float*)nullptr, (const float*)nullptr, a.hfm, 0, 0.f, d_out + (size_t)Dp * W, W,
+        HIP_TRY(d_id.alloc(ident.size()));
+        HIP_TRY(d_out.alloc((size_t)(Dp + 1) * W));
+        HIP_TRY(hipMemcpy(d_id.p, ident.data(), ident.size() * sizeof(float), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_rows_build, dim3(4), dim3(256), 0, 0, (const float*)d_id.p, Dp, (long long)Dp, a.Wp[g], a.ldp_emb, (const float*)nullptr, KP,
+                           a.W0, d0.ldw, g * KP, H0, KP, (const float*)nullptr, (const float*)nullptr, a.hfm, 0, 0.f, d_out.p, W, (float*)nullptr, 0);
+        hipLaunchKernelGGL(k_rows_build, dim3(1), dim3(256), 0, 0, (const float*)(d_id.p + (size_t)Dp * Dp), Dp, 1ll, a.Wp[g], a.ldp_emb, a.bp[g], KP,
+                           a.W0, d0.ldw, g * KP, H0, KP, (const float*)nullptr, (const float*)nullptr, a.hfm, 0, 0.f, d_out.p + (size_t)Dp * W, W,
                            (float*)nullptr, 0);
-        int rcp = hipGetLastError() == hipSuccess ? SPRK_OK : fail(SPRK_EHIP, "rows chain: projection probe launch failed");
-        if (!rcp) rcp = pull(lin[b], d_out, (size_t)Dp * W);
-        if (!rcp) rcp = pull(cst[b], d_out + (size_t)Dp * W, W);
-        (void)hipFree(d_id); (void)hipFree(d_out);
-        if (rcp) return rcp;
+        if (hipGetLastError() != hipSuccess) return fail(SPRK_EHIP, "rows chain: projection probe launch failed");
+        SPRK_TRY(pull(lin[b], d_out.p, (size_t)Dp * W));
+        SPRK_TRY(pull(cst[b], d_out.p + (size_t)Dp * W, W));
     }
     for (int f = 0; f < nsm; ++f) build(sm[f], h->rows_small + r.s_off[f], rv.ss, nullptr);
     HIP_TRY(hipGetLastError());
@@ -252,8 +243,7 @@ int setup_rows_v2(sprk_engine* h) {
             for (int m = 0; m < H0; ++m) img[off_c0 + m] += cst[b][KP + m];
         }
         if (!(amax < 3.0e38f)) return fail(SPRK_EINVAL, "non-finite projection weights");
-        float w_scale = 1.f;
-        { int e = 0; if (amax > 0.f) { (void)frexpf(amax, &e); e = 15 - e; if (e > 60) e = 60; if (e < -60) e = -60; w_scale = ldexpf(1.f, e); } }
+        const float w_scale = pow2_scale(amax);
         _Float16* fh = reinterpret_cast<_Float16*>(&img[off_af]);
         for (int nb = 0; nb < W / 16; ++nb)
             for (int ln = 0; ln < 64; ++ln)
@@ -301,7 +291,7 @@ int setup_rows_ncf(sprk_engine* h) {
         rows_total += (size_t)sg.vocab + 1;
     }
     if (rows_total >= ((size_t)1 << 31)) return SPRK_OK;
-    { const int rc_ = table_alloc(h, (void**)&h->rows_tab, rows_total * rv.rb + 64); if (rc_) return rc_; }
+    SPRK_TRY(table_alloc(h, &h->rows_tab, rows_total * rv.rb + 64));
     HIP_TRY(hipMemset(h->rows_tab, 0, rows_total * rv.rb + 64));
     h->derived_bytes += rows_total * rv.rb;
     const float* W0 = (const float*)h->slot_ptr[o0.w_slot];

@@ -1,4 +1,4 @@
-// host_setup_v2.h -- DeepFM_v2: k_deepfm_v2_chain / _joint / _joint1 dispatch tables, plan matcher, fold + joint-table set-up.
+// host_setup_v2.h -- DeepFM_v2: the folded shapes, k_deepfm_v2_joint / _joint1 dispatch tables, plan matcher, fold + joint-table set-up.
 // Part of sparrow_hip.hip (one translation unit); included there, not compilable on its own.
 // ---- the DeepFM_v2 plan shapes the joint kernels are built on: folded tables (KP-wide projected rows), the LDS image of k_v2_pack_image ----
 // ([r6] until round 6 this was the dispatch table of k_deepfm_v2_chain, whose kernels are retired: k_chain_v2.h)
@@ -193,7 +193,6 @@ bool match_v2_chain(sprk_engine* h) {
             h->v2 = a;
             h->v2_fo_floats = fo_floats;
             h->v2_variant = (int)v;
-            h->v2_lds_bytes = vv.lds_bytes;
             h->rows_g_emb = g_emb;                             // (should the joint set-up refuse the model: finalize hands the parsed plan to k_rows_chain)
             h->v2_rows_ok = kpc >= 1 && kpc <= 4 && h0c >= 1 && h1c >= 1 && !raw_over_4g;
             return true;
@@ -211,7 +210,6 @@ bool match_v2_chain(sprk_engine* h) {
 // Split the fields of a folded DeepFM_v2 engine into big ones (gathered per field) and a joint group of
 // small-vocabulary ones (one gather per sample), build the joint table.  Leaves v2j_variant = -1 when the
 // model has no small field or no instantiation fits.
-int wide_dynamic_range(const float* rows, long long nrows, int row_floats, int ncols, float mx, bool* wide);
 int setup_v2_joint(sprk_engine* h) {
     const V2Variant& vv = kV2Variants[h->v2_variant];
     if (vv.kpc != 1 || vv.h0c != 2 || vv.h1c != 1 || !h->tune.v2_joint) return SPRK_OK;
@@ -227,41 +225,28 @@ int setup_v2_joint(sprk_engine* h) {
     bool half = h->tune.v2_half;
     float p_scale = 1.f, w_scale = 1.f;
     if (half) {
-        DevProbe d_max_probe;
-        unsigned*& d_max = d_max_probe.p;
-        HIP_TRY(hipMalloc((void**)&d_max, 2 * sizeof(unsigned)));
-        HIP_TRY(hipMemset(d_max, 0, 2 * sizeof(unsigned)));
+        std::vector<AbsmaxJob> jobs;
         for (int b = 0; b < nbig; ++b) {
             const long long rows = (long long)h->v2run.vocab[big[b]] + 1;
-            long long blocks = (rows * KP + 255) / 256;
-            if (blocks > 8192) blocks = 8192;
-            hipLaunchKernelGGL(k_v2_absmax, dim3((unsigned)blocks), dim3(256), 0, 0,
-                               h->v2_folded + (size_t)h->v2run.rowbase[big[b]] * (KP + 16), rows, KP + 16, KP, d_max);
+            jobs.push_back({h->v2_folded + (size_t)h->v2run.rowbase[big[b]] * (KP + 16), rows, KP + 16, KP, absmax_grid(rows * KP, 8192), 0});
         }
-        hipLaunchKernelGGL(k_v2_absmax, dim3(8), dim3(256), 0, 0, h->v2.W0, (long long)H0, (G + 1) * KP, (G + 1) * KP, d_max + 1);
-        HIP_TRY(hipGetLastError());
-        unsigned bits[2];
-        HIP_TRY(hipMemcpy(bits, d_max, sizeof(bits), hipMemcpyDeviceToHost));
+        jobs.push_back({h->v2.W0, (long long)H0, (G + 1) * KP, (G + 1) * KP, 8, 1});
         float mx[2];
-        memcpy(mx, bits, sizeof(mx));
+        SPRK_TRY(device_absmax(jobs, mx, 2));
         for (int i = 0; i < 2; ++i) {
             if (!(mx[i] < 3.0e38f)) { half = false; break; }     // NaN / Inf in the weights: keep the f32 path
-            int e = 0;
-            if (mx[i] > 0.f) { (void)frexpf(mx[i], &e); e = 15 - e; }   // mx * 2^e in [2^14, 2^15)
-            if (e > 60) e = 60;
-            if (e < -60) e = -60;
-            (i == 0 ? p_scale : w_scale) = ldexpf(1.f, e);
+            (i == 0 ? p_scale : w_scale) = pow2_scale(mx[i]);
         }
         // an outlier row next to ordinary ones: the ordinary rows' lo halves would be subnormal -> keep the f32 variant
         for (int b = 0; half && b < nbig; ++b) {
             bool wide = false;
-            if (int rcw = wide_dynamic_range(h->v2_folded + (size_t)h->v2run.rowbase[big[b]] * (KP + 16),
-                                             (long long)h->v2run.vocab[big[b]] + 1, KP + 16, KP, mx[0], &wide)) return rcw;
+            SPRK_TRY(wide_dynamic_range(h->v2_folded + (size_t)h->v2run.rowbase[big[b]] * (KP + 16),
+                                        (long long)h->v2run.vocab[big[b]] + 1, KP + 16, KP, mx[0], &wide));
             if (wide) half = false;
         }
         if (half) {
             bool wide = false;
-            if (int rcw = wide_dynamic_range(h->v2.W0, (long long)H0, (G + 1) * KP, (G + 1) * KP, mx[1], &wide)) return rcw;
+            SPRK_TRY(wide_dynamic_range(h->v2.W0, (long long)H0, (G + 1) * KP, (G + 1) * KP, mx[1], &wide));
             if (wide) half = false;
         }
     }
@@ -307,7 +292,7 @@ int setup_v2_joint(sprk_engine* h) {
         size_t big_rows = 0;
         for (int b = 0; b < nbig; ++b) big_rows += (size_t)r.big_vocab[b] + 1;
         if (big_rows * (KP + 16) * sizeof(float) >= ((size_t)1 << 32)) return fail(SPRK_EINVAL, "split rows exceed 32-bit offsets");
-        { const int rc_ = table_alloc(h, (void**)&h->v2j_big, big_rows * (KP + 16) * sizeof(float)); if (rc_) return rc_; }
+        SPRK_TRY(table_alloc(h, &h->v2j_big, big_rows * (KP + 16) * sizeof(float)));
         h->derived_bytes += big_rows * (KP + 16) * sizeof(float);
         size_t base = 0;
         for (int b = 0; b < nbig; ++b) {
@@ -332,7 +317,7 @@ int setup_v2_joint(sprk_engine* h) {
         for (size_t v = 0; v < sizeof(kV2J1Variants) / sizeof(kV2J1Variants[0]); ++v) {
             const V2J1Variant& ov = kV2J1Variants[v];
             if (ov.g_big != nbig || ov.njf != njf) continue;
-            HIP_TRY(hipMalloc((void**)&h->v2j1_image, (size_t)ov.image_floats * sizeof(float)));
+            SPRK_TRY(dev_alloc(h, &h->v2j1_image, (size_t)ov.image_floats * sizeof(float)));
             hipLaunchKernelGGL(k_v2j1_pack_image, dim3(1), dim3(256), 0, 0, h->v2, r, nbig, G + 1, h->v2j1_image);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipDeviceSynchronize());
@@ -343,6 +328,49 @@ int setup_v2_joint(sprk_engine* h) {
             HIP_TRY(hipFuncSetAttribute(h->v2j1_hoist ? ov.fn_h : ov.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->v2j1_lds_bytes));
         }
     }
+    return SPRK_OK;
+}
+
+// The folded form match_v2_chain found: first-order weight blocks back to back, every field's rows projected into one buffer of folded
+// rows (k_v2_fold), then the joint set-up.  A model without a joint form (no small-vocabulary field, more than three large ones,
+// SPRK_V2_JOINT=0) releases both again: [r6] until round 6 k_deepfm_v2_chain took it, now the parsed plan goes to k_rows_chain, then to
+// the interpreter.
+int setup_v2_fold(sprk_engine* h) {
+    const V2Variant& vv = kV2Variants[h->v2_variant];
+    const int KP = vv.kpc * 16;
+    h->v2_grid_cap = h->num_cus;                             // one 8-wave workgroup per CU (weights in registers: two waves per SIMD)
+    SPRK_TRY(dev_alloc(h, &h->v2_fo_all, h->v2_fo_floats * sizeof(float)));
+    for (int g = 0; g < vv.g_emb; ++g)
+        HIP_TRY(hipMemcpy(h->v2_fo_all + h->v2run.fo_off[g], h->v2_w1_grp[g], ((size_t)h->v2run.vocab[g] + 1) * sizeof(float), hipMemcpyDeviceToDevice));
+    h->v2run.fo_all = h->v2_fo_all;
+    size_t rows_total = 0;
+    for (int g = 0; g < vv.g_emb; ++g) { h->v2run.rowbase[g] = (unsigned)rows_total; rows_total += (size_t)h->v2run.vocab[g] + 1; }
+    SPRK_TRY(table_alloc(h, &h->v2_folded, rows_total * (KP + 16) * sizeof(float)));
+    for (int g = 0; g < vv.g_emb; ++g) {
+        const long long rows = (long long)h->v2run.vocab[g] + 1;
+        long long blocks = (rows + 3) / 4;
+        if (blocks > 65536) blocks = 65536;
+        hipLaunchKernelGGL(k_v2_fold, dim3((unsigned)blocks), dim3(256), 0, 0, h->v2.table[g], h->v2.ldp_emb,
+                           h->v2.Wp[g], h->v2.ldp_emb, h->v2.bp[g], h->v2_w1_grp[g], h->v2.hfm, h->v2.n_hfm, h->v2.h0w,
+                           h->v2_folded + (size_t)h->v2run.rowbase[g] * (KP + 16), KP, rows);
+        HIP_TRY(hipGetLastError());
+    }
+    h->v2run.tab0 = h->v2_folded;
+    HIP_TRY(hipDeviceSynchronize());
+    SPRK_TRY(setup_v2_joint(h));
+    if (h->v2j_variant < 0) {
+        dev_free(h, h->v2_fo_all); h->v2_fo_all = nullptr;
+        dev_free(h, h->v2_folded); h->v2_folded = nullptr;
+        h->v2_variant = -1;
+        h->rows_from_v2 = h->v2_rows_ok;
+        return SPRK_OK;
+    }
+    h->derived_bytes += rows_total * (KP + 16) * sizeof(float);   // (after the joint set-up: its HOIST choice counts only the split rows)
+    SPRK_TRY(dev_alloc(h, &h->v2_image, vv.lds_bytes));
+    HIP_TRY(hipMemset(h->v2_image, 0, vv.lds_bytes));
+    vv.pack(h->v2, h->v2_image);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return SPRK_OK;
 }
 

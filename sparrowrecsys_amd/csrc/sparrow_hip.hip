@@ -23,16 +23,17 @@
 // everything back into this one unit (the ISA scripts).  The pieces share one named namespace for the kernels (sprk_dev) and one
 // anonymous namespace for the host helpers, and are meaningful only in this order:
 #include "tu_kernels.h"              // system headers, include/sparrow_hip.h, host_common.h .. k_operators.h, tu_instances.h
-#include "host_engine.h"             // struct sprk_engine: everything a finalized handle owns
+#include "host_engine.h"             // struct sprk_engine: everything a finalized handle owns, its route and stage, the owner of its device memory
 #include "host_plan.h"               // plan validation and small host helpers
-#include "host_setup_v2.h"           // DeepFM_v2: k_deepfm_v2_chain / _joint / _joint1 dispatch tables, plan matcher, fold + joint-table set-up
+#include "host_setup_common.h"       // the attention shape table, the interpreter's first-Dense fold, static split-f16 scales, split-f16 fragment packing
+#include "host_setup_v2.h"           // DeepFM_v2: k_deepfm_v2_joint / _joint1 dispatch tables, plan matcher, fold + joint-table set-up
 #include "host_setup_rows.h"         // k_rows_chain (literal DeepFM_v2, NeuralCF): dispatch table and set-up
-#include "host_setup_common.h"       // k_din_attn dispatch table, the interpreter's first-Dense fold, the dynamic-range guard, split-f16 fragment packing
 #include "host_setup_pairs.h"        // pair-dot DeepFM: k_deepfm_pairs / _pairs1 dispatch table, plan matcher and set-up
 #include "host_setup_mlp.h"          // EmbeddingMLP / Wide&Deep: k_mlp_rows set-up
+#include "host_setup_din.h"          // DIN / DIEN history stage: k_dien_seq(_mfma), k_din_pool, k_din_attn_cols / k_din_fused attention tables
 #include "host_setup_din_tail.h"     // DIN / DIEN tail: k_din_tail dispatch table and set-up -- closes the host helpers' anonymous namespace
 #include "api_engine.h"              // C ABI: sprk_last_error .. sprk_create / sprk_upload / sprk_finalize / sprk_workspace_bytes
 #include "api_forward.h"             // C ABI: sprk_din_pool, sprk_forward, sprk_forward_many, sprk_describe, sprk_check_ids, sprk_destroy, operators, emb ranker
 #include "api_ingest.h"              // C ABI: CSV ingest on the host (sprk_pack_csv[_mt]) and on the device (sprk_pack_csv_device), sprk_cross_hash
-#include "api_comm.h"
-#include "api_vtable.h"              // C ABI: a row-sharded table every rank sees as one (sprk_vtable_*: HIP virtual memory over xGMI), sprk_upload_external                // C ABI: the score all-gather over RCCL (sprk_comm_*) and as direct peer writes (sprk_peer_*)
+#include "api_comm.h"                // C ABI: the score all-gather over RCCL (sprk_comm_*) and as direct peer writes (sprk_peer_*)
+#include "api_vtable.h"              // C ABI: a row-sharded table every rank sees as one (sprk_vtable_*: HIP virtual memory over xGMI), sprk_upload_external

@@ -611,6 +611,31 @@ def test_deepfm_v2_outlier_row_keeps_fp32_class(torch, monkeypatch):
     assert np.abs(p2 - ref).max() > np.abs(p - ref).max()
 
 
+def test_din_outlier_row_releases_attention_tables(torch, monkeypatch):
+    """The attention set-up of k_din_attn_cols / k_din_fused builds its tables, then the dynamic-range guard refuses a movie table with
+    one outlier row and the generic k_din_pool runs the stage.  The scores stay fp32-class, and the refused tables are released:
+    derived_bytes equals that of the same model built with SPRK_DIN_COLS=0, which never makes them."""
+    T, D, V, U, B = 50, 32, 5000, 7000, 4096
+    feats = SY.synth_din(B, T, V, U, seed=71)
+    for k in ("movieId", "userRatedMovies"):                       # id 3 is referenced by nobody
+        feats[k] = np.where(feats[k] == 3, 4, feats[k]).astype(feats[k].dtype)
+    w = dict(M.DIN(seed=72, emb_dim=D, hist_len=T, movie_buckets=V, user_buckets=U).weights)
+    tab = w["emb/movie"].copy()
+    tab[3] *= np.float32(3.0e8)                                     # the outlier row
+    w["emb/movie"] = tab
+    ref = O.din_forward(feats, w, dtype=np.float64, hist_len=T, movie_buckets=V, user_buckets=U)[:, 0]
+    model = M.DIN(weights=w, emb_dim=D, hist_len=T, movie_buckets=V, user_buckets=U)
+    p = model.predict(feats)[:, 0]
+    d = model.engine.describe()
+    print("outlier row: kernel", d.get("kernel"), "stage", d.get("stage"), "derived_bytes", d.get("derived_bytes"), "max|err|", float(np.abs(p - ref).max()))
+    assert d["stage"] == "k_din_pool", d
+    assert np.abs(p - ref).max() <= TOL
+    monkeypatch.setenv("SPRK_DIN_COLS", "0")
+    d0 = M.DIN(weights=w, emb_dim=D, hist_len=T, movie_buckets=V, user_buckets=U).engine.describe()
+    assert d0["stage"] == "k_din_pool", d0
+    assert int(d["derived_bytes"]) == int(d0["derived_bytes"]), (d, d0)
+
+
 def test_deepfm_v2_unaligned_views_and_tails(torch, config2):
     """ids/dense views that do not start on a 16-byte boundary take the element-wise staging path;
     every batch length mod 16 exercises the partial last task.  Pure data movement: bit-equal."""
