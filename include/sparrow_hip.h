@@ -330,6 +330,74 @@ int sprk_pack_csv_device(const char* text_dev, size_t len, const sprk_csv_col* i
  * call failed early.  The packed arrays are the same bits whichever ran. */
 int sprk_csv_last_path(void);
 
+/* ---- column ingest: a dict of feature columns -> the two packed arrays (what `model.predict(features_dict)` runs first) ----
+ * Replaces the feature-column resolution of the reference's Keras inputs (DeepFM.py:30-76) for columns that are already in
+ * memory: every output column of `ids [rows, n_id] int32` / `dense [rows, n_dense] float32` is described by one sprk_pack_col.
+ * The rule is CONVERT OR DECLINE, NEVER GUESS: the cases below are converted with the bits of the Python packer
+ * (schema.pack_ids / pack_dense); a batch that holds anything else is DECLINED -- SPRK_EKIND, sprk_last_error names the column
+ * and the row -- and the caller runs it through its next route.  The one error raised here is an identity id outside
+ * [0, vocab), and only when nothing in the batch was declined: SPRK_ERANGE with the Python packer's message, chosen as it
+ * chooses it (first column in id_cols order that holds a bad value, first bad row of that column).
+ *   identity  integer / bool -> the value; float -> NaN = 0, else truncation (outside int64: declined); string -> empty = 0,
+ *             else (long long) of the parsed double
+ *   genre     integer -> the value, -1 outside [0, vocab); string -> position in the 19-entry vocabulary (DeepFM.py:64-66)
+ *             below vocab, else -1; float / bool columns: declined
+ *   dense     integer -> (float), one rounding; float -> NaN = 0.0, else (float); string -> empty = 0.0, else (float) of the
+ *             parsed double
+ * A numeric string is [+-]? (digits [. digits?] | . digits) ([eE] [+-]? digits)? and nothing else (no blanks, "inf", "nan",
+ * hex, "_"; a result of +-inf is declined).  The element of a fixed-width column is what is in front of its trailing NULs; an
+ * embedded NUL is part of the value; a code point above 127 matches no genre and is declined in a numeric column.  Text
+ * columns share ONE block of bytes: the columns' fields one after the other, column by column, EVERY field terminated by
+ * '\n' (fields are raw: no quotes, no '\r' stripping); field i of text column k is line k * rows + i.  A block whose newline
+ * count is not (text columns) * rows is declined. */
+#define SPRK_COL_BOOL 0
+#define SPRK_COL_I8 1
+#define SPRK_COL_I16 2
+#define SPRK_COL_I32 3
+#define SPRK_COL_I64 4
+#define SPRK_COL_U8 5
+#define SPRK_COL_U16 6
+#define SPRK_COL_U32 7
+#define SPRK_COL_F32 8
+#define SPRK_COL_F64 9
+#define SPRK_COL_BYTES 10   /* fixed-width bytes, NUL padded (numpy S<width>)                  */
+#define SPRK_COL_UCS4 11    /* fixed-width native-endian UCS4, NUL padded (numpy U<width>)     */
+#define SPRK_COL_TEXT 12    /* fields of the shared text block                                 */
+#define SPRK_RULE_IDENTITY 0
+#define SPRK_RULE_GENRE 1
+#define SPRK_RULE_DENSE 2
+#define SPRK_PACK_MAX_COLS 128   /* id + dense columns of one sprk_pack_columns_device call    */
+typedef struct sprk_pack_col {
+    const void* data;    /* first element (NULL for SPRK_COL_TEXT)                              */
+    int64_t stride;      /* bytes from one row's element to the next (any sign)                 */
+    int32_t storage;     /* SPRK_COL_*                                                          */
+    int32_t width;       /* BYTES: bytes, UCS4: code points per element (1 .. 65535); TEXT: the column's index in the block */
+    int32_t on_device;   /* 0 = `data` is host memory, 1 = device memory (sprk_pack_columns_device only) */
+    int32_t rule;        /* SPRK_RULE_*: id columns IDENTITY or GENRE, dense columns DENSE      */
+    int32_t vocab;       /* buckets / vocabulary size (unused for DENSE)                        */
+    int32_t reserved;    /* 0                                                                   */
+    const char* name;    /* for messages (reference schema key)                                 */
+} sprk_pack_col;
+/* On the host (no GPU involved; every column and the outputs are HOST memory).  Rows are cut into chunks over n_threads host
+ * threads (clamped to [1, 256], one thread below 16384 rows); outputs, the decline and the range error are identical for
+ * any thread count.  Bad arguments (NULL pointers, unknown storage / rule, width 0, negative rows) -> SPRK_EINVAL. */
+int sprk_pack_columns(const sprk_pack_col* id_cols, int32_t n_id, const sprk_pack_col* dense_cols, int32_t n_dense,
+                      const char* text, size_t text_len, int32_t rows, int32_t n_threads, int32_t* ids_out, float* dense_out);
+/* The same ON THE DEVICE (k_pack_columns.h), same bits: `ids_dev` / `dense_dev` are DEVICE arrays (16-byte aligned).  Columns
+ * marked on_device are read where they are, with their stride; host columns (and the text block, always host memory) are
+ * compacted into a pinned buffer on n_threads host threads and sent with ONE asynchronous copy; the buffer and its device
+ * twin are kept per calling thread and grow to the largest batch seen.  At most SPRK_PACK_MAX_COLS columns, strides below
+ * 2^31.  Numeric strings are converted on strtod's exact path only (at most 15 significant digits, decimal exponent within
+ * +-22); the rest is declined, and sprk_pack_columns converts it.  Synchronises `stream`.  Arguments are validated before
+ * any device call. */
+int sprk_pack_columns_device(const sprk_pack_col* id_cols, int32_t n_id, const sprk_pack_col* dense_cols, int32_t n_dense,
+                             const char* text, size_t text_len, int32_t rows, int32_t n_threads, int32_t* ids_dev,
+                             float* dense_dev, void* stream);
+/* What the calling thread's last column pack did (diagnostics / tests): 2 = converted on the device, 1 = converted on the
+ * host, 0 = declined (SPRK_EKIND), -1 = no call yet / the call failed before converting anything.  A call that ends in
+ * SPRK_ERANGE converted the batch (1 or 2). */
+int sprk_pack_last_route(void);
+
 /* ---- multi-GPU: the path's one collective (the reference has no distributed path) ----
  * Batch rows are sharded over one process per GPU, tables and weights replicated; every rank ends with all scores through ONE
  * all-gather of the per-rank score slices over RCCL / xGMI, enqueued on the caller's HIP stream (no host synchronisation).

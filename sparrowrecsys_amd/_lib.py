@@ -33,7 +33,8 @@ EXPORTED_SYMBOLS = [
     "sprk_forward", "sprk_forward_many", "sprk_forward_many_opts", "sprk_forward_embedding_mlp", "sprk_forward_widedeep", "sprk_forward_neuralcf",
     "sprk_forward_deepfm", "sprk_forward_deepfm_v2", "sprk_forward_din", "sprk_forward_dien", "sprk_din_pool",
     "sprk_check_ids", "sprk_destroy", "sprk_embedding_gather", "sprk_cross_hash", "sprk_last_error",
-    "sprk_pack_csv", "sprk_pack_csv_mt", "sprk_pack_csv_device", "sprk_csv_last_path", "sprk_set_many_streams", "sprk_set_many_batches", "sprk_emb_rank",
+    "sprk_pack_csv", "sprk_pack_csv_mt", "sprk_pack_csv_device", "sprk_csv_last_path",
+    "sprk_pack_columns", "sprk_pack_columns_device", "sprk_pack_last_route", "sprk_set_many_streams", "sprk_set_many_batches", "sprk_emb_rank",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -42,6 +43,17 @@ EXPORTED_SYMBOLS = [
 
 class CsvCol(C.Structure):
     _fields_ = [("name", C.c_char_p), ("kind", C.c_int32), ("vocab", C.c_int32)]
+
+
+# storage kinds / rules of a PackCol (include/sparrow_hip.h SPRK_COL_*, SPRK_RULE_*)
+COL_BOOL, COL_I8, COL_I16, COL_I32, COL_I64, COL_U8, COL_U16, COL_U32, COL_F32, COL_F64, COL_BYTES, COL_UCS4, COL_TEXT = range(13)
+RULE_IDENTITY, RULE_GENRE, RULE_DENSE = range(3)
+PACK_MAX_COLS = 128
+
+
+class PackCol(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("stride", C.c_int64), ("storage", C.c_int32), ("width", C.c_int32), ("on_device", C.c_int32),
+                ("rule", C.c_int32), ("vocab", C.c_int32), ("reserved", C.c_int32), ("name", C.c_char_p)]
 
 
 class Seg(C.Structure):
@@ -229,6 +241,9 @@ def load_library():
                                          C.POINTER(i32)]
         lib.sprk_pack_csv_device.argtypes = [vp, sz, C.POINTER(CsvCol), i32, C.POINTER(C.c_char_p), i32, i32, vp, vp, C.POINTER(i32), vp]
         lib.sprk_csv_last_path.argtypes = []
+        lib.sprk_pack_columns.argtypes = [C.POINTER(PackCol), i32, C.POINTER(PackCol), i32, C.c_char_p, sz, i32, i32, vp, vp]
+        lib.sprk_pack_columns_device.argtypes = [C.POINTER(PackCol), i32, C.POINTER(PackCol), i32, C.c_char_p, sz, i32, i32, vp, vp, vp]
+        lib.sprk_pack_last_route.argtypes = []
         lib.sprk_emb_rank.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp]
         for name in EXPORTED_SYMBOLS:
             if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):

@@ -259,6 +259,38 @@ struct DevScratch {
 thread_local DevScratch g_csv_scratch;
 thread_local int g_csv_last_path = -1;
 
+// perfect hash of the 19 genre strings into 32 slots (k_csv_pack.h: csv_genre_slot): the first odd multiplier without a collision; a slot holds
+// the entry's 16 little-endian bytes, its length and its vocabulary position (-1: empty).  false = no multiplier found.
+bool genre_hash_table(unsigned long long* g_mul, unsigned long long* gt_lo, unsigned long long* gt_hi, signed char* gt_len, signed char* gt_idx) {
+    unsigned long long lo[19], hi[19];
+    unsigned len[19];
+    for (int g = 0; g < 19; ++g) {
+        const size_t n = strlen(kGenreVocab[g]);
+        lo[g] = hi[g] = 0;
+        len[g] = (unsigned)n;
+        for (size_t k = 0; k < n && k < 16; ++k) (k < 8 ? lo[g] : hi[g]) |= (unsigned long long)(unsigned char)kGenreVocab[g][k] << (8 * (k & 7));
+    }
+    unsigned long long mul = 0x9E3779B97F4A7C15ull;
+    for (int tries = 0; tries < 100000; ++tries, mul += 0x632BE59BD9B4E019ull * 2) {
+        unsigned used = 0;
+        bool ok = true;
+        for (int g = 0; g < 19 && ok; ++g) {
+            const unsigned sl = csv_genre_slot(lo[g], hi[g], len[g], mul | 1);
+            ok = !(used & (1u << sl));
+            used |= 1u << sl;
+        }
+        if (ok) break;
+    }
+    *g_mul = mul | 1;
+    for (int sl = 0; sl < 32; ++sl) { gt_idx[sl] = -1; gt_len[sl] = -1; }
+    for (int g = 0; g < 19; ++g) {
+        const unsigned sl = csv_genre_slot(lo[g], hi[g], len[g], *g_mul);
+        if (gt_idx[sl] >= 0) return false;
+        gt_lo[sl] = lo[g]; gt_hi[sl] = hi[g]; gt_len[sl] = (signed char)len[g]; gt_idx[sl] = (signed char)g;
+    }
+    return true;
+}
+
 // exclusive scan of n unsigned counters (in -> out, in place allowed), grand total -> *total_dev; sums = scratch of ceil(n / SCAN_TILE)
 void scan_u32(const unsigned* in, unsigned* out, size_t n, unsigned* sums, unsigned* total_dev, hipStream_t st) {
     const size_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
@@ -320,35 +352,7 @@ int sprk_pack_csv_device(const char* text_dev, size_t len, const sprk_csv_col* i
         for (int j = L.id_head[c]; j >= 0; j = L.id_next[j]) L.role[c] |= L.id_kind[j] == 1 ? 2 : 1;
         if (L.dense_head[c] >= 0) L.role[c] |= 1;
     }
-    {
-        // perfect hash of the 19 genre strings into 32 slots: the first odd multiplier without a collision
-        unsigned long long lo[19], hi[19];
-        unsigned len[19];
-        for (int g = 0; g < 19; ++g) {
-            const size_t n = strlen(kGenreVocab[g]);
-            lo[g] = hi[g] = 0;
-            len[g] = (unsigned)n;
-            for (size_t k = 0; k < n && k < 16; ++k) (k < 8 ? lo[g] : hi[g]) |= (unsigned long long)(unsigned char)kGenreVocab[g][k] << (8 * (k & 7));
-        }
-        unsigned long long mul = 0x9E3779B97F4A7C15ull;
-        for (int tries = 0; tries < 100000; ++tries, mul += 0x632BE59BD9B4E019ull * 2) {
-            unsigned used = 0;
-            bool ok = true;
-            for (int g = 0; g < 19 && ok; ++g) {
-                const unsigned sl = csv_genre_slot(lo[g], hi[g], len[g], mul | 1);
-                ok = !(used & (1u << sl));
-                used |= 1u << sl;
-            }
-            if (ok) break;
-        }
-        L.g_mul = mul | 1;
-        for (int sl = 0; sl < 32; ++sl) { L.gt_idx[sl] = -1; L.gt_len[sl] = -1; }
-        for (int g = 0; g < 19; ++g) {
-            const unsigned sl = csv_genre_slot(lo[g], hi[g], len[g], L.g_mul);
-            if (L.gt_idx[sl] >= 0) return fail(SPRK_EINVAL, "no perfect hash for the genre vocabulary");
-            L.gt_lo[sl] = lo[g]; L.gt_hi[sl] = hi[g]; L.gt_len[sl] = (signed char)len[g]; L.gt_idx[sl] = (signed char)g;
-        }
-    }
+    if (!genre_hash_table(&L.g_mul, L.gt_lo, L.gt_hi, L.gt_len, L.gt_idx)) return fail(SPRK_EINVAL, "no perfect hash for the genre vocabulary");
     // pass 1: newlines per chunk
     const size_t n_chunks = (len + CSV_CHUNK - 1) / CSV_CHUNK;
     const size_t sums_a = (n_chunks + SCAN_TILE - 1) / SCAN_TILE;

@@ -39,5 +39,6 @@
 #include "k_dien_fused.h"
 #include "k_peer_gather.h"
 #include "k_csv_pack.h"
+#include "k_pack_columns.h"          // feature columns -> packed ids / dense (a template: only sparrow_hip.hip instantiates it)
 #include "k_operators.h"             // stand-alone operator kernels (bit-exact gather, cross hash) -- closes the kernels' anonymous namespace
 #include "tu_instances.h"          // the heavy templates: defined in ONE family unit, `extern template` elsewhere

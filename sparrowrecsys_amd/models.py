@@ -22,7 +22,7 @@ import numpy as np
 from . import _lib as L
 from .plan import DeviceTable, PlanBuilder, pad4, pad16, pad_table
 from .schema import (GENRE_VOCAB, HISTORY_KEYS, MOVIE_BUCKETS, MOVIE_GENRE_KEYS, N_GENRES, NUMERIC_KEYS,
-                     USER_BUCKETS, USER_GENRE_KEYS, IdColumn, iter_feature_batches, pack_dense, pack_ids,
+                     USER_BUCKETS, USER_GENRE_KEYS, IdColumn, batch_size_of, iter_feature_batches, pack_dense, pack_ids,
                      to_int_column)
 
 # typical magnitude of each raw numeric column (webroot/sampledata/testSamples.csv ranges); used
@@ -385,8 +385,49 @@ class CTRModel:
         return self._engine
 
     # ---- host packing -------------------------------------------------------------------
+    # Routes of the packing, in order: device native (k_pack_columns.h), host native (sprk_pack_columns), the Python packer
+    # (schema.pack_ids / pack_dense: the definition of the result).  A native route converts the storage kinds it lists with the
+    # Python packer's bits or DECLINES the batch, and the next route takes it: results, exceptions and messages are the Python
+    # packer's whichever route ran.  SPRK_PACK_NATIVE=0 forces the Python packer (A/B runs).
+    PACK_DEVICE_MIN_ROWS = 4096      # below this a host-staged batch goes host native + asynchronous upload: the device route ends in a
+                                     # stream synchronisation, which small batches enqueued back to back (predict(batch_size=...)) would pay per batch
+
+    def _columns(self, features: Mapping, keep_device: bool = False) -> Mapping:
+        """The feature dict with one entry per packed column (models with a matrix input split it into column views)."""
+        return features
+
+    def _pack_python(self, features: Mapping) -> Tuple[np.ndarray, np.ndarray]:
+        from . import ingest
+        features = self._columns(features)
+        ids = pack_ids(features, self.id_columns)
+        dense = pack_dense(features, self.numeric_keys) if len(self.numeric_keys) else np.zeros((ids.shape[0], 0), dtype=np.float32)
+        ingest.note_route("python")
+        return ids, dense
+
     def pack(self, features: Mapping) -> Tuple[np.ndarray, np.ndarray]:
-        return pack_ids(features, self.id_columns), pack_dense(features, self.numeric_keys)
+        """-> host arrays ``(ids [B, F] int32, dense [B, N] float32)``: host native, else the Python packer (same bits)."""
+        from . import ingest
+        if not ingest.force_python():
+            got = ingest.pack_columns(self._columns(features), self.id_columns, list(self.numeric_keys))
+            if got is not None:
+                return got
+        return self._pack_python(features)
+
+    def pack_device(self, features: Mapping):
+        """-> DEVICE tensors ``(ids, dense)``: device native (CUDA tensor columns are read in place, host columns staged by the
+        library), else host native + upload, else the Python packer + upload."""
+        import torch
+
+        from . import ingest
+        if not ingest.force_python():
+            cols = self._columns(features, keep_device=True)
+            on_device = any(hasattr(v, "is_cuda") and v.is_cuda for v in cols.values())
+            if on_device or batch_size_of(cols) >= self.PACK_DEVICE_MIN_ROWS:
+                got = ingest.pack_columns_device(cols, self.id_columns, list(self.numeric_keys))
+                if got is not None:
+                    return got
+        ids, dense = self.pack(features)
+        return torch.from_numpy(ids).cuda(non_blocking=True), torch.from_numpy(dense).cuda(non_blocking=True)
 
     # ---- predict ------------------------------------------------------------------------
     def predict_device(self, ids, dense, out=None, workspace=None, stream=None):
@@ -446,11 +487,9 @@ class CTRModel:
                 outs.extend(self.predict_device_many([b[0] for b in pending], [b[1] for b in pending]))
             pending.clear()
         for feats in iter_feature_batches(x, batch_size):
-            ids, dense = self.pack(feats)
-            if ids.shape[0] == 0:
+            ids_t, dense_t = self.pack_device(feats)
+            if ids_t.shape[0] == 0:
                 continue
-            ids_t = torch.from_numpy(ids).cuda(non_blocking=True)
-            dense_t = torch.from_numpy(dense).cuda(non_blocking=True)
             if pending and (ids_t.shape[0] != pending[0][0].shape[0] or len(pending) == self.MANY_GROUP):
                 flush()
             pending.append((ids_t, dense_t))
@@ -697,10 +736,6 @@ class NeuralCF(CTRModel):
             s["head/kernel"] = (1, 1)
         s["head/bias"] = (1,)
         return s
-
-    def pack(self, features):
-        ids = pack_ids(features, self.id_columns)
-        return ids, np.zeros((ids.shape[0], 0), dtype=np.float32)
 
     def _compile(self, pb, w):
         D, Dp = self.emb_dim, pad4(self.emb_dim)
@@ -988,16 +1023,18 @@ class DIN(CTRModel):
         s["head/bias"] = (1,)
         return s
 
-    def pack(self, features):
+    def _columns(self, features, keep_device=False):
+        """``userRatedMovies [B, T]`` as T strided column views (no copy; a device tensor stays on the device when ``keep_device``)."""
         if "userRatedMovies" in features and self._hist_keys()[0] not in features:
             hist = features["userRatedMovies"]
-            hist = hist.detach().cpu().numpy() if hasattr(hist, "detach") else np.asarray(hist)
+            if not (keep_device and hasattr(hist, "detach")):
+                hist = hist.detach().cpu().numpy() if hasattr(hist, "detach") else np.asarray(hist)
             if hist.ndim != 2 or hist.shape[1] != self.hist_len:
                 raise ValueError("userRatedMovies must be [B, %d]" % self.hist_len)
             features = dict(features)
             for i, k in enumerate(self._hist_keys()):
                 features[k] = hist[:, i]
-        return super().pack(features)
+        return features
 
     def _compile(self, pb, w):
         D, Dp, T = self.emb_dim, pad4(self.emb_dim), self.hist_len
