@@ -255,8 +255,11 @@ int sprk_check_ids(sprk_handle h, void* stream);
  * when no fused kernel matched the plan and the generic plan interpreter runs it (fused=0: several times slower -- a shape that
  * silently fell off the fast path is visible here); stage = the history stage of DIN / DIEN handles (k_din_attn, k_din_pool,
  * k_dien_seq) or empty; uploaded_bytes / derived_bytes = device memory of the uploaded slots and of the tables derived from them
- * at finalize (folded rows, split halfs, per-id terms); first_dense_fold = embedding columns folded into the first Dense layer.
- * SPRK_EINVAL when the buffer is too small (256 bytes always suffice). */
+ * at finalize (folded rows, split halfs, per-id terms); first_dense_fold = embedding columns folded into the first Dense layer;
+ * split_f16 = the sites of that route and stage whose operand runs as hi + lo f16 halves under a STATIC power-of-two scale chosen
+ * at finalize, comma separated (v2, pairs_e, rows_unf, tail_unf, dyn_w1, dyn_w0, dyn_w0p, din_attn, dien_seq) --
+ * a site that a range guard, a non-finite weight or a switch refused is absent and runs f32; empty = everything f32.
+ * SPRK_EINVAL when the buffer is too small (512 bytes always suffice). */
 int sprk_describe(sprk_handle h, char* buf, size_t buf_bytes);
 
 void sprk_destroy(sprk_handle h);

@@ -519,8 +519,34 @@ int sprk_describe(sprk_handle h, char* buf, size_t buf_bytes) {
 #ifndef SPRK_BUILD_DEFINES_STR
 #define SPRK_BUILD_DEFINES_STR ""                             // (_lib.build_library passes the experiment defines of SPRK_BUILD_DEFINES; the product build has none)
 #endif
-    const int n = snprintf(buf, buf_bytes, "kernel=%s;stage=%s;stage_waves_per_workgroup=%d;fused=%d;uploaded_bytes=%zu;derived_bytes=%zu;first_dense_fold=%d;build_defines=%s", kern,
-                           kStageName[(int)h->stage], cols ? DC_WAVES : 0, h->route != Route::Tile ? 1 : 0, uploaded, h->derived_bytes, h->n_acc_folded, SPRK_BUILD_DEFINES_STR);
+    // split_f16: the sites of the route and stage in use whose operand runs as hi + lo f16 halves with a STATIC scale chosen at finalize (a
+    // site a range guard, a non-finite weight or a switch refused is absent: it runs f32; empty = everything f32).  v2 = DeepFM_v2's folded
+    // rows and W0; pairs_e = the pair-dot deep tables; rows_unf = the rows chain's raw rows and projection weights; tail_unf = the DIN / DIEN
+    // tail's raw rows and fc0 columns; dyn_w1 / dyn_w0 / dyn_w0p = weight fragments of the per-sample dynamic chains (make_dyn_fragments);
+    // din_attn = the attention tables; dien_seq = DIEN's sequence stage
+    char split[96] = "";
+    auto site = [&](bool on, const char* name) {
+        if (!on) return;
+        if (split[0]) strncat(split, ",", sizeof(split) - strlen(split) - 1);
+        strncat(split, name, sizeof(split) - strlen(split) - 1);
+    };
+    switch (h->route) {
+    case Route::V2Joint: site(kV2JVariants[h->v2j_variant].half, "v2"); break;
+    case Route::Pairs:
+        site(h->v1_run.w1frag != nullptr, "dyn_w1"); site(h->v1_run.w0frag != nullptr, "dyn_w0"); site(h->v1_run.e_scale != 0.f, "pairs_e");
+        break;
+    case Route::Rows: site(kRowsVariants[h->rows_variant].unf, "rows_unf"); break;
+    case Route::MlpRows: site(h->mlp_rows_run.inv_w1_scale != 0.f, "dyn_w1"); break;
+    case Route::DinTail: case Route::DinFused: case Route::DienFused:
+        site(h->din_tail_run.inv_w1_scale != 0.f, "dyn_w1"); site(h->din_tail_run.inv_w0p_scale != 0.f, "dyn_w0p");
+        site(h->din_tail_run.e_unscale != 0.f, "tail_unf");
+        break;
+    case Route::Tile: break;
+    }
+    site(cols, "din_attn");
+    site(h->stage == Stage::DienSeqMfma, "dien_seq");
+    const int n = snprintf(buf, buf_bytes, "kernel=%s;stage=%s;stage_waves_per_workgroup=%d;fused=%d;uploaded_bytes=%zu;derived_bytes=%zu;first_dense_fold=%d;split_f16=%s;build_defines=%s", kern,
+                           kStageName[(int)h->stage], cols ? DC_WAVES : 0, h->route != Route::Tile ? 1 : 0, uploaded, h->derived_bytes, h->n_acc_folded, split, SPRK_BUILD_DEFINES_STR);
     if (n < 0 || (size_t)n >= buf_bytes) return fail(SPRK_EINVAL, "describe: buffer of %zu bytes is too small", buf_bytes);
     return SPRK_OK;
 }

@@ -133,6 +133,22 @@ int wide_dynamic_range(const float* rows, long long nrows, int row_floats, int n
     return SPRK_OK;
 }
 
+// The same rule for weights the host already holds (pulled for packing): absmax_nan keeps a NaN that fmaxf would drop, so that the callers'
+// `mx < 3.0e38f` refuses non-finite weights; wide_dynamic_range_host counts over v[0 .. n).
+inline float absmax_nan(float m, float v) { const float a = fabsf(v); return (a > m || a != a) ? a : m; }
+bool wide_dynamic_range_host(const float* v, size_t n, float mx) {
+    const bool guard_on = g_finalize_tune ? g_finalize_tune->half_range_guard : SprkTuning::from_env().half_range_guard;
+    if (!guard_on || !(mx > 0.f)) return false;
+    const float thresh = ldexpf(mx, -20);
+    unsigned long long small = 0, nz = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const float a = fabsf(v[i]);
+        nz += a > 0.f;
+        small += a > 0.f && a < thresh;
+    }
+    return small * 1024ull > nz;
+}
+
 // A static split-f16 scale: the power of two that puts m * scale in [2^14, 2^15), the exponent clamped to +-60; 1 for m <= 0.
 float pow2_scale(float m) {
     int e = 0;

@@ -3,8 +3,10 @@
 // Part of sparrow_hip.hip (one translation unit); included there, not compilable on its own.
 
 // DIEN.py's sequence stage (GRU -> attention gate -> AUGRU).  Sixteen samples per wave on the matrix pipe (k_dien_mfma.h) where the shape
-// allows: the host's packed image -> split-f16 MFMA A fragments with static scales from max|E| and the weights' row sums; non-finite
-// weights keep the lane-per-sample kernel (dien_frag = NULL).
+// allows: the host's packed image -> split-f16 MFMA A fragments with static scales from max|E| and the weights' row sums.  The
+// lane-per-sample kernel stays (dien_frag = NULL, exact f32) for a non-finite table or weight, for a movie table the dynamic-range guard
+// calls wide (an outlier row: s_xh and s_p come from max|E|, and [x ; h] share s_xh, so the ordinary rows AND the bounded state would lose
+// their lo halves), and for weights k_dien_mfma_pack refuses (a block whose entries span more than 2^20).
 int setup_dien_stage(sprk_engine* h, DevDin& d) {
     const sprk_plan& p = h->plan;
     const sprk_din& s = p.din;
@@ -25,10 +27,18 @@ int setup_dien_stage(sprk_engine* h, DevDin& d) {
     HIP_TRY(d_max.alloc(1));
     HIP_TRY(hipMemset(d_max.p, 0, sizeof(unsigned)));
     hipLaunchKernelGGL(k_v2_absmax, dim3(1024), dim3(256), 0, 0, d.table, (long long)s.vocab, s.row_stride, s.row_stride, d_max.p);
+    HIP_TRY(hipGetLastError());
+    float maxE = 0.f;
+    HIP_TRY(hipMemcpy(&maxE, d_max.p, sizeof(float), hipMemcpyDeviceToHost));
+    if (!(maxE < 3.0e38f)) return SPRK_OK;                    // NaN / Inf in the table
+    bool wide = false;
+    SPRK_TRY(wide_dynamic_range(d.table, (long long)s.vocab, s.row_stride, s.row_stride, maxE, &wide));
+    if (wide) return SPRK_OK;
+    const bool guard_on = h->tune.half_range_guard;
     float* frag = nullptr;
     SPRK_TRY(dev_alloc(h, &frag, fl * sizeof(float)));
-    if (d10) hipLaunchKernelGGL((k_dien_mfma_pack<10, 32>), dim3(1), dim3(256), 0, 0, r.image, (const unsigned*)d_max.p, frag);
-    else hipLaunchKernelGGL((k_dien_mfma_pack<16, 32>), dim3(1), dim3(256), 0, 0, r.image, (const unsigned*)d_max.p, frag);
+    if (d10) hipLaunchKernelGGL((k_dien_mfma_pack<10, 32>), dim3(1), dim3(256), 0, 0, r.image, (const unsigned*)d_max.p, frag, guard_on ? 1 : 0);
+    else hipLaunchKernelGGL((k_dien_mfma_pack<16, 32>), dim3(1), dim3(256), 0, 0, r.image, (const unsigned*)d_max.p, frag, guard_on ? 1 : 0);
     HIP_TRY(hipGetLastError());
     float ok = 0.f;
     HIP_TRY(hipMemcpy(&ok, frag + ok_at, sizeof(float), hipMemcpyDeviceToHost));

@@ -160,8 +160,16 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
             float amax = 0.f;
             for (int g = 0; g < dp->n_acc; ++g)
                 for (int n = 0; n < q0.N; ++n)
-                    for (int d = 0; d < 4 * raw[g]->count; ++d) amax = fmaxf(amax, fabsf(W0h[(size_t)n * q0.ldw + raw[g]->dst - q0.src_off + d]));
-            ok = amax < 3.0e38f;
+                    for (int d = 0; d < 4 * raw[g]->count; ++d) amax = absmax_nan(amax, W0h[(size_t)n * q0.ldw + raw[g]->dst - q0.src_off + d]);
+            ok = amax < 3.0e38f;                                   // NaN / Inf in fc0's columns: the folded tables
+            // an outlier weight: the ordinary columns' lo halves would be subnormal (the rule of wide_dynamic_range over fc0's raw-row columns)
+            if (ok) {
+                std::vector<float> cols;
+                for (int g = 0; g < dp->n_acc; ++g)
+                    for (int n = 0; n < q0.N; ++n)
+                        for (int d = 0; d < 4 * raw[g]->count; ++d) cols.push_back(W0h[(size_t)n * q0.ldw + raw[g]->dst - q0.src_off + d]);
+                ok = !wide_dynamic_range_host(cols.data(), cols.size(), amax);
+            }
             if (ok) {
                 const float w_scale = pow2_scale(amax);
                 std::vector<float> fr((size_t)n0c * nblk * 512, 0.f);

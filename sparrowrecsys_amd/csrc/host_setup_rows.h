@@ -79,7 +79,7 @@ int rows_finish(sprk_engine* h, const RowsVariant& rv, const std::vector<float>&
 
 // DeepFM_v2 plans whose projection width has no k_deepfm_v2_joint instantiation (the reference's own Dense(64)): every field
 // becomes a table of rows {P | W0^T P} (+ scalars), see k_rows_chain.h.  h->v2 holds the parsed plan (match_v2_chain).
-int setup_rows_v2(sprk_engine* h) {
+int setup_rows_v2(sprk_engine* h, bool allow_unf = true) {
     const V2Args& a = h->v2;
     const sprk_plan& p = h->plan;
     const int G = h->rows_g_emb;
@@ -95,7 +95,7 @@ int setup_rows_v2(sprk_engine* h) {
     // matrix pipe -- when the fold would multiply the bytes per row (emb_dim 10 -> 96 floats for DeepFM_v2.py as written)
     int variant = -1;
     float p_scale = 1.f;
-    if (h->tune.rows_unf && h->tune.dyn_f16 && nbig <= 2 && Dp <= 16 && KP + H0 > 16) {
+    if (allow_unf && h->tune.rows_unf && h->tune.dyn_f16 && nbig <= 2 && Dp <= 16 && KP + H0 > 16) {
         const int vu = find_rows_variant(KP / 16, H0 / 16, H1 / 16, nbig, nsm, true, true);
         if (vu >= 0) {
             std::vector<AbsmaxJob> jobs;
@@ -238,11 +238,25 @@ int setup_rows_v2(sprk_engine* h) {
         const int W = KP + H0;
         float amax = 0.f;
         for (int b = 0; b < nbig; ++b) {
-            for (float v : lin[b]) amax = fmaxf(amax, fabsf(v));
+            for (float v : lin[b]) amax = absmax_nan(amax, v);
             for (int n = 0; n < KP; ++n) img[off_cp + n] += cst[b][n];
             for (int m = 0; m < H0; ++m) img[off_c0 + m] += cst[b][KP + m];
         }
-        if (!(amax < 3.0e38f)) return fail(SPRK_EINVAL, "non-finite projection weights");
+        // non-finite projection weights, or an outlier among them (the others' lo halves would be subnormal): like every other static-scale
+        // site, keep the f32 form -- here the folded rows {P | W0^T P}, built by the same function once the raw-row tables are released
+        bool refuse = !(amax < 3.0e38f);
+        if (!refuse) {
+            std::vector<float> all;
+            for (int b = 0; b < nbig; ++b) all.insert(all.end(), lin[b].begin(), lin[b].end());
+            refuse = wide_dynamic_range_host(all.data(), all.size(), amax);
+        }
+        if (refuse) {
+            HIP_TRY(hipDeviceSynchronize());
+            dev_free(h, h->rows_tab); dev_free(h, h->rows_scal); dev_free(h, h->rows_small);
+            h->rows_tab = nullptr; h->rows_scal = nullptr; h->rows_small = nullptr;
+            h->derived_bytes -= big_rows * rv.rb + big_rows * sizeof(float);
+            return setup_rows_v2(h, false);
+        }
         const float w_scale = pow2_scale(amax);
         _Float16* fh = reinterpret_cast<_Float16*>(&img[off_af]);
         for (int nb = 0; nb < W / 16; ++nb)

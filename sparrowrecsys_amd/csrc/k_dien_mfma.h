@@ -57,7 +57,7 @@ __device__ inline float dm_scale14(float bound) {
 
 template <int D, int H>
 __global__ __launch_bounds__(256) void k_dien_mfma_pack(const float* __restrict__ img, const unsigned* __restrict__ table_absmax_bits,
-                                                        float* __restrict__ out) {
+                                                        float* __restrict__ out, int range_guard) {
     using LY = DienLayout<D, H>;
     using FR = DienFrag<D, H>;
     __shared__ float sA[DM_BLOCKS], sB[DM_BLOCKS], sc[8];
@@ -96,17 +96,27 @@ __global__ __launch_bounds__(256) void k_dien_mfma_pack(const float* __restrict_
             s_pre[g] = dm_scale14(bound);
         }
         bool ok = s_xh > 0.f && s_p > 0.f && s_gs > 0.f && s_pre[0] > 0.f && s_pre[1] > 0.f && s_pre[2] > 0.f;
+        // the dynamic-range rule of wide_dynamic_range over the twelve blocks, each against its own maximum: an outlier weight would push the
+        // other entries of its block into f16 subnormals -> ok = 0 (the host keeps the lane-per-sample kernel)
+        unsigned n_small = 0, n_nz = 0;
         for (int blk = 0; blk < DM_BLOCKS; ++blk) {
             float mx = 0.f;
             for (int chunk = 0; chunk < 2; ++chunk)
                 for (int k = 0; k < D; ++k)
-                    for (int n = 0; n < 16; ++n) mx = fmaxf(mx, fabsf(wt(blk, chunk, k, n)));
+                    for (int n = 0; n < 16; ++n) { const float a = fabsf(wt(blk, chunk, k, n)); mx = (a > mx || a != a) ? a : mx; }   // (a NaN stays)
             float s = 0.f;
             if (mx < 3.0e38f) { int e = 0; if (mx > 0.f) (void)frexpf(mx, &e); e = 15 - e; e = e > 60 ? 60 : (e < -60 ? -60 : e); s = ldexpf(1.f, e); }
             ok = ok && s > 0.f;
+            if (range_guard && mx < 3.0e38f) {
+                const float thresh = ldexpf(mx, -20);
+                for (int chunk = 0; chunk < 2; ++chunk)
+                    for (int k = 0; k < D; ++k)
+                        for (int n = 0; n < 16; ++n) { const float a = fabsf(wt(blk, chunk, k, n)); n_nz += a > 0.f; n_small += a > 0.f && a < thresh; }
+            }
             sA[blk] = s;
             sB[blk] = blk < 4 ? s_xh : blk < 6 ? s_p : (blk == 6 || blk == 7 || blk == 10) ? s_gs : s_pre[blk == 8 ? 0 : blk == 9 ? 1 : 2];
         }
+        ok = ok && !(n_small * 1024u > n_nz);
         sc[0] = s_xh; sc[1] = s_p; sc[2] = s_gs; sc[3] = s_pre[0]; sc[4] = s_pre[1]; sc[5] = s_pre[2]; sc[6] = ok ? 1.f : 0.f;
     }
     __syncthreads();

@@ -571,8 +571,11 @@ def test_deepfm_v2_split_f16_is_fp32_class(torch, monkeypatch):
             monkeypatch.setenv("SPRK_V2_HALF", half)
             p = M.DeepFMv2(weights=w, emb_dim=16, fields=fields, proj_dim=16).predict(feats)[:, 0]
             err[half] = float(np.abs(p - ref).max())
-        print("split-f16 vs f32 MFMA, table scale %g: max|err| vs fp64 oracle %.3g (split) %.3g (f32), score std %.3f"
-              % (table_scale, err["1"], err["0"], ref.std()))
+        # (table scale 37 is a SATURATION check, not an accuracy check: about 1.5 % of its oracle scores have |logit| < 8, and the score std it
+        # passes with is that of scores at 0 / 1 -- see the printed live share; live inputs at every scale: tests/test_gpu_value_range.py)
+        from tests.value_range_cases import live_share
+        print("split-f16 vs f32 MFMA, table scale %g: max|err| vs fp64 oracle %.3g (split) %.3g (f32), score std %.3f, live share %.3f"
+              % (table_scale, err["1"], err["0"], ref.std(), live_share(ref)))
         assert 0.02 < ref.std()
         assert err["1"] <= TOL and err["0"] <= TOL, (table_scale, err)
         assert err["1"] <= 2 * err["0"] + 2e-6, (table_scale, err)
@@ -738,7 +741,10 @@ def test_din_tail_dynamic_f16_wide_activation_range(torch, monkeypatch, scale):
     ref = O.din_forward(feats, model.weights, dtype=np.float64, hist_len=T, movie_buckets=V, user_buckets=U)[:, 0]
     assert np.isfinite(out["1"]).all()
     e1, e0 = np.abs(out["1"] - ref).max(), np.abs(out["0"] - ref).max()
-    print("scale %g: dyn-f16 err %.3e, f32-MFMA err %.3e" % (scale, e1, e0))
+    # (scale 300 is a SATURATION check, not an accuracy check: under a tenth of its oracle scores have |logit| < 8 -- see the printed live
+    # share; live inputs over the same range: tests/test_gpu_value_range.py)
+    from tests.value_range_cases import live_share
+    print("scale %g: dyn-f16 err %.3e, f32-MFMA err %.3e, live share %.3f" % (scale, e1, e0, live_share(ref)))
     if scale <= 1.0:                       # at 300x the logits reach 1e5: fp32 itself cannot hold 1e-4 on the sigmoid
         assert e1 <= TOL and e0 <= TOL
     # the f16-split path is no worse than twice the f32-MFMA path (+ fp32 rounding of the sigmoid)
