@@ -12,7 +12,7 @@ MAP = {"deepfm_v2_c2": ("c2", "k_deepfm_v2_joint", 65536), "deepfm_v2_c2_hbm_res
        "widedeep_c5": ("c5", "k_mlp_rows", 131072), "deepfm_v2_ref": ("v2ref", "k_rows_chain", 65536)}
 if rnd >= "r06":       # round 6's tags (scripts/r06/20_profiles.sh) and the kernels those workloads dispatch since rounds 3-5
     MAP = {"deepfm_v2_c2": ("c2", "k_deepfm_v2_joint1", 65536), "deepfm_v2_c2_hbm_resident": ("c2_hbm", "k_deepfm_v2_joint1", 65536),
-           "deepfm_c2": ("c2_pairs", "k_deepfm_pairs1", 65536), "din_c3": ("c3", "k_din_fused<2, false, true, false, 0>", 32768),
+           "deepfm_c2": ("c2_pairs", "k_deepfm_pairs1", 65536), "din_c3": ("c3", "k_din_fused<2, false, true, false>", 32768),
            "deepfm_c4": ("c4_pairs", "k_deepfm_pairs", 65536), "widedeep_c5": ("c5", "k_mlp_rows", 131072), "deepfm_v2_ref": ("v2_ref", "k_rows_chain1", 65536)}
 for wl, (tag, kern, batch) in MAP.items():
     try:

@@ -101,11 +101,10 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     (hipcc cross-compiles without a GPU)."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc)] + [os.path.join(INCLUDE_DIR, "sparrow_hip.h")]
-    # [r5, ADVICE r04] the experiment defines are part of what "fresh" means: a library built once with SPRK_BUILD_DEFINES (other wave
-    # counts, ablation kernels, the stamped-timeline build's file writes) must not be reused as the product after the variable is
-    # unset, nor the product when it is set.  The string the library was built with sits next to it.
+    # [r5, ADVICE r04] the experiment defines are part of what "fresh" means: a library built once with SPRK_BUILD_DEFINES must not be
+    # reused as the product after the variable is unset, nor the product when it is set.  The string the library was built with sits
+    # next to it.
     defines = " ".join(os.environ.get("SPRK_BUILD_DEFINES", "").split())
-    stamp_defines = defines
     stamp = LIB_PATH + ".defines"
     def fresh():
         if not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(d) for d in deps):
@@ -114,7 +113,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
             built_with = open(stamp).read().strip()
         except OSError:
             built_with = ""                                       # (no stamp: a product build of an earlier tree)
-        return built_with == stamp_defines
+        return built_with == defines
     if not force and fresh():
         return LIB_PATH
     # several processes (one rank per GPU, pytest-xdist workers) may get here at once: one builds, the others wait
@@ -135,15 +134,11 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
             import tempfile
             from concurrent.futures import ThreadPoolExecutor
             units = [SRC_PATH] + sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.startswith("tu_") and f.endswith(".hip"))
-            # [r6, ADVICE r05] the stamped-timeline builds (-DSPRK_DF_XP) keep their stamps in `static __device__` arrays that sprk_destroy reads
-            # with hipMemcpyFromSymbol: split over units, every unit has its own copy and the main unit's is all zeros.  One unit for those.
-            if "SPRK_DF_XP" in defines or "SPRK_SINGLE_TU" in defines:
+            if "SPRK_SINGLE_TU" in defines:                       # one unit: sparrow_hip.hip includes every kernel header itself
                 units = [SRC_PATH]
-                if "SPRK_SINGLE_TU" not in defines:
-                    defines = defines + " -DSPRK_SINGLE_TU"
             flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
                      "-I", INCLUDE_DIR, "-I", csrc]               # [r6] hidden by default: include/sparrow_hip.h's declarations are the only exports
-            if defines:                                           # experiment builds (e.g. -DSPRK_DF_XP: k_din_fused's ablation variants)
+            if defines:                                           # experiment builds
                 flags = defines.split() + ["-DSPRK_BUILD_DEFINES_STR=\"%s\"" % defines.replace('"', "'")] + flags
             objdir = tempfile.mkdtemp(prefix="sprk_obj_")
             try:
@@ -168,7 +163,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
                 shutil.rmtree(objdir, ignore_errors=True)
             os.replace(tmp, LIB_PATH)
             with open(stamp, "w") as f:
-                f.write(stamp_defines + "\n")
+                f.write(defines + "\n")
             return LIB_PATH
         finally:
             fcntl.flock(lock, fcntl.LOCK_UN)

@@ -49,28 +49,6 @@ static int launch_din_fused(sprk_handle h, const int32_t* ids, const float* dens
 #define DF_LAUNCH(KC, MB, TAIL, marg)                                                                                                   \
     hipLaunchKernelGGL((k_din_fused<KC, MB, TAIL>), dim3((unsigned)grid), dim3(DF_WAVES * 64), lds, st, c, MB ? (const int*)nullptr : ids, \
                        MB ? (const float*)nullptr : dense, MB ? (float*)nullptr : out, MB ? (float*)nullptr : att, B, h->dev_err, marg)
-#ifdef SPRK_DF_XP
-    if (h->tune.df_xp == 128 && kc == 2 && many && tail) {        // the persistent form without the folded rows' gathers
-        hipLaunchKernelGGL((k_din_fused<2, true, true, false, 128>), dim3((unsigned)grid), dim3(DF_WAVES * 64), lds, st, c, (const int*)nullptr,
-                           (const float*)nullptr, (float*)nullptr, (float*)nullptr, B, h->dev_err, *many);
-        HIP_TRY(hipGetLastError());
-        return SPRK_OK;
-    }
-    if (h->tune.df_xp >= 128 && kc == 2 && !many && tail) {       // the tail's ablations
-#define DF_XPT(X) case X: hipLaunchKernelGGL((k_din_fused<2, false, true, false, X>), dim3((unsigned)grid), dim3(DF_WAVES * 64), lds, st, c, ids, dense, out, att, B, h->dev_err, DinFusedOne{}); break;
-        switch (h->tune.df_xp) { DF_XPT(128) DF_XPT(256) DF_XPT(512) DF_XPT(896) DF_XPT(1024) default: return fail(SPRK_EINVAL, "SPRK_DF_XP=%d is not compiled in", h->tune.df_xp); }
-#undef DF_XPT
-        HIP_TRY(hipGetLastError());
-        return SPRK_OK;
-    }
-    if (h->tune.df_xp && h->tune.df_xp < 128 && kc == 2 && !many && !tail && !att) {     // ablation builds only (scripts/r04): garbage out, the time is the point
-#define DF_XP(X) case X: hipLaunchKernelGGL((k_din_fused<2, false, false, false, X>), dim3((unsigned)grid), dim3(DF_WAVES * 64), lds, st, c, ids, dense, out, att, B, h->dev_err, DinFusedOne{}); break;
-        switch (h->tune.df_xp) { DF_XP(1) DF_XP(2) DF_XP(4) DF_XP(8) DF_XP(16) DF_XP(32) DF_XP(64) DF_XP(3) DF_XP(56) DF_XP(60) DF_XP(63) DF_XP(127) DF_XP(65) DF_XP(126) default: return fail(SPRK_EINVAL, "SPRK_DF_XP=%d is not compiled in", h->tune.df_xp); }
-#undef DF_XP
-        HIP_TRY(hipGetLastError());
-        return SPRK_OK;
-    }
-#endif
     if (many) {
         if (kc == 2) { if (tail) DF_LAUNCH(2, true, true, *many); else DF_LAUNCH(2, true, false, *many); }
         else { if (tail) DF_LAUNCH(1, true, true, *many); else DF_LAUNCH(1, true, false, *many); }
@@ -566,35 +544,6 @@ int sprk_check_ids(sprk_handle h, void* stream) {
 }
 
 void sprk_destroy(sprk_handle h) {
-#ifdef SPRK_DF_XP
-    if (h) {
-        if (const char* path = getenv("SPRK_V2J1_TS_FILE")) {      // k_deepfm_v2_joint1's timeline: the LAST launch's stamps
-            std::vector<unsigned long long> ts((size_t)V2J1_TS_WAVES * 8);
-            hipDeviceSynchronize();
-            if (hipMemcpyFromSymbol(ts.data(), HIP_SYMBOL(g_v2j1_ts), ts.size() * 8) == hipSuccess) {
-                if (FILE* fp = fopen(path, "wb")) { fwrite(ts.data(), 8, ts.size(), fp); fclose(fp); }
-            }
-        }
-    }
-    if (h) {
-        if (const char* path = getenv("SPRK_MR_TS_FILE")) {        // k_mlp_rows' timeline: the LAST launch's stamps
-            std::vector<unsigned long long> ts((size_t)MR_TS_WAVES * MR_TS_SLOTS);
-            hipDeviceSynchronize();
-            if (hipMemcpyFromSymbol(ts.data(), HIP_SYMBOL(g_mr_ts), ts.size() * 8) == hipSuccess) {
-                if (FILE* fp = fopen(path, "wb")) { fwrite(ts.data(), 8, ts.size(), fp); fclose(fp); }
-            }
-        }
-    }
-    if (h && h->tune.df_xp == 1024) {                              // the timeline build: the LAST launch's stamps -> $SPRK_DF_TS_FILE
-        if (const char* path = getenv("SPRK_DF_TS_FILE")) {
-            std::vector<unsigned long long> ts((size_t)DF_TS_WAVES * 8);
-            hipDeviceSynchronize();
-            if (hipMemcpyFromSymbol(ts.data(), HIP_SYMBOL(g_df_ts), ts.size() * 8) == hipSuccess) {
-                if (FILE* fp = fopen(path, "wb")) { fwrite(ts.data(), 8, ts.size(), fp); fclose(fp); }
-            }
-        }
-    }
-#endif
     if (!h) return;
     for (size_t i = 0; i < h->slot_ptr.size(); ++i) free_slot(h, i);
     for (const sprk_engine::DevAlloc& a : h->allocs) release(a);

@@ -273,12 +273,6 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_full));
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_full));
             HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_full));
-#ifdef SPRK_DF_XP
-#define DF_XPT_ATTR(X) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<2, false, true, false, X>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_full));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<2, true, true, false, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_full));
-            DF_XPT_ATTR(128) DF_XPT_ATTR(256) DF_XPT_ATTR(512) DF_XPT_ATTR(896) DF_XPT_ATTR(1024)
-#undef DF_XPT_ATTR
-#endif
             h->din_fused = true;
         }
     }

@@ -527,15 +527,10 @@ __device__ __forceinline__ void v2j_body(const V2JRun& A, const int* __restrict_
     }
     // weight image -> LDS by LDS-DMA (no VGPRs, no ds_write pass): 1-KB pieces, wave w takes w, w+WAVES, ...
 #pragma unroll 1
-    for (int c = wave; c < LD::total_pad / 256; c += WAVES)
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(image + c * 256 + lane * 4),
-            (__attribute__((address_space(3))) void*)(smem + c * 256), 16, 0, 0);
+    for (int c = wave; c < LD::total_pad / 256; c += WAVES) lds_dma16(image + c * 256 + lane * 4, smem + c * 256);
+    // ... and the small fields' rows
 #pragma unroll 1
-    for (int c = wave; c < A.small_floats / 256; c += WAVES)          // ... and the small fields' rows
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(A.small + c * 256 + lane * 4),
-            (__attribute__((address_space(3))) void*)(smem + LD::total_pad + WAVES * LD::stage_floats + c * 256), 16, 0, 0);
+    for (int c = wave; c < A.small_floats / 256; c += WAVES) lds_dma16(A.small + c * 256 + lane * 4, smem + LD::total_pad + WAVES * LD::stage_floats + c * 256);
     // At most two tasks per wave (B <= 65 536 on a full chip): no loop, hence no loop-carried loads -- the
     // compiler counts every outstanding load exactly and score(A) waits for A's rows only, running while
     // B's rows are still streaming in.  (At a loop header hipcc falls back to waiting for ALL outstanding

@@ -23,36 +23,20 @@
 // [r5] with the leaner image sixteen win wherever the rows come out of the caches -- config 2 6.88-6.95 against 6.97-6.99 us, config 4
 // 5.90 against 6.09 (profiles/r05/experiments/r05_02): one image staging per CU instead of two -- and lose where they come from HBM
 // (9.03 against 8.70-8.78 us on one box, r05_03): the HOIST form keeps eight.
-#ifndef V2J1_WAVES
 #define V2J1_WAVES 16
-#endif
-#ifndef V2J1_WAVES_HOIST
 #define V2J1_WAVES_HOIST 8
-#endif
 // (HBM-resident rows AND three gathered fields: config 2 on 8 M-row tables 8.6-8.9 us with eight waves, 8.7-9.0 with sixteen; config 4's two
 //  fields -- 27 M-row table -- 6.1-6.2 against 5.9: r05_02 .. r05_05)
 #define V2J1_WAVES_OF(HOIST, G_BIG) (((HOIST) && (G_BIG) >= 3) ? V2J1_WAVES_HOIST : V2J1_WAVES)
-#ifndef V2J1_DEDUP
-#define V2J1_DEDUP 1                         // [r5] A fragments stored ONCE per (field, n-block) as {hi4 | lo4}: one ds_read_b128 where there were two, the selection fragment built in registers
-#endif
-#ifndef V2J1_ZZ_LATE
-#define V2J1_ZZ_LATE 1                       // [r5] the rows' first-order scalar is consumed BEHIND the row fence (it is the last load issued: see phase A); not in the HOIST form
-#endif
 #define V2J1_MAX_TASKS 16384                 // B <= 262 144: beyond, the looped kernel amortises the image staging better
 
 template <int G_BIG>
 struct V2J1Lds {
-#if V2J1_DEDUP
+    // [r5] A fragments stored ONCE per (field, n-block) as {hi4 | lo4}: one ds_read_b128 where there were two; no selection fragment in the
+    // image (built in registers)
     static constexpr int off_frag = 0;                              // [G_BIG][2 n-blocks] A fragments {hi4 | lo4} per lane, 256 floats (1 KB) each
-    static constexpr int off_sel = off_frag + G_BIG * 2 * 256;      // (no selection fragment in the image: built in registers)
     static constexpr int S1 = 36;
-    static constexpr int off_w1 = off_sel;                          // deep1 W^T [16][S1]
-#else
-    static constexpr int off_frag = 0;                              // [G_BIG][2 n-blocks][hi, lo] A fragments, 256 floats (1 KB) each
-    static constexpr int off_sel = off_frag + G_BIG * 4 * 256;      // the 0/1 selection fragment (FM sum of hi + lo)
-    static constexpr int S1 = 36;
-    static constexpr int off_w1 = off_sel + 256;                    // deep1 W^T [16][S1]
-#endif
+    static constexpr int off_w1 = off_frag + G_BIG * 2 * 256;       // deep1 W^T [16][S1]
     static constexpr int off_b1 = off_w1 + 16 * S1;                 // [16]
     static constexpr int off_hd = off_b1 + 16;                      // [16] head weights on deep1's output
     static constexpr int off_bpn = off_hd + 16;                     // [16] numeric projection bias
@@ -63,17 +47,12 @@ struct V2J1Lds {
     static constexpr int total_pad = (total + 255) & ~255;
 };
 
-// One-time (finalize) kernel, one block.  Fragment (b, n0, part) lane l = (r = l & 15, q = l >> 4) holds 8 halfs
-// {h[0..3], h[0..3]} of W0[n0*16 + r][16*grp_b + 4q + j] * w_scale, h = hi (part 0) or lo (part 1): exactly the registers
-// v2j_body's load_weights() builds with split_half4 at every launch.
+// One-time (finalize) kernel, one block.  Fragment (b, n0) lane l = (r = l & 15, q = l >> 4) holds 8 halfs
+// {hi[0..3], lo[0..3]}, the split_half4 of W0[n0*16 + r][16*grp_b + 4q + j] * w_scale: the hi and lo registers
+// v2j_body's load_weights() builds at every launch, side by side.
 static __global__ __launch_bounds__(256) void k_v2j1_pack_image(const V2Args A, const V2JRun R, int g_big, int G, float* __restrict__ img) {
     const int tid = threadIdx.x;
-#if V2J1_DEDUP
-    const int off_sel = g_big * 2 * 256, off_w1 = off_sel;
-#else
-    const int off_sel = g_big * 4 * 256, off_w1 = off_sel + 256;
-#endif
-    const int off_b1 = off_w1 + 16 * 36, off_hd = off_b1 + 16, off_bpn = off_hd + 16,
+    const int off_w1 = g_big * 2 * 256, off_b1 = off_w1 + 16 * 36, off_hd = off_b1 + 16, off_bpn = off_hd + 16,
               off_hfm = off_bpn + 16, off_wn8 = off_hfm + 16, off_fn8 = off_wn8 + 128, total_pad = (off_fn8 + 8 + 255) & ~255;
     for (int i = tid; i < total_pad; i += 256) img[i] = 0.f;
     __syncthreads();
@@ -83,21 +62,8 @@ static __global__ __launch_bounds__(256) void k_v2j1_pack_image(const V2Args A, 
         const f32x4 w = ld4(A.W0 + (size_t)(n0 * 16 + r) * (G * 16) + 16 * R.big_grp[b] + 4 * q);
         f16x4 hi, lo;
         split_half4(w, R.w_scale, hi, lo);
-#if V2J1_DEDUP
         frag[(b * 2 + n0) * 64 + l] = f16x8{hi[0], hi[1], hi[2], hi[3], lo[0], lo[1], lo[2], lo[3]};
     }
-#else
-        frag[((b * 2 + n0) * 2 + 0) * 64 + l] = f16x8{hi[0], hi[1], hi[2], hi[3], hi[0], hi[1], hi[2], hi[3]};
-        frag[((b * 2 + n0) * 2 + 1) * 64 + l] = f16x8{lo[0], lo[1], lo[2], lo[3], lo[0], lo[1], lo[2], lo[3]};
-    }
-    if (tid < 64) {
-        const int r = tid & 15, q = tid >> 4;
-        f16x8 s;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) s[e] = (4 * q + (e & 3) == r) ? (_Float16)1.0f : (_Float16)0.0f;
-        reinterpret_cast<f16x8*>(img + off_sel)[tid] = s;
-    }
-#endif
     for (int i = tid; i < 16 * 32; i += 256) img[off_w1 + (i >> 5) * 36 + (i & 31)] = A.W1[i];      // deep1 W^T [16][32]
     if (tid < 16) {
         img[off_b1 + tid] = A.b1[tid];
@@ -113,15 +79,6 @@ static __global__ __launch_bounds__(256) void k_v2j1_pack_image(const V2Args A, 
 // of global -> LDS -> registers at scoring time -- half of a wave's LDS reads in the scoring stage.  8.10 instead of 7.65 us,
 // 10.3 instead of 9.2 us with HBM-resident tables: sixteen waves per CU pulling the same 12 KB through the texture path queue
 // in front of the row gathers, and 110 VGPRs leave four waves per SIMD where 71 leave seven.)
-#ifdef SPRK_DF_XP
-// (timeline build, scripts/r04: every wave stamps the 100 MHz clock at entry, with its ids staged, with its gathers requested, behind
-// the barrier, after phase A, with its rows landed, at exit -- SPRK_V2J1_TS_FILE at sprk_destroy)
-#define V2J1_TS_WAVES 8192
-static __device__ unsigned long long g_v2j1_ts[V2J1_TS_WAVES * 8];
-#define V2J1_STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); if (lane == 0 && tk < V2J1_TS_WAVES) g_v2j1_ts[tk * 8 + (k)] = t_; } while (0)
-#else
-#define V2J1_STAMP(k) do { } while (0)
-#endif
 // HOIST ([r4]; chosen at finalize for tables larger than the Infinity Cache): the big fields' weight fragments and the selection
 // fragment -- 13 of the 26 KB a wave reads from LDS, none of it needing an id -- are read in FRONT of the gathers.  With rows coming
 // from HBM the texture path backs up longer and the LDS sits idle meanwhile: 8.9 -> 8.68 us; with cache-resident tables the same
@@ -158,7 +115,6 @@ __global__ __launch_bounds__(V2J1_WAVES_OF(HOIST, G_BIG) * 64, 4) void k_deepfm_
     const float* small_s = smem + LD::total_pad;                       // small fields' rows, then Wf
     float* stage = smem + LD::total_pad + A.small_floats + wave * 256; // this wave's ids / numerics slot
     const bool fast = work && !(A.flags & 1) && tk * 16 + 16 <= B;     // aligned, full task: one 16-byte load per lane
-    V2J1_STAMP(0);
     // (tried, no gain: s_setprio 3 from here to the last gather request -- 6.82 us either way, HBM-resident 8.7-9.0 against 8.7-8.8: profiles/r05/experiments/r05_12)
 
     // ---- the task's ids + numerics first, then the image pieces (they land inside the ids' latency) ----
@@ -171,13 +127,9 @@ __global__ __launch_bounds__(V2J1_WAVES_OF(HOIST, G_BIG) * 64, 4) void k_deepfm_
         raw = ld4(src + 4 * (j < n4 ? j : 0));
     }
 #pragma unroll 1
-    for (int c = wave; c < LD::total_pad / 256; c += WAVES)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(image + c * 256 + lane * 4),
-                                         (__attribute__((address_space(3))) void*)(smem + c * 256), 16, 0, 0);
+    for (int c = wave; c < LD::total_pad / 256; c += WAVES) lds_dma16(image + c * 256 + lane * 4, smem + c * 256);
 #pragma unroll 1
-    for (int c = wave; c < A.small_floats / 256; c += WAVES)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(A.small + c * 256 + lane * 4),
-                                         (__attribute__((address_space(3))) void*)(smem + LD::total_pad + c * 256), 16, 0, 0);
+    for (int c = wave; c < A.small_floats / 256; c += WAVES) lds_dma16(A.small + c * 256 + lane * 4, smem + LD::total_pad + c * 256);
 
     // ---- [r4] the workgroup meets HERE, with its ids and its DMA pieces in, BEFORE the rows are requested.  Round 3 met after the
     // requests ("every row of the batch is requested as soon as its ids are in -- before the barrier"), and the stamped timeline of
@@ -189,7 +141,6 @@ __global__ __launch_bounds__(V2J1_WAVES_OF(HOIST, G_BIG) * 64, 4) void k_deepfm_
     __builtin_amdgcn_s_barrier();
     if (!work) return;
     f16x8 wa[G_BIG][H0C], wb[G_BIG][H0C], hSel;
-#if V2J1_DEDUP
     // one 16-byte read per (field, n-block): {hi4 | lo4}; the MFMA's A operand {h, h} is the same four halfs twice -- two register
     // copies (expand_frags) instead of a second kilobyte out of LDS.  The selection fragment is a constant of the lane: 1.0 at
     // k = r - 4q.
@@ -215,17 +166,6 @@ __global__ __launch_bounds__(V2J1_WAVES_OF(HOIST, G_BIG) * 64, 4) void k_deepfm_
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         hSel = __builtin_bit_cast(f16x8, u32x4{lo01, lo23, lo01, lo23});
     };
-#else
-    auto read_frags = [&]() {
-        const f16x8* frag = reinterpret_cast<const f16x8*>(smem + LD::off_frag) + lane;
-#pragma unroll
-        for (int b = 0; b < G_BIG; ++b)
-#pragma unroll
-            for (int n0 = 0; n0 < H0C; ++n0) { wa[b][n0] = frag[((b * 2 + n0) * 2 + 0) * 64]; wb[b][n0] = frag[((b * 2 + n0) * 2 + 1) * 64]; }
-        hSel = reinterpret_cast<const f16x8*>(smem + LD::off_sel)[lane];
-    };
-    auto expand_frags = [&]() {};
-#endif
     if constexpr (HOIST) {
         read_frags();
         expand_frags();                                               // (with its LDS wait: measured equal to round 4's two-reads form, 8.61 against 8.58-8.60 us, r05_01)
@@ -249,7 +189,6 @@ __global__ __launch_bounds__(V2J1_WAVES_OF(HOIST, G_BIG) * 64, 4) void k_deepfm_
         } else {
             stage_task_slow(stage, ids, dense, A.F, A.ND, tk, B, lane);
         }
-        V2J1_STAMP(1);
         const int* sid_row = reinterpret_cast<const int*>(stage) + r * A.F;   // (one wave: LDS operations complete in issue order)
         unsigned sid[G_BIG];
 #pragma unroll
@@ -281,9 +220,7 @@ __global__ __launch_bounds__(V2J1_WAVES_OF(HOIST, G_BIG) * 64, 4) void k_deepfm_
             if (G_BIG > 2) sx = q == 2 ? s2 : sx;
             w1a = *reinterpret_cast<const float*>(tb + (sx + 4u * KP));
         }
-        V2J1_STAMP(2);
     }
-    V2J1_STAMP(3);
 
     // ---- scoring, phase A: everything that does NOT need the rows -- every LDS read of the stage (fragments, small fields'
     //      rows, W1, the small vectors: 26 KB per wave) and the numerics' MFMAs -- is issued HERE, while the rows are still
@@ -330,10 +267,9 @@ __global__ __launch_bounds__(V2J1_WAVES_OF(HOIST, G_BIG) * 64, 4) void k_deepfm_
     //  With HBM-resident tables (HOIST) the early wait is KEPT: measured 8.58-8.70 us with it, 8.65-8.87 without (r05_01, r05_02) -- there the
     //  rows are what everything waits for, and six f32 MFMAs issued in front of that wait hold up the VALU the SIMD's other waves need
     //  to get THEIR gathers out.)
-    constexpr bool ZZ_LATE = V2J1_ZZ_LATE && !HOIST;
     const float zz_num = __builtin_fmaf(rfn8b, xn1, rfn8a * xn0);
     float zz = 0.f;
-    if constexpr (!ZZ_LATE) {
+    if constexpr (HOIST) {
         zz = ((q < G_BIG) ? w1a : 0.f) + zz_num;
         zz += (q == 3) ? ssc : 0.f;
     }
@@ -347,14 +283,6 @@ __global__ __launch_bounds__(V2J1_WAVES_OF(HOIST, G_BIG) * 64, 4) void k_deepfm_
     f32x4 s = sp + pn;
     // ---- phase B: the rows (the compiler's s_waitcnt vmcnt lands at their first use, below this fence) ----
     __builtin_amdgcn_sched_barrier(0);
-#ifdef SPRK_DF_XP
-    if (s[0] + hA[0][0] == 123.456f) V2J1_STAMP(7);       // (phase A's results exist)
-    V2J1_STAMP(4);
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    V2J1_STAMP(5);
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     {
         f32x4 aFa[H0C], aFb[H0C], aS = zero;
 #pragma unroll
@@ -388,7 +316,7 @@ __global__ __launch_bounds__(V2J1_WAVES_OF(HOIST, G_BIG) * 64, 4) void k_deepfm_
         }
         z += dot4f(rhd, relu4_fast(e + o));
     }
-    if constexpr (ZZ_LATE) {
+    if constexpr (!HOIST) {
         zz = ((q < G_BIG) ? w1a : 0.f) + zz_num;
         zz += (q == 3) ? ssc : 0.f;
     }
@@ -400,5 +328,4 @@ __global__ __launch_bounds__(V2J1_WAVES_OF(HOIST, G_BIG) * 64, 4) void k_deepfm_
     const int m = tk * 16 + r;
     if (q == 0 && m < B) out[m] = score;
     if (__ballot(bad) != 0 && lane == 0) atomicOr(err, 1);
-    V2J1_STAMP(6);
 }

@@ -65,8 +65,7 @@ __global__ __launch_bounds__(DNF_WAVES * 64, 4) void k_dien_fused(const DienRun 
 #pragma unroll 1
     for (int c = wave; c < C0 + C1; c += DNF_WAVES) {
         const float* src = c < C0 ? A.image + c * 256 : tail_image + (c - C0) * 256;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + lane * 4),
-                                         (__attribute__((address_space(3))) void*)(smem + c * 256), 16, 0, 0);
+        lds_dma16(src + lane * 4, smem + c * 256);
     }
     __syncthreads();
 

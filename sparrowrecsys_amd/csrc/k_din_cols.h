@@ -116,9 +116,7 @@ __global__ __launch_bounds__(DC_WAVES * 64, 4) void k_din_attn_cols(const DinCol
 
     // ---- the coefficient tables (18 KB, built at finalize) by LDS-DMA: 1-KB pieces, wave w takes w, w + 8, ... ----
 #pragma unroll 1
-    for (int c = wave; c < 2 * ROWS * AS / 256; c += DC_WAVES)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(A.coef + c * 256 + lane * 4),
-                                         (__attribute__((address_space(3))) void*)(smem + c * 256), 16, 0, 0);
+    for (int c = wave; c < 2 * ROWS * AS / 256; c += DC_WAVES) lds_dma16(A.coef + c * 256 + lane * 4, smem + c * 256);
 
     // ---- this wave's (task, time slice) ----
     const int ntpb = (B + 15) >> 4;

@@ -48,9 +48,6 @@
 
 #define DF_WAVES 8
 #define DF_MB 16
-#ifndef DF_LATE_IMAGE
-#define DF_LATE_IMAGE 1                   // [r5] one batch per launch: the tail's image (88 KB per workgroup) and the raw tail rows are requested BEHIND the first
-#endif                                    // trip of the slot loop, not in front of it (below)
 struct DinFusedRun {
     // ---- activation unit + pooling (as DinColsRun) ----
     int T, F, hist_col, cand_col, Dp, vocab;
@@ -151,16 +148,8 @@ static __global__ __launch_bounds__(256) void k_din_fused_pack(const float* __re
 typedef _Float16 df_h2 __attribute__((ext_vector_type(2)));
 typedef float df_f2 __attribute__((ext_vector_type(2)));
 
-// XP: ablation bits for scripts/r04 experiments (only instantiated under -DSPRK_DF_XP): 1 no MFMAs, 2 no product split, 4 no h32,
-// 8 no PReLU dot, 16 no reduce / sigmoid, 32 no pooling, 64 no row loads in the loop; TAIL: 128 no folded-row gathers, 256 no fc1, 512 no
-// fc0 MFMAs (numerics + pooled) -- results are garbage, the time is the point
-template <int N> struct DfInt { static constexpr int value = N; };
-#ifdef SPRK_DF_XP
-// XP & 1024: a timeline -- every wave stamps the constant 100 MHz clock at kernel entry, loop entry, loop exit, after fc0, after fc1, exit
-#define DF_TS_WAVES 4096
-static __device__ unsigned long long g_df_ts[DF_TS_WAVES * 8];
-#endif
-template <int KC, bool MB, bool TAIL, bool ATT = false, int XP = 0>
+template <int N> struct DfInt { static constexpr int value = N; };   // (a compile-time count handed to the slot loop's waits)
+template <int KC, bool MB, bool TAIL, bool ATT = false>
 __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRun A, const int* __restrict__ ids, const float* __restrict__ dense,
                                                               float* __restrict__ out, float* __restrict__ att, int B, int* __restrict__ err,
                                                               const typename DinFusedArg<MB>::type Mm) {
@@ -188,8 +177,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
     float* park0 = smem + DF_COEF_FLOATS + img_floats + DF_WAVES * 16 * A.idp;
     float* park_s = smem + DF_COEF_FLOATS + img_floats + DF_WAVES * 16 * A.idp + wave * PSL * 64 * EL;
 
-    unsigned long long ts_entry = 0;
-    if constexpr ((XP & 1024) != 0) ts_entry = __builtin_amdgcn_s_memrealtime();
     // ---- this wave's (task, time slice) ----
     const int ntpb = (B + 15) >> 4;
     int nb_batches = 1;
@@ -201,14 +188,10 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
     // epilogue (matrix pipe, LDS) run under the other waves' slot loops (the fabric).  One wave per task (ts = 1).
     if constexpr (MB) {
 #pragma unroll 1
-        for (int c = wave; c < DF_COEF_FLOATS / 256; c += DF_WAVES)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(A.coef + c * 256 + lane * 4),
-                                             (__attribute__((address_space(3))) void*)(smem + c * 256), 16, 0, 0);
+        for (int c = wave; c < DF_COEF_FLOATS / 256; c += DF_WAVES) lds_dma16(A.coef + c * 256 + lane * 4, smem + c * 256);
         if constexpr (TAIL) {
 #pragma unroll 1
-            for (int c = wave; c < IM::dma_floats / 256; c += DF_WAVES)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(A.image + c * 256 + lane * 4),
-                                                 (__attribute__((address_space(3))) void*)(img_s + c * 256), 16, 0, 0);
+            for (int c = wave; c < IM::dma_floats / 256; c += DF_WAVES) lds_dma16(A.image + c * 256 + lane * 4, img_s + c * 256);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
@@ -243,14 +226,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
     const int m = tl * 16 + r;
     const int mc = min(m, B - 1);
     const bool tail_wave = TAIL && work && slice == 0;    // wave-uniform
-    auto stamp = [&](int k) {
-#ifdef SPRK_DF_XP
-        if constexpr ((XP & 1024) != 0) {
-            const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-            if (lane == 0 && gw < DF_TS_WAVES) { g_df_ts[gw * 8 + k] = t; if (k == 1) g_df_ts[gw * 8] = ts_entry; }
-        }
-#endif
-    };
 
     // ================= prologue: TWO round trips (ids; then every row and table the first trip needs), the tail's image behind them =========
     // Everything of the second round trip is a HIDDEN load (asm, like the slot loop's): hipcc's own waits sit in front of the first
@@ -278,8 +253,7 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
 #pragma unroll 1
             for (int c = 0; c * 256 < nint; ++c)
                 if (c * 256 + lane * 4 < nint)             // (16 F ints: a multiple of four)
-                    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + c * 256 + lane * 4),
-                                                     (__attribute__((address_space(3))) void*)(ids_s + c * 256), 16, 0, 0);
+                    lds_dma16(src + c * 256 + lane * 4, ids_s + c * 256);
         } else {
             for (int i = lane; i < nint; i += 64) {
                 const int s = i / A.F, col = i - s * A.F;
@@ -288,7 +262,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the ids are in LDS (one wave: its own LDS operations complete in issue order)
-    stamp(3);
     // ---- round trip two: the candidate's row (for h * c) and vc row (the accumulators' start), the A fragments (the same eight for
     // every slot), TAIL: the UNF columns' raw split rows (128 bytes per id: lane (r,q) takes hi / lo halfs 8q .. 8q+7 of sample r's
     // row, the B operand of fc0's blocks for that column -- sixteen registers through the slot loop, but random rows that miss every
@@ -315,8 +288,7 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
             // (the eight A fragments are the same 8 KB for every wave: ONE copy per workgroup through LDS -- wave w stages fragment w
             // in the parking region, which nothing else touches before the workgroup's second meeting -- instead of 64 KB per CU
             // through the texture path in front of the first rows)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(A.frag + wave * 256 + lane * 4),
-                                             (__attribute__((address_space(3))) void*)(park0 + wave * 256), 16, 0, 0);
+            lds_dma16(A.frag + wave * 256 + lane * 4, park0 + wave * 256);
         } else if constexpr (!MB) {
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb)
@@ -397,18 +369,18 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         else
             asm volatile("global_load_dwordx4 %0, %1, %2" : "=&v"(rw[0]) : "v"(voff), "s"(tbase));
     };
-    // [r5] LATE: round 4's prologue ended with "the second round trip moves 27 KB per wave at the moment every wave of the chip does the
-    // same" (3.9 us in the stamped timeline) -- 11 KB of it this wave's share of the tail's image, wanted 25 us later.  Now the image's
+    // [r5] LATE (one batch per launch, with a tail): the tail's image (88 KB per workgroup) and the raw tail rows are requested BEHIND the
+    // first trip of the slot loop, not in front of it.  Round 4's prologue ended with "the second round trip moves 27 KB per wave at the moment
+    // every wave of the chip does the same" (3.9 us in the stamped timeline) -- 11 KB of it this wave's share of the image, wanted 25 us later.  Now the image's
     // pieces and the raw tail rows go out AFTER the first trip and land under the second; the coefficient pieces go out in FRONT of the first
     // row sets so that one vmcnt says "everything but the rows".
-    constexpr bool LATE = TAIL && !MB && (DF_LATE_IMAGE != 0);
+    constexpr bool LATE = TAIL && !MB;
     constexpr int NCW = (DF_COEF_FLOATS / 256 + DF_WAVES - 1) / DF_WAVES;
     auto coef_dma = [&]() {
 #pragma unroll
         for (int i = 0; i < NCW; ++i) {
             const int c = min(wave + DF_WAVES * i, DF_COEF_FLOATS / 256 - 1);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(A.coef + c * 256 + lane * 4),
-                                             (__attribute__((address_space(3))) void*)(smem + c * 256), 16, 0, 0);
+            lds_dma16(A.coef + c * 256 + lane * 4, smem + c * 256);
         }
     };
     if constexpr (LATE) coef_dma();
@@ -423,13 +395,11 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
 #pragma unroll
         for (int i = 0; i < NPW; ++i) {
             const int c = wave + DF_WAVES * i;
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(A.image + c * 256 + lane * 4),
-                                             (__attribute__((address_space(3))) void*)(img_s + c * 256), 16, 0, 0);
+            lds_dma16(A.image + c * 256 + lane * 4, img_s + c * 256);
         }
         unf_load();
     };
-    if constexpr (TAIL && !MB && !LATE) image_dma();
-    constexpr int NW0 = LATE ? 4 * KC : NPW + NU;             // younger operations at the wait below: the four row sets, or the image's pieces + raw rows
+    constexpr int NW0 = LATE ? 4 * KC : 0;                    // younger operations at the wait below: LATE: the four row sets
     // everything but the image pieces (and the raw rows behind them) has landed: this wave's coefficient pieces, the second round trip,
     // the first four row sets
     // (volatile statements keep their order: the empty ones tie the remaining registers to the wait in front of them)
@@ -441,7 +411,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
     if constexpr (KC == 2) asm volatile("" : "+v"(cp[KC - 1]));
     if constexpr (TAIL) asm volatile("" : "+v"(xna), "+v"(xnb));          // (tied to the wait above: the oldest loads of the task)
     if constexpr (UNFK && MB) asm volatile("" : "+v"(er[0]), "+v"(er[UNFK ? 1 : 0]), "+v"(er[UNFK ? 2 : 0]), "+v"(er[UNFK ? 3 : 0]));
-    stamp(7);
     if constexpr (AWL) {
         __builtin_amdgcn_s_barrier();                     // coefficient tables and the A fragments staged by every wave
 #pragma unroll
@@ -497,7 +466,7 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
                 tb2_front |= g0 + g < A.n_cols && !ok && id != -1;
                 const float* frow = tab + (size_t)(ok ? id : 0) * IM::N0 + 4 * q;
 #pragma unroll
-                for (int nb = 0; nb < N0C; ++nb) f[g][nb] = (ok && !(XP & 128)) ? ld4(frow + nb * 16) : zero;
+                for (int nb = 0; nb < N0C; ++nb) f[g][nb] = ok ? ld4(frow + nb * 16) : zero;
             }
         };
         fold_load(0);                                          // (requested first, under the matrix work below)
@@ -505,7 +474,7 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         // fc0's bias rides in numeric slot b0_slot against a constant 1 (else it is added here)
 #pragma unroll
         for (int nb = 0; nb < N0C; ++nb) z0[nb] = zero;
-        if constexpr (!(XP & 512)) {
+        {
             // slot n_num carries 1.0 against fc0's bias (b0_slot); slots beyond duplicate a finite value that only ever meets zero weights
             const float xa1 = q == A.b0_slot ? 1.0f : xna;
             const float xb1 = q + 4 == A.b0_slot ? 1.0f : xnb;
@@ -552,7 +521,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         }
     };
     if constexpr (!MB && !AWL) __builtin_amdgcn_s_barrier();      // coefficient tables staged by every wave
-    stamp(1);
 
     // ---- slot loop ----
     float pacc[EL];
@@ -597,7 +565,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
     // PReLU(alpha[t][n]) -> Dense(1) (DIN.py:150-151) as ca u + cb |u| summed over this lane's eight units; the coefficient rows are
     // wave-uniform LDS addresses (broadcast)
     auto prelu_dot = [&](int t, const f32x4 (&uu)[2]) -> float {
-        if constexpr (XP & 8) return uu[0][0] + uu[1][1];
         const int tc = min(t, ROWS - 1);
         float sa = 0.f, sb = 0.f;
 #pragma unroll
@@ -621,17 +588,14 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
             unpack_halfs<KC>(rw, bh, bl);
             f32x4 acc[2] = {acc_init[0], acc_init[1]};
             // W12 . (hi + lo): independent of the product below -- the matrix pipe works while the VALU forms h * c
-            if constexpr (!(XP & 1)) {
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) acc[nb] = mfma_f16(aW[nb][0], bh, acc[nb]);
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) acc[nb] = mfma_f16(aW[nb][0], bl, acc[nb]);
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) acc[nb] = mfma_f16(aW[nb][1], bh, acc[nb]);
-            }
             // h * c * sP, split: packed f16 arithmetic on the halfs (header)
             f16xe qh = bh, ql = bl;
-            if constexpr (!(XP & 2)) {
 #pragma unroll
             for (int j = 0; j < NP; ++j) {
                 const df_h2 hh = {bh[2 * j], bh[2 * j + 1]}, hl = {bl[2 * j], bl[2 * j + 1]};
@@ -642,18 +606,12 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
                 qh[2 * j] = ph[0]; qh[2 * j + 1] = ph[1];
                 ql[2 * j] = pl[0]; ql[2 * j + 1] = pl[1];
             }
-            }
-            if constexpr (!(XP & 1)) {
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) acc[nb] = mfma_f16(aW[nb][2], qh, acc[nb]);
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) acc[nb] = mfma_f16(aW[nb][2], ql, acc[nb]);
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) acc[nb] = mfma_f16(aW[nb][3], qh, acc[nb]);
-            } else {
-                acc[0][0] += (float)qh[0] + (float)ql[1];
-                acc[1][1] += (float)bh[0] + (float)bl[1];
-            }
             if (x == 0) lga = prelu_dot(t0 + step, acc);
             else { ub[0] = acc[0]; ub[1] = acc[1]; }
             // h back to f32 (sH units): one v_fma_mix_f32 per element (inputs: loaded registers; outputs go to compiler-visible VALU)
@@ -661,8 +619,7 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
             for (int e = 0; e < EL; ++e) {
                 const float hp = KC == 2 ? rw[0][e >> 1] : rw[0][e >> 1];
                 const float lp = KC == 2 ? rw[KC - 1][e >> 1] : rw[0][2 + (e >> 1)];
-                if constexpr (XP & 4) h32[x][e] = hp;
-                else h32[x][e] = (e & 1) ? halfs_sum<true>(one, hp, lp) : halfs_sum<false>(one, hp, lp);
+                h32[x][e] = (e & 1) ? halfs_sum<true>(one, hp, lp) : halfs_sum<false>(one, hp, lp);
             }
         }
     };
@@ -674,7 +631,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         lg[0] = lga;
         lg[1] = prelu_dot(t0 + step + 1, ub);
         float wa, wb;
-        if constexpr (XP & 16) { wa = lg[0]; wb = lg[1]; } else {
         float xx = lg[0], yy = lg[1];
         asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(xx), "+v"(yy));   // xx = [a0 b0 a2 b2], yy = [a1 b1 a3 b3]
         xx += yy;                                                                     // [a01 b01 a23 b23]
@@ -685,7 +641,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         wb = wa;
         // (s_nop 1 also covers the one wait state a transcendental's result needs before a non-transcendental VALU reads it)
         asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(wa), "+v"(wb));   // wa = [a a a a], wb = [b b b b]
-        }
         wa = step < nsteps ? wa : 0.f;                                                // (a pair past the end: the pipeline's last, unused, round)
         wb = step + 1 < nsteps ? wb : 0.f;                                            // the padding slot of an odd history
         if constexpr (ATT) {
@@ -694,16 +649,10 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
                 if (step + 1 < nsteps) att[(size_t)m * T + t0 + step + 1] = wb;
             }
         }
-        if constexpr (XP & 32) {
-            pacc[0] += wa + wb;
-#pragma unroll
-            for (int e = 0; e < EL; ++e) pacc[1] += h32[0][e] + h32[1][e];
-        } else {
 #pragma unroll
         for (int e = 0; e < EL; ++e) pacc[e] = fmaf(wa, h32[0][e], pacc[e]);
 #pragma unroll
         for (int e = 0; e < EL; ++e) pacc[e] = fmaf(wb, h32[1][e], pacc[e]);
-        }
     };
     {
         // at most N younger SETS outstanding => this set has landed (vmcnt retires in order; a set is KC loads).  No "memory" clobber:
@@ -722,7 +671,7 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         };
         // One trip = two pairs = four slots, straight-line: the four register sets of the ring keep their roles statically (an if / else
         // on a round's parity made hipcc merge the two arms' tails and COPY row registers with loads still in flight; a loop per quarter
-        // inside a loop over the quarters made it copy them at the inner loop's entry -- scripts/r04/check_din_fused_isa.py walks the ISA
+        // inside a loop over the quarters made it copy them at the inner loop's entry -- scripts/isa/check_din_fused_isa.py walks the ISA
         // of every instantiation for exactly that).  A quarter is a multiple of four slots, so a trip never straddles one; a history
         // that ends inside a trip leaves slots whose weights are forced to zero.  Rows are requested two pairs ahead, as soon as the
         // matrix half has consumed the set.  (A software-pipelined form -- the matrix half of pair i + 1 in one block with the VALU half
@@ -732,28 +681,24 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         float h0[2][EL];
         int jq = 0, qnext = A.ql;                             // current local quarter, the first slot of the next one (wave-uniform)
         auto trip = [&](int step, auto x) {
-            if constexpr (!(XP & 64)) { wait3(rowA, x); wait2(rowB, x); }
+            wait3(rowA, x); wait2(rowB, x);
             mfma_part(step, rowA, rowB, l0, u0, h0);
-            if constexpr (!(XP & 64)) { load(step + 4, rowA); load(step + 5, rowB); }
+            load(step + 4, rowA); load(step + 5, rowB);
             finish(step, l0, u0, h0);
-            if constexpr (!(XP & 64)) { wait3(rowC, x); wait2(rowD, x); }
+            wait3(rowC, x); wait2(rowD, x);
             mfma_part(step + 2, rowC, rowD, l0, u0, h0);
-            if constexpr (!(XP & 64)) { load(step + 6, rowC); load(step + 7, rowD); }
+            load(step + 6, rowC); load(step + 7, rowD);
             finish(step + 2, l0, u0, h0);
         };
         int step = 0;
-        if constexpr (TAIL && !MB) {
+        if constexpr (LATE) {
             // the first trip runs under the image's DMA (its pieces are younger than the four row sets it waits for), by EVERY wave
             // (one without slots works on zero weights), then the wave's pieces have landed -- at most the four re-requested row
             // sets stay in flight -- and the workgroup meets once more: from here on the image is readable by all of it
-            if constexpr (LATE) {
-                trip(0, DfInt<0>{});
-                image_dma();                                      // (younger than the four row sets trip 0 re-requested)
-                if (4 < nsteps && 4 == qnext) { park(jq); ++jq; qnext += A.ql; }
-                trip(4, DfInt<NPW + NU>{});                       // (a wave with at most four slots: zero weights)
-            } else {
-                trip(0, DfInt<NPW + NU>{});
-            }
+            trip(0, DfInt<0>{});
+            image_dma();                                          // (younger than the four row sets trip 0 re-requested)
+            if (4 < nsteps && 4 == qnext) { park(jq); ++jq; qnext += A.ql; }
+            trip(4, DfInt<NPW + NU>{});                           // (a wave with at most four slots: zero weights)
             if constexpr (UNFK)
                 asm volatile("s_waitcnt vmcnt(%4)" : "+v"(er[0]), "+v"(er[UNFK ? 1 : 0]), "+v"(er[UNFK ? 2 : 0]), "+v"(er[UNFK ? 3 : 0]) : "n"(4 * KC));
             else
@@ -761,7 +706,7 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
 #pragma unroll
             for (int u = 0; u < (UNFK ? 2 : 0); ++u) { eh[u] = __builtin_bit_cast(din_f16x8, er[2 * u]); el[u] = __builtin_bit_cast(din_f16x8, er[2 * u + 1]); }
             __builtin_amdgcn_s_barrier();
-            step = LATE ? 8 : 4;
+            step = 8;
         }
         for (; step < nsteps; step += 4) {
             if (step == qnext) { park(jq); ++jq; qnext += A.ql; }
@@ -775,7 +720,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         else
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(rowA[0]), "+v"(rowB[0]), "+v"(rowC[0]), "+v"(rowD[0]));
     }
-    stamp(2);
     float res[EL];
     if (nq == 1) {
 #pragma unroll
@@ -831,7 +775,7 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         bool tb2 = tb2_front;
         // the pooled history on the f16 pipe, from the registers it was accumulated in (k = EL q + e): per-sample dynamic scale
         // (DIN's attention weights are not normalised), hi / lo split, three products per 16 outputs
-        if constexpr (XP & 512) { z0[0][0] += res[0]; } else {
+        {
             float xp[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) xp[e] = e < EL ? res[e < EL ? e : 0] * A.inv_h_scale : 0.f;
@@ -855,8 +799,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
             }
         }
         if (__ballot(tb2) != 0 && lane == 0) atomicOr(err, 1);
-        if constexpr ((XP & 1024) != 0) { if (z0[0][0] + z0[7][3] == 123.456f) stamp(7); }   // (the stamp below waits for fc0's results)
-        stamp(4);
         // PReLU(alpha0) (DIN.py:164)
 #pragma unroll
         for (int nb = 0; nb < N0C; ++nb) {
@@ -883,7 +825,7 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
             for (int n1 = 0; n1 < N1C; ++n1) acc[n1] = zero;
             const float* wf = img_s + IM::off_w1 + lane * 4;                 // this lane's 16 bytes inside a 1-KB fragment (k_dyn_pack_w: lane order)
 #pragma unroll
-            for (int b = 0; b < ((XP & 256) ? 0 : N0C / 2); ++b) {
+            for (int b = 0; b < N0C / 2; ++b) {
                 din_f16x8 bh, bl;
                 dyn_split8(z0[2 * b], z0[2 * b + 1], scale, bh, bl);
 #pragma unroll
@@ -898,8 +840,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
 #pragma unroll
             for (int n1 = 0; n1 < N1C; ++n1) z1[n1] = acc[n1] * inv + ld4(img_s + IM::off_b1 + n1 * 16 + 4 * q);
         }
-        if constexpr ((XP & 1024) != 0) { if (z1[0][0] + z1[3][3] == 123.456f) stamp(7); }
-        stamp(5);
         // PReLU(alpha1) (DIN.py:166) -> Dense(1) -> sigmoid (DIN.py:167)
         float z = 0.f;
 #pragma unroll
@@ -915,7 +855,6 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
         }
         z = rows4_sum(z);
         if (q == 0 && m < B) out_b[m] = sigmoidf_acc(z + A.head_bias);
-        stamp(6);
     }
     if constexpr (!MB) break;
     }   // (tasks of this wave)

@@ -29,12 +29,7 @@
 #define MR_MAX_BIG 3
 #define MR_MAX_SMALL 8
 #define MR_STAGE 320                      // floats per wave: ids [16][F <= 12] + numerics [16][<= 8]
-#ifndef MR_RS
 #define MR_RS 132                         // floats between two LDS rows of a small column (128 + 4: see the header)
-#endif
-#ifndef MR_XP
-#define MR_XP 0                           // ablation builds (scripts/r05): 1 no small-column reads, 2 one weight fragment pair for the whole second layer,
-#endif                                    // 4 big rows not loaded, 8 no wide part, 16 no second-layer MFMAs, 128 big rows with a quad of lanes per row -- WRONG RESULTS, timing only
 
 struct MlpRowsRun {
     int F, ND, n_num;
@@ -150,17 +145,6 @@ __global__ __launch_bounds__(256) void k_mlp_rows_pack(const float* __restrict__
 //     together (pass 1: Ah Bh x 4, pass 2: Ah Bl x 4, pass 3: Al Bh x 4 -- the accumulation order per output is unchanged), and the next
 //     group's fragments are requested as soon as a pass has freed their registers;
 //   * b0 rides in the numerics' free eighth K slot (x = 1) when there are at most seven numerics: eight LDS reads + sixteen adds less.
-#ifdef SPRK_DF_XP
-// (timeline build, scripts/r06/34_mlp_rows_timeline.sh: every wave stamps the 100 MHz clock at entry, behind the meeting, with its first gather out, and per
-// trip with its rows summed, the next gather out, the first layer done, the second layer done, its scores stored -- SPRK_MR_TS_FILE at sprk_destroy)
-#define MR_TS_WAVES 2048
-#define MR_TS_SLOTS 32
-static __device__ unsigned long long g_mr_ts[MR_TS_WAVES * MR_TS_SLOTS];
-#define MR_STAMP(k) do { __builtin_amdgcn_sched_barrier(0); const unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); \
-    const int w_ = blockIdx.x * WAVES + wave; if (lane == 0 && w_ < MR_TS_WAVES && (k) < MR_TS_SLOTS) g_mr_ts[w_ * MR_TS_SLOTS + (k)] = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define MR_STAMP(k) do { } while (0)
-#endif
 // [r6] MB: several batches per launch (sprk_forward_many): the launch's tasks are n x ceil(B / 16), task t belongs to batch t / ntpb -- own ids,
 // numerics and score buffers each -- and the waves walk them exactly as they walk one batch's: the image is staged once, the ramp of a strict
 // launch (5 us of config 5's 39) is paid once per MR_MB batches.  Same instruction sequence per task: the same bits as batch by batch.
@@ -216,7 +200,6 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
     // live = false: the trip behind a wave's last task.  Its loads are issued all the same -- into the all-zero rows, one hot line per table --
     // so that the registers a gather writes are the SAME on every path into the next trip: with the gather inside `if (more tasks)` hipcc
     // kept two copies of the 80 registers and moved one into the other at the end of every trip (forty v_mov_b64, build/sparrow.s).
-    [[maybe_unused]] bool stamp_gather = false;                  // (timeline build: the FIRST gather stamps its stages, slots 27..30)
     auto gather = [&](int tk, const f32x4& ri, const f32x4& rd, bool live) {
         const Loc L = locate(tk);
         if (aligned && L.tl * 16 + 16 <= B) {
@@ -247,9 +230,6 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
             if (RT ? f < ns : f < NS) sidv[f] = idrow[A.s_col[f]];
         }
         if constexpr (WK != 0) { wid_a = idrow[A.wide_a]; wid_b = idrow[A.wide_b]; }
-#ifdef SPRK_DF_XP
-        if (stamp_gather) { asm volatile("" : "+v"(bid[0])); MR_STAMP(28); }
-#endif
         {
             const float* nrow = stage + 192 + r * A.ND;
             const int last = A.n_num - 1;
@@ -264,14 +244,9 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
             const unsigned sid = live ? min((unsigned)bid[b], (unsigned)A.big_vocab[b]) : (unsigned)A.big_vocab[b];      // -1 -> the zero row at index vocab
             // (one SGPR base + a 32-bit byte offset per lane: the set-up admits folded tables below 4 GiB)
             const char* row = reinterpret_cast<const char*>(A.big_tab[b]) + (sid * (unsigned)(N0 * 4) + 16u * q);
-            if (MR_XP & 128)              // (timing only: a quad of lanes on ONE row's 64 consecutive bytes -- the same lines per instruction, coalesced)
-                row = reinterpret_cast<const char*>(A.big_tab[b]) + ((unsigned)__shfl((int)sid, lane >> 2) * (unsigned)(N0 * 4) + 16u * (lane & 3));
 #pragma unroll
-            for (int nb = 0; nb < N0C; ++nb) g[b][nb] = (MR_XP & 4) ? f32x4{(float)sid, 0.f, 0.f, 0.f} : *reinterpret_cast<const f32x4*>(row + 64 * nb);
+            for (int nb = 0; nb < N0C; ++nb) g[b][nb] = *reinterpret_cast<const f32x4*>(row + 64 * nb);
         }
-#ifdef SPRK_DF_XP
-        if (stamp_gather) MR_STAMP(29);
-#endif
 #pragma unroll
         for (int f = 0; f < MR_MAX_SMALL; ++f) {
             if (RT ? f < ns : f < NS) {                           // (wave-uniform when RT)
@@ -281,11 +256,9 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
                 so[f] = (unsigned)id < (unsigned)A.s_vocab[f] ? t : A.zero_off * 4;
             }
         }
-        if constexpr (WK != 0 && !(MR_XP & 8)) {
+        if constexpr (WK != 0) {
             unsigned long long bkt;
-            if (MR_XP & 32) {
-                bkt = 0;
-            } else if (A.wide_magic != 0) {                           // wave-uniform
+            if (A.wide_magic != 0) {                           // wave-uniform
                 unsigned long long hh = 0xDECAFCAFFEULL;              // cross_bucket's chain (k_tile_forward.h), the modulo as a multiply
                 hh = fingerprint_cat64(hh, (uint64_t)(int64_t)wid_a);
                 hh = fingerprint_cat64(hh, (uint64_t)(int64_t)wid_b);
@@ -293,8 +266,6 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
             } else {
                 bkt = cross_bucket(wid_a, wid_b, (uint64_t)A.wide_buckets);
             }
-            if (MR_XP & 32) bkt = (unsigned long long)(((unsigned)wid_a * 2654435761u) ^ ((unsigned)wid_b * 40503u)) % (unsigned)A.wide_buckets;
-            if (MR_XP & 64) bkt = bkt & 1;
             bkt = live ? bkt : 0ull;
             if constexpr (WK == 1) {
 #pragma unroll
@@ -325,33 +296,16 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
     //  round 4's timeline showed for k_deepfm_v2_joint1's meeting.)
     f32x4 ri = zero, rd = zero;
     int tk = blockIdx.x * WAVES + wave;
-    MR_STAMP(0);
     if (ntasks > 0) ld_raw(clampt(tk), ri, rd);
 #pragma unroll 1
-    for (int c = wave; c < LD::total_pad / 256; c += WAVES)
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(image + c * 256 + lane * 4),
-            (__attribute__((address_space(3))) void*)(smem + c * 256), 16, 0, 0);
+    for (int c = wave; c < LD::total_pad / 256; c += WAVES) lds_dma16(image + c * 256 + lane * 4, smem + c * 256);
 #pragma unroll 1
-    for (int c = wave; c < A.small_floats / 256; c += WAVES)
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(A.small + c * 256 + lane * 4),
-            (__attribute__((address_space(3))) void*)(smem + LD::total_pad + c * 256), 16, 0, 0);
+    for (int c = wave; c < A.small_floats / 256; c += WAVES) lds_dma16(A.small + c * 256 + lane * 4, smem + LD::total_pad + c * 256);
     __builtin_amdgcn_s_waitcnt(0x0F70);                           // vmcnt(0): this wave's DMA pieces and ids have landed
     __builtin_amdgcn_s_barrier();
-    MR_STAMP(1);
     if (tk >= ntasks) return;                                     // (behind the barrier; a wave without a task flags nothing)
-    MR_STAMP(27);
-#ifdef SPRK_DF_XP
-    stamp_gather = true;
-#endif
     gather(tk, ri, rd, true);
-#ifdef SPRK_DF_XP
-    stamp_gather = false;
-#endif
-    MR_STAMP(30);
     ld_raw(clampt(tk + task_stride), ri, rd);
-    MR_STAMP(2);
     // numerics' A operands: rows (nb*16 + r) of W0[:, numerics]^T, columns q and q + 4, first used by the first task's MFMAs.  [r6] Requested
     // BEHIND the first gather, as four coalesced 16-byte loads per lane (the image holds them lane-major: k_mlp_rows_pack).  Rounds 5's sixteen
     // 4-byte loads per lane sat between the meeting and the gather -- "nobody waits for them there", but a wave issues in order, and the stamped
@@ -374,7 +328,6 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
             if (d < A.wide_dim) wwide[h] = ld4(A.wide_w + d);
         }
     }
-    [[maybe_unused]] int trip = 0;
     for (;; tk += task_stride) {
         // ---- the task's gathered rows -> first-layer accumulators (frees the register set for the next task) ----
         f32x4 z0[N0C];
@@ -399,10 +352,8 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
 #pragma unroll
         for (int nb = 0; nb < N0C; ++nb) asm volatile("" : "+v"(z0[nb]));
         __builtin_amdgcn_sched_barrier(0);
-        MR_STAMP(3 + 6 * trip);
         gather(clampt(tk + task_stride), ri, rd, more);
         ld_raw(clampt(tk + 2 * task_stride), ri, rd);
-        MR_STAMP(4 + 6 * trip);
         // ---- small columns from LDS (a lane's piece nb of a row: + 64 nb bytes, the instruction's offset field) ----
         if (!bias_in_k7) {
 #pragma unroll
@@ -410,7 +361,7 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
         }
 #pragma unroll
         for (int f = 0; f < MR_MAX_SMALL; ++f) {
-            if (!(MR_XP & 1) && (RT ? f < ns : f < NS)) {
+            if (RT ? f < ns : f < NS) {
                 const float* row = reinterpret_cast<const float*>(small_b + so_c[f]);
 #pragma unroll
                 for (int nb = 0; nb < N0C; ++nb) z0[nb] += ld4(row + 16 * nb);
@@ -424,10 +375,6 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
 #pragma unroll
         for (int nb = 0; nb < N0C; ++nb) z0[nb] = relu4_fast(z0[nb]);
         // ---- second layer: K = N0, B operand = h1 as it sits in the registers ----
-#ifdef SPRK_DF_XP
-        asm volatile("" : "+v"(z0[0]), "+v"(z0[N0C - 1]));
-        MR_STAMP(5 + 6 * trip);
-#endif
         f32x4 z1[N1C];
         if constexpr (DYN) {
             float mx = 0.f;
@@ -441,7 +388,6 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
             const float* wf = smem + LD::off_w1 + lane * 4;              // this lane's 16 bytes inside a 1-KB fragment (k_dyn_pack_w: lane order)
             constexpr int KB = N0C / 2, NG = N1C / 4;                    // K blocks of 32; groups of four output blocks
             auto frag = [&](int n1, int b, int part) {
-                if (MR_XP & 2) return __builtin_bit_cast(din_f16x8, ld4(wf + part * 256 + 0 * (n1 + b)));
                 return __builtin_bit_cast(din_f16x8, ld4(wf + ((n1 * KB + b) * 2 + part) * 256));
             };
             din_f16x8 ah[4], al[4];
@@ -456,11 +402,6 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
                     const int step = b * NG + gi + 1;                       // the group behind this one
                     const int nb_ = step / NG, ng_ = step - nb_ * NG;       // (compile-time after unrolling)
                     const bool more = step < KB * NG;
-                    if (MR_XP & 16) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) z1[4 * gi + j] = (b == 0 ? zero : z1[4 * gi + j]) + __builtin_bit_cast(f32x4, ah[j]) + __builtin_bit_cast(f32x4, al[j]) + __builtin_bit_cast(f32x4, bh) + __builtin_bit_cast(f32x4, bl);
-                        continue;
-                    }
 #pragma unroll
                     for (int j = 0; j < 4; ++j) z1[4 * gi + j] = mfma_f16(ah[j], bh, b == 0 ? zero : z1[4 * gi + j]);
 #pragma unroll
@@ -495,10 +436,6 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
                         z1[n1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[n1][st], z0[c][st], z1[n1], 0, 0, 0);
             }
         }
-#ifdef SPRK_DF_XP
-        asm volatile("" : "+v"(z1[0]), "+v"(z1[N1C - 1]));
-        MR_STAMP(6 + 6 * trip);
-#endif
         float z = zw;
 #pragma unroll
         for (int n1 = 0; n1 < N1C; ++n1) {
@@ -511,10 +448,6 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
         const Loc Ls = locate(tk);
         const int mm = Ls.tl * 16 + r;
         if (q == 0 && mm < B) Ls.out[mm] = sigmoidf_acc(z + A.head_bias);
-        MR_STAMP(7 + 6 * trip);
-#ifdef SPRK_DF_XP
-        ++trip;
-#endif
         if (!more) break;
     }
     if (badm != 0 && lane == 0) atomicOr(err, 1);

@@ -439,16 +439,10 @@ __device__ __forceinline__ void rows_chain_body(const RowsRun& A, const int* __r
         if (!ONE) ld_raw(clampt(tB), rawB);
     }
 #pragma unroll 1
-    for (int c = wave; c < LD::total_pad / 256; c += WAVES)
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)(image + c * 256 + lane * 4),
-            (__attribute__((address_space(3))) void*)(smem + c * 256), 16, 0, 0);
+    for (int c = wave; c < LD::total_pad / 256; c += WAVES) lds_dma16(image + c * 256 + lane * 4, smem + c * 256);
     if constexpr (NJF > 0) {
 #pragma unroll 1
-        for (int c = wave; c < A.small_floats / 256; c += WAVES)
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void*)(A.small + c * 256 + lane * 4),
-                (__attribute__((address_space(3))) void*)(smem + LD::total_pad + WAVES * LD::stage_floats + c * 256), 16, 0, 0);
+        for (int c = wave; c < A.small_floats / 256; c += WAVES) lds_dma16(A.small + c * 256 + lane * 4, smem + LD::total_pad + WAVES * LD::stage_floats + c * 256);
     }
     constexpr int NG = (UNF ? 2 : G_BIG * (KPC + H0C)) + (HASFM ? 1 : 0);   // VMEM loads per gather
     // s_waitcnt vmcnt(NG), lgkmcnt / expcnt untouched: vmcnt is a 6-bit field split over bits [3:0] and [15:14]

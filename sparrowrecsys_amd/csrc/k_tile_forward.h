@@ -74,6 +74,11 @@ __device__ __forceinline__ float sigmoidf_acc(float z) {
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+// LDS-DMA, one 1-KB piece: every lane's 16 bytes at g (the LANE's address) land at l + 16 lane (l: the piece, wave-uniform); no VGPRs, no ds_write.
+// N floats go as pieces c = wave, wave + WAVES, ... in a loop at the call site: the same loop inside a helper moved instructions in 185 kernels.
+__device__ __forceinline__ void lds_dma16(const void* g, void* l) {
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
+}
 
 __device__ __forceinline__ f32x4 mfma4(f32x4 a, f32x4 b, f32x4 c) {
     // four K-steps of v_mfma_f32_16x16x4_f32; lane (r = lane&15, q = lane>>4) feeds k = 4q+s at step s

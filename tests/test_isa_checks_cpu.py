@@ -1,6 +1,6 @@
 """k_din_fused hides its row loads from hipcc's waitcnt pass and owns them with hand-counted `s_waitcnt vmcnt(N)` statements
 (sparrowrecsys_amd/csrc/k_din_fused.h).  Whether that is CORRECT is a property of the generated ISA, not of the source: hipcc has
-twice copied registers with a load still in flight.  scripts/r04/check_din_fused_isa.py compiles the device
+twice copied registers with a load still in flight.  scripts/isa/check_din_fused_isa.py compiles the device
 code (no GPU needed) and walks the control-flow graph of every instantiation; this test runs it."""
 import os
 import shutil
@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.skipif(shutil.which("hipcc") is None and not os.path.exists("/opt/rocm/bin/hipcc"), reason="needs hipcc")
 def test_din_fused_hidden_loads_are_never_touched_in_flight():
     env = dict(os.environ, PATH=os.environ.get("PATH", "") + ":/opt/rocm/bin")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "r04", "check_din_fused_isa.py"), "--compile"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "isa", "check_din_fused_isa.py"), "--compile"],
                        capture_output=True, text=True, env=env, timeout=900)
     lines = [l for l in r.stdout.splitlines() if l.startswith("k_din_fused<")]
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
