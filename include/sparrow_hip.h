@@ -293,6 +293,32 @@ int sprk_emb_rank(const float* item_emb, const uint8_t* item_has, int32_t n_item
                   const float* query_emb, const uint8_t* query_has, int32_t n_queries, int32_t query_stride,
                   const int32_t* cand, int32_t C, double* scores, int32_t* order, void* stream);
 
+/* Embedding RECALL, exact, over the whole table: SimilarMovieProcess.retrievalCandidatesByEmbedding (SimilarMovieProcess.java:91-112) --
+ * score EVERY movie against the query embedding (calculateEmbSimilarScore :167-172, Embedding.java:33-47), sort, keep `size`.
+ * For every query u the result is exactly what sprk_emb_rank gives for cand[u] = 0, 1, .., n_items-1, cut to the first K:
+ *   items[u][k]  = the table row of the k-th entry;
+ *   scores[u][k] = its score, the same doubles bit for bit (-1.0 for a row with item_has == 0 or a query with query_has == 0, NaN for an
+ *                  all-zero vector).
+ * largest = 1: descending Double.compareTo order (NaN first, 0.0 before -0.0), equal scores by ascending row -- the ranker's order
+ *              (`comparingByValue(Comparator.reverseOrder())`, SimilarMovieProcess.java:135), i.e. the K MOST similar rows.
+ * largest = 0: ascending Double.compareTo order, equal scores again by ascending row.  This is what the Java literally does:
+ *              retrievalCandidatesByEmbedding sorts with `Map.Entry.comparingByValue()` and NO reverseOrder (:104), so the reference
+ *              returns the `size` LEAST similar movies.
+ * (score, row) is a total order: the answer is unique and does not depend on how the table is chunked or merged.  A query without an
+ * embedding gets rows 0 .. K-1 with score -1.0 in both directions.
+ * Limits: 1 <= K <= 1024 and K <= n_items; 1 <= D <= 1024, strides >= D; largest 0 or 1; item_emb, query_emb, scores, items not NULL;
+ * `workspace` (device memory, 8-byte aligned) of at least the bytes the workspace function below names for (n_items, n_queries, K), which
+ * is 0 -- and the pointer may be NULL -- when the table fits one chunk of 4096 rows.  Anything else returns SPRK_EINVAL BEFORE any device
+ * call (the message names the bytes needed).  n_queries == 0 does nothing.  Asynchronous on `stream`: no host synchronisation, no memory
+ * owned by the library; all index arithmetic in 64 bits.  All pointers are device memory, laid out as for sprk_emb_rank; scores and items
+ * are [n_queries][K].  SPRK_EMB_TOPK_CHUNK = a power of two in [64, 4096] shortens the chunk (tests), for both functions. */
+size_t sprk_emb_topk_workspace_bytes(int32_t n_items, int32_t n_queries, int32_t K);
+int sprk_emb_topk(const float* item_emb, const uint8_t* item_has, int32_t n_items, int32_t D, int32_t item_stride,
+                  const float* query_emb, const uint8_t* query_has, int32_t n_queries, int32_t query_stride,
+                  int32_t K, int32_t largest,
+                  double* scores /* [n_queries][K] */, int32_t* items /* [n_queries][K] */,
+                  void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- host ingest (no GPU involved): the step before the path ----
  * Replaces `tf.data.experimental.make_csv_dataset(..., na_value="0", ignore_errors=True)` of the reference's
  * get_dataset (DeepFM.py:14-22) plus the feature-column id resolution (DeepFM.py:54-76) for a CSV text held in

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "sprk_check_ids", "sprk_destroy", "sprk_embedding_gather", "sprk_cross_hash", "sprk_last_error",
     "sprk_pack_csv", "sprk_pack_csv_mt", "sprk_pack_csv_device", "sprk_csv_last_path",
     "sprk_pack_columns", "sprk_pack_columns_device", "sprk_pack_last_route", "sprk_set_many_streams", "sprk_set_many_batches", "sprk_emb_rank",
+    "sprk_emb_topk", "sprk_emb_topk_workspace_bytes",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -240,8 +241,11 @@ def load_library():
         lib.sprk_pack_columns_device.argtypes = [C.POINTER(PackCol), i32, C.POINTER(PackCol), i32, C.c_char_p, sz, i32, i32, vp, vp, vp]
         lib.sprk_pack_last_route.argtypes = []
         lib.sprk_emb_rank.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp]
+        lib.sprk_emb_topk.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+        lib.sprk_emb_topk_workspace_bytes.argtypes = [i32, i32, i32]
+        lib.sprk_emb_topk_workspace_bytes.restype = sz
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

@@ -34,6 +34,7 @@
 #include "k_chain_v1.h"
 #include "k_mlp_rows.h"
 #include "k_emb_rank.h"
+#include "k_emb_topk.h"           // exact top-K recall over the whole table (reuses er_key)
 #include "k_dien_seq.h"
 #include "k_dien_mfma.h"
 #include "k_dien_fused.h"

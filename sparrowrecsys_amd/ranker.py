@@ -5,6 +5,10 @@ movies and the ranked candidate list -- `RecForYouProcess.ranker(user, candidate
 
 Host side only parses the reference's embedding files and moves arrays; the scores and the ranking come from
 `sprk_emb_rank` (HIP, include/sparrow_hip.h).  There is no CPU fallback: without the library / a GPU it raises.
+
+Recall -- the step in front of the ranker -- is `EmbRanker.topk` / `retrieve` / `similar_movies`: the K table rows closest to a
+query over the WHOLE table, exact (`sprk_emb_topk`; `SimilarMovieProcess.retrievalCandidatesByEmbedding`,
+SimilarMovieProcess.java:91-112).
 """
 from __future__ import annotations
 
@@ -59,6 +63,8 @@ class EmbRanker:
             else:
                 table[i] = v
         self.row_of = {m: i for i, m in enumerate(ids)}
+        self.ids = np.array(ids, dtype=np.int64)                         # movie id of every table row
+        self._topk_ws = None
         self.table = torch.from_numpy(table).to(self.device)
         self.has = torch.from_numpy(has).to(self.device)
 
@@ -98,3 +104,81 @@ class EmbRanker:
         _, order = self.score_many(q, cand, qh)
         ids = list(candidate_ids)
         return [ids[i] for i in order[0].cpu().tolist()]
+
+    # ---- recall: the K closest rows of the whole table (sprk_emb_topk) ----
+    TOPK_WORKSPACE_BYTES = 256 << 20
+
+    def topk(self, query_emb, k: int, query_has=None, largest: bool = True) -> Tuple[object, object]:
+        """The first `k` entries of every query's ranking of the WHOLE table: query_emb [Q, D] float32 (numpy or a device
+        tensor) -> (scores [Q, k] float64, rows [Q, k] int32) as device tensors -- what `score_many(q, arange(N))` gives, cut to
+        k, for a table of any size.  largest=False: ascending order (the least similar rows first).  1 <= k <= min(1024, N),
+        else SparrowHipError; a wrong shape is a ValueError.
+
+        A table above one chunk of 4 096 rows merges through a workspace this object owns (a cached device tensor that
+        grows as needed): 12 bytes x about min(k, 4096) x N / 4096 per query for the first level, 5/4 of it with the next.  The
+        queries are walked in tiles of as many as fit TOPK_WORKSPACE_BYTES (256 MiB), one at the least, so the workspace is
+        max(256 MiB, one query's need) at the most -- 101 MB per query for 27 M rows at k = 1024."""
+        torch = self._torch
+        q = torch.as_tensor(query_emb, dtype=torch.float32).to(self.device).contiguous()
+        if q.dim() != 2 or q.shape[1] != self.D:
+            raise ValueError("query_emb must be [Q, %d]" % self.D)
+        Q, N = q.shape[0], self.table.shape[0]
+        qh = None if query_has is None else torch.as_tensor(query_has, dtype=torch.uint8).to(self.device).contiguous()
+        if qh is not None and tuple(qh.shape) != (Q,):
+            raise ValueError("query_has must be [Q]")
+        k = int(k)
+        kk = k if 1 <= k <= 1024 else 1                                  # (a k the library refuses: it says so below, nothing is written)
+        scores = torch.empty((Q, kk), dtype=torch.float64, device=self.device)
+        rows = torch.empty((Q, kk), dtype=torch.int32, device=self.device)
+        per_query = int(self._lib.sprk_emb_topk_workspace_bytes(N, 1, k))
+        tile = max(1, Q if per_query == 0 else min(Q, self.TOPK_WORKSPACE_BYTES // per_query))
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        for u0 in range(0, Q, tile):
+            n = min(tile, Q - u0)
+            need = int(self._lib.sprk_emb_topk_workspace_bytes(N, n, k))
+            if need and (self._topk_ws is None or self._topk_ws.numel() < need):
+                self._topk_ws = None                                     # free before growing
+                self._topk_ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            L.check(self._lib.sprk_emb_topk(
+                C.c_void_p(self.table.data_ptr()), C.c_void_p(self.has.data_ptr()), C.c_int32(N), C.c_int32(self.D), C.c_int32(self.D),
+                C.c_void_p(q.data_ptr() + u0 * self.D * 4), C.c_void_p(qh.data_ptr() + u0 if qh is not None else None),
+                C.c_int32(n), C.c_int32(self.D), C.c_int32(k), C.c_int32(1 if largest else 0),
+                C.c_void_p(scores.data_ptr() + u0 * kk * 8), C.c_void_p(rows.data_ptr() + u0 * kk * 4),
+                C.c_void_p(self._topk_ws.data_ptr() if need else None), C.c_size_t(self._topk_ws.numel() if need else 0),
+                C.c_void_p(stream)))
+        return scores, rows
+
+    def retrieve(self, query: Optional[np.ndarray], size: int, reference_order: bool = False) -> Optional[list]:
+        """retrievalCandidatesByEmbedding (SimilarMovieProcess.java:91-112): the `size` movie ids closest to `query` over the
+        whole table, best first; None when the query is None or has the wrong length (Java: null for a movie without an
+        embedding); `size` is clamped to the table as `subList(0, Math.min(candidates.size(), size))` does.
+        reference_order=True is the Java to the letter: it sorts ASCENDING (`comparingByValue()` without reverseOrder, :104)
+        and so returns the `size` LEAST similar movies.  The reference scores "the first 10 000 movies by rating" (:96): which
+        movies are candidates is the caller's choice of the dict this EmbRanker is built from."""
+        n = _retrieve_size(query, size, self.D, len(self.ids))
+        if n is None:
+            return None
+        if n == 0:
+            return []
+        _, rows = self.topk(np.asarray(query, dtype=np.float32)[None, :], n, largest=not reference_order)
+        return self.ids[rows[0].cpu().numpy()].tolist()
+
+    def similar_movies(self, movie_id: int, size: int) -> list:
+        """The `size` movies closest to `movie_id`'s own embedding, the movie itself left out (asked for as size + 1 rows and
+        dropped on the host, as `candidateMap.remove(movie.getMovieId())` does in the reference's candidate generators); [] for
+        a movie the table does not know (getRecList, SimilarMovieProcess.java:22-24)."""
+        row = self.row_of.get(int(movie_id))
+        if row is None or int(size) <= 0:
+            return []
+        n = min(int(size) + 1, len(self.ids))
+        _, rows = self.topk(self.table[row:row + 1], n, query_has=self.has[row:row + 1])
+        out = [int(m) for m in self.ids[rows[0].cpu().numpy()].tolist() if m != int(movie_id)]
+        return out[:int(size)]
+
+
+def _retrieve_size(query, size: int, D: int, n_rows: int) -> Optional[int]:
+    """How many rows `retrieve` asks for: None = the Java's null (no query embedding / wrong length), else size clamped to
+    [0, table rows]."""
+    if query is None or np.asarray(query).shape != (D,):
+        return None
+    return max(0, min(int(size), n_rows))
