@@ -268,8 +268,10 @@ def _embedding_mlp_body(features, w, dtype, movie_buckets, user_buckets):
     blocks["userId_embedding"] = embedding_lookup(                       # EmbeddingMLP.py:58-60
         w["emb/userId"].astype(dtype), identity_ids(int_feature(features, "userId"), user_buckets, "userId"))
     x, _ = dense_features(blocks)                                        # EmbeddingMLP.py:73
-    x = relu(dense(x, w["dense0/kernel"], w["dense0/bias"], dtype))      # EmbeddingMLP.py:74
-    x = relu(dense(x, w["dense1/kernel"], w["dense1/bias"], dtype))      # EmbeddingMLP.py:75
+    i = 0                                                                # EmbeddingMLP.py:74-75 (two layers there; as deep as w is)
+    while "dense%d/kernel" % i in w:
+        x = relu(dense(x, w["dense%d/kernel" % i], w["dense%d/bias" % i], dtype))
+        i += 1
     return x
 
 
@@ -541,8 +543,10 @@ def din_forward(features: Dict, w: Dict[str, np.ndarray], dtype=np.float32,
                                                            vocab_ids(features["movieGenre1"]))
     context, _ = dense_features(ctx_blocks)
     x = np.concatenate([profile, pooled, c, context], axis=1)               # DIN.py:161-162
-    x = prelu(dense(x, w["fc0/kernel"], w["fc0/bias"], dtype), w["fc0_prelu/alpha"])   # DIN.py:163-164
-    x = prelu(dense(x, w["fc1/kernel"], w["fc1/bias"], dtype), w["fc1_prelu/alpha"])   # DIN.py:165-166
+    i = 0                                                                   # DIN.py:163-166 (two layers there; as deep as w is)
+    while "fc%d/kernel" % i in w:
+        x = prelu(dense(x, w["fc%d/kernel" % i], w["fc%d/bias" % i], dtype), w["fc%d_prelu/alpha" % i])
+        i += 1
     out = sigmoid(dense(x, w["head/kernel"], w["head/bias"], dtype)).astype(np.float32)  # DIN.py:167
     if return_parts:
         return out, {"pooled": pooled, "att": wgt[..., 0]}
