@@ -6,8 +6,11 @@
 // precedence over the tail they are built on.
 static void choose_route(sprk_engine* h) {
     const int din = h->plan.din.enabled;
-    if (din == 2) h->stage = h->dien_frag ? Stage::DienSeqMfma : Stage::DienSeq;
-    else if (din == 1) h->stage = h->din_fused_attn ? Stage::DinFusedAttn : (h->din_cols_kc ? Stage::DinCols : Stage::DinPool);
+    if (din == 2) {
+        const bool d10 = h->plan.din.emb_dim == 10;
+        h->stage = h->dien_frag ? Stage::DienSeqMfma : Stage::DienSeq;
+        h->dien_seq_kernel = h->dien_frag ? (d10 ? &k_dien_seq_mfma<10, 32> : &k_dien_seq_mfma<16, 32>) : (d10 ? &k_dien_seq<10, 32> : &k_dien_seq<16, 32>);
+    } else if (din == 1) h->stage = h->din_fused_attn ? Stage::DinFusedAttn : (h->din_cols_kc ? Stage::DinCols : Stage::DinPool);
     else h->stage = Stage::None;
     if (din == 1 && h->din_fused) h->route = Route::DinFused;
     else if (din == 2 && h->dien_fused) h->route = Route::DienFused;
@@ -167,7 +170,7 @@ int sprk_finalize(sprk_handle h) {
     if (p.din.enabled == 2 && (rc = setup_dien_stage(h, dp->din))) return rc;
     if (p.din.enabled == 1 && (rc = setup_din_stage(h, dp->din))) return rc;
     // 4. the forward routes: the interpreter (every plan's fall-back), then each fused form only where the ones before it refused
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_tile_forward), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->tile_lds_bytes));
+    SPRK_TRY(set_max_lds(k_tile_forward, h->tile_lds_bytes));
     h->tile_grid_cap = lds_grid_cap(h, h->tile_lds_bytes);
     if (!h->tune.force_interpreter && match_v2_chain(h) && (rc = setup_v2_fold(h))) return rc;
     const bool v2_on = h->v2j_variant >= 0;

@@ -14,17 +14,10 @@ static int launch_din_cols(sprk_handle h, const int32_t* ids, float* pooled, flo
     const int EL = 4 * h->din_cols_kc;
     const size_t lds = ((size_t)2 * 64 * 36 + (size_t)DC_WAVES * 16 * c.idp + (size_t)DC_WAVES * 2 * 64 * EL) * sizeof(float);
     const long long grid = (ntasks * c.ts + DC_WAVES - 1) / DC_WAVES;
-    if (many) {
-        if (h->din_cols_kc == 2)
-            hipLaunchKernelGGL((k_din_attn_cols<2, true>), dim3((unsigned)grid), dim3(DC_WAVES * 64), lds, st, c, (const int*)nullptr, (float*)nullptr, (float*)nullptr, B, h->dev_err, *many);
-        else
-            hipLaunchKernelGGL((k_din_attn_cols<1, true>), dim3((unsigned)grid), dim3(DC_WAVES * 64), lds, st, c, (const int*)nullptr, (float*)nullptr, (float*)nullptr, B, h->dev_err, *many);
-    } else {
-        if (h->din_cols_kc == 2)
-            hipLaunchKernelGGL((k_din_attn_cols<2, false>), dim3((unsigned)grid), dim3(DC_WAVES * 64), lds, st, c, ids, pooled, att, B, h->dev_err, DinColsOne{});
-        else
-            hipLaunchKernelGGL((k_din_attn_cols<1, false>), dim3((unsigned)grid), dim3(DC_WAVES * 64), lds, st, c, ids, pooled, att, B, h->dev_err, DinColsOne{});
-    }
+    if (many)
+        hipLaunchKernelGGL(h->din_cols_kernels.many, dim3((unsigned)grid), dim3(DC_WAVES * 64), lds, st, c, nullptr, nullptr, nullptr, B, h->dev_err, *many);
+    else
+        hipLaunchKernelGGL(h->din_cols_kernels.one, dim3((unsigned)grid), dim3(DC_WAVES * 64), lds, st, c, ids, pooled, att, B, h->dev_err, DinColsOne{});
     HIP_TRY(hipGetLastError());
     return SPRK_OK;
 }
@@ -46,20 +39,12 @@ static int launch_din_fused(sprk_handle h, const int32_t* ids, const float* dens
                         (size_t)DF_WAVES * (tail ? 1 : 2) * 64 * 4 * kc) * sizeof(float);   // (k_din_fused.h: PREG)
     long long grid = (ntasks * c.ts + DF_WAVES - 1) / DF_WAVES;
     if (many && grid > h->num_cus) grid = h->num_cus;         // persistent: the waves walk the tasks
-#define DF_LAUNCH(KC, MB, TAIL, marg)                                                                                                   \
-    hipLaunchKernelGGL((k_din_fused<KC, MB, TAIL>), dim3((unsigned)grid), dim3(DF_WAVES * 64), lds, st, c, MB ? (const int*)nullptr : ids, \
-                       MB ? (const float*)nullptr : dense, MB ? (float*)nullptr : out, MB ? (float*)nullptr : att, B, h->dev_err, marg)
-    if (many) {
-        if (kc == 2) { if (tail) DF_LAUNCH(2, true, true, *many); else DF_LAUNCH(2, true, false, *many); }
-        else { if (tail) DF_LAUNCH(1, true, true, *many); else DF_LAUNCH(1, true, false, *many); }
-    } else {
-        if (att && !tail) {                                     // attention weights out (tests, inspection): its own instantiation
-            if (kc == 2) hipLaunchKernelGGL((k_din_fused<2, false, false, true>), dim3((unsigned)grid), dim3(DF_WAVES * 64), lds, st, c, ids, dense, out, att, B, h->dev_err, DinFusedOne{});
-            else hipLaunchKernelGGL((k_din_fused<1, false, false, true>), dim3((unsigned)grid), dim3(DF_WAVES * 64), lds, st, c, ids, dense, out, att, B, h->dev_err, DinFusedOne{});
-        } else if (kc == 2) { if (tail) DF_LAUNCH(2, false, true, DinFusedOne{}); else DF_LAUNCH(2, false, false, DinFusedOne{}); }
-        else { if (tail) DF_LAUNCH(1, false, true, DinFusedOne{}); else DF_LAUNCH(1, false, false, DinFusedOne{}); }
-    }
-#undef DF_LAUNCH
+    const DinFusedKernels& k = h->din_fused_kernels[tail];
+    if (many)
+        hipLaunchKernelGGL(k.many, dim3((unsigned)grid), dim3(DF_WAVES * 64), lds, st, c, nullptr, nullptr, nullptr, nullptr, B, h->dev_err, *many);
+    else                                                        // (attention weights out -- tests, inspection -- is its own instantiation)
+        hipLaunchKernelGGL((att && !tail) ? h->din_fused_att_kernel : k.one, dim3((unsigned)grid), dim3(DF_WAVES * 64), lds, st, c, ids, dense, out, att, B, h->dev_err,
+                           DinFusedOne{});
     HIP_TRY(hipGetLastError());
     return SPRK_OK;
 }
@@ -82,31 +67,19 @@ static int launch_din(sprk_handle h, const int32_t* ids, float* pooled, float* a
         const int ntiles = (B + 15) / 16;
         int gridm = (ntiles + DM_WAVES - 1) / DM_WAVES;
         if (gridm > h->num_cus * 8) gridm = h->num_cus * 8;
-        const size_t lds10 = DienFrag<10, 32>::total_pad * sizeof(float), lds16 = DienFrag<16, 32>::total_pad * sizeof(float);
-        if (h->plan.din.emb_dim == 10)
-            hipLaunchKernelGGL((k_dien_seq_mfma<10, 32>), dim3(gridm), dim3(DM_WAVES * 64), lds10, st, run, ids, pooled, B, h->dev_err);
-        else
-            hipLaunchKernelGGL((k_dien_seq_mfma<16, 32>), dim3(gridm), dim3(DM_WAVES * 64), lds16, st, run, ids, pooled, B, h->dev_err);
+        hipLaunchKernelGGL(h->dien_seq_kernel, dim3(gridm), dim3(DM_WAVES * 64), h->dien_frag_floats * sizeof(float), st, run, ids, pooled, B, h->dev_err);
         break;
     }
     case Stage::DienSeq: {                                        // one lane per sample
         int grid = (B + 63) / 64;
         if (grid > h->num_cus * 8) grid = h->num_cus * 8;
-        if (h->plan.din.emb_dim == 10)
-            hipLaunchKernelGGL((k_dien_seq<10, 32>), dim3(grid), dim3(64), 0, st, h->dien_run, ids, pooled, B, h->dev_err);
-        else
-            hipLaunchKernelGGL((k_dien_seq<16, 32>), dim3(grid), dim3(64), 0, st, h->dien_run, ids, pooled, B, h->dev_err);
+        hipLaunchKernelGGL(h->dien_seq_kernel, dim3(grid), dim3(64), 0, st, h->dien_run, ids, pooled, B, h->dev_err);
         break;
     }
     case Stage::None: return fail(SPRK_EKIND, "handle has no DIN stage");
     }
     HIP_TRY(hipGetLastError());
     return SPRK_OK;
-}
-
-// waves per workgroup of the k_din_tail form finalize chose (16 with raw embedding rows for emb_dim <= 16)
-static int din_tail_waves(sprk_handle h) {
-    return h->din_tail_run.e_unscale != 0.f ? dt_waves_unf(kDinTailVariants[h->din_tail_variant].kpc) : DT_WAVES;
 }
 
 int sprk_din_pool(sprk_handle h, const int32_t* ids, float* pooled, float* att, int32_t B, void* stream) {
@@ -152,12 +125,8 @@ int sprk_forward(sprk_handle h, const int32_t* ids, const float* dense, float* o
             const int ntiles = (B + 15) / 16;
             int grid = (ntiles + DNF_WAVES - 1) / DNF_WAVES;
             if (grid > h->num_cus) grid = h->num_cus;              // one 16-wave workgroup per CU (both weight images in its LDS)
-            if (h->plan.din.emb_dim == 10)
-                hipLaunchKernelGGL((k_dien_fused<10, 32, 8, 4>), dim3(grid), dim3(DNF_WAVES * 64), h->dien_fused_lds, st, run, h->din_tail_run, ids, dense, out, B,
-                                   h->dev_err, (const float*)h->din_tail_image, (float*)workspace);
-            else
-                hipLaunchKernelGGL((k_dien_fused<16, 32, 8, 4>), dim3(grid), dim3(DNF_WAVES * 64), h->dien_fused_lds, st, run, h->din_tail_run, ids, dense, out, B,
-                                   h->dev_err, (const float*)h->din_tail_image, (float*)workspace);
+            hipLaunchKernelGGL(h->dien_fused_kernel, dim3(grid), dim3(DNF_WAVES * 64), h->dien_fused_lds, st, run, h->din_tail_run, ids, dense, out, B, h->dev_err,
+                               h->din_tail_image, (float*)workspace);
             HIP_TRY(hipGetLastError());
             return SPRK_OK;
         }
@@ -171,39 +140,32 @@ int sprk_forward(sprk_handle h, const int32_t* ids, const float* dense, float* o
         const V2JVariant& jv = kV2JVariants[h->v2j_variant];
         V2JRun jr = h->v2j_run;
         jr.flags = unaligned;
-        const V2J1Variant* one = nullptr;                          // one strict launch of one batch: one task per wave, four waves per SIMD (k_chain_v2j1.h)
-        if (h->v2j1_image && ntasks <= V2J1_MAX_TASKS)
-            for (const V2J1Variant& v : kV2J1Variants)
-                if (!one && v.g_big == jv.g_big && v.njf == jv.njf) one = &v;
-        if (one) {
-            (h->v2j1_hoist ? one->launch_h : one->launch)(jr, ids, dense, out, B, h->dev_err, h->v2j1_image, (ntasks + h->v2j1_waves - 1) / h->v2j1_waves,
-                                                          h->v2j1_lds_bytes, st);
+        if (h->v2j1_kernel && ntasks <= V2J1_MAX_TASKS) {          // one strict launch of one batch: one task per wave, four waves per SIMD (k_chain_v2j1.h)
+            hipLaunchKernelGGL(h->v2j1_kernel, dim3((ntasks + h->v2j1_waves - 1) / h->v2j1_waves), dim3(h->v2j1_waves * 64), h->v2j1_lds_bytes, st, jr, ids,
+                               dense, out, B, h->dev_err, h->v2j1_image);
             break;
         }
         int grid = (ntasks + V2_WAVES - 1) / V2_WAVES;
         if (grid > h->v2_grid_cap) grid = h->v2_grid_cap;
-        jv.launch(jr, ids, dense, out, B, h->dev_err, h->v2_image, grid, h->v2j_lds_bytes, st);
+        hipLaunchKernelGGL(jv.fn, dim3(grid), dim3(V2_WAVES * 64), h->v2j_lds_bytes, st, jr, ids, dense, out, B, h->dev_err, h->v2_image);
         break;
     }
     case Route::Rows: {
+        const RowsVariant& rv = kRowsVariants[h->rows_variant];
         int grid = (ntasks + RC_WAVES - 1) / RC_WAVES;
-        if (grid > h->num_cus) grid = h->num_cus;                  // one 8-wave workgroup per CU (2 waves per SIMD)
+        const bool one = ntasks <= V2J1_MAX_TASKS;                 // k_rows_chain1: one task per wave, no cap (the joint1 family's threshold serves here too)
+        if (!one && grid > h->num_cus) grid = h->num_cus;          // looped: one 8-wave workgroup per CU (2 waves per SIMD)
         RowsRun rr = h->rows_run;
         rr.flags = unaligned;
-        if (h->rows_one && ntasks <= V2J1_MAX_TASKS)
-            kRowsVariants[h->rows_variant].launch_one(rr, ids, dense, out, B, h->dev_err, h->rows_image, (ntasks + RC_WAVES - 1) / RC_WAVES,
-                                                      h->rows_lds_bytes, st);
-        else
-            kRowsVariants[h->rows_variant].launch(rr, ids, dense, out, B, h->dev_err, h->rows_image, grid, h->rows_lds_bytes, st);
+        hipLaunchKernelGGL(one ? rv.fn_one : rv.fn, dim3(grid), dim3(RC_WAVES * 64), h->rows_lds_bytes, st, rr, ids, dense, out, B, h->dev_err, h->rows_image);
         break;
     }
     case Route::Pairs: {
         int grid = (ntasks + V1_WAVES - 1) / V1_WAVES;
-        if (grid > h->num_cus) grid = h->num_cus;                  // one 8-wave workgroup per CU (2 waves per SIMD; 3 per SIMD measured slower at B = 65 536)
-        if (h->v1_one && ntasks <= V1_ONE_MAX_TASKS)
-            kV1Variants[h->v1_variant].launch_one(h->v1_run, ids, dense, out, B, h->dev_err, (ntasks + V1_WAVES - 1) / V1_WAVES, st);
-        else
-            kV1Variants[h->v1_variant].launch(h->v1_run, ids, dense, out, B, h->dev_err, grid, st);
+        const bool one = h->v1_one_kernel && ntasks <= V1_ONE_MAX_TASKS;
+        if (!one && grid > h->num_cus) grid = h->num_cus;          // looped: one 8-wave workgroup per CU (2 waves per SIMD; 3 per SIMD measured slower at B = 65 536)
+        hipLaunchKernelGGL(one ? h->v1_one_kernel : h->v1_kernel, dim3(grid), dim3(V1_WAVES * 64), kV1Variants[h->v1_variant].lds_bytes, st, h->v1_run, ids,
+                           dense, out, B, h->dev_err);
         break;
     }
     case Route::MlpRows: {
@@ -215,10 +177,11 @@ int sprk_forward(sprk_handle h, const int32_t* ids, const float* dense, float* o
         break;
     }
     case Route::DinTail: {
-        const int tw = din_tail_waves(h);
+        const int tw = h->din_tail_waves;
         int grid = (ntasks + tw - 1) / tw;
         if (grid > h->num_cus) grid = h->num_cus;                  // one workgroup per CU (8 waves, or 16 with raw embedding rows)
-        kDinTailVariants[h->din_tail_variant].launch(h->din_tail_run, ids, dense, aux, out, B, h->dev_err, h->din_tail_image, grid, st);
+        hipLaunchKernelGGL(h->din_tail_kernel, dim3(grid), dim3(tw * 64), kDinTailVariants[h->din_tail_variant].lds_bytes, st, h->din_tail_run, ids, dense, aux,
+                           out, B, h->dev_err, h->din_tail_image, DinTailMany{});
         break;
     }
     default: {                                                     // Route::Tile (the one-launch DIN / DIEN routes returned above)
@@ -299,7 +262,7 @@ static int forward_many_impl(sprk_handle h, int32_t n_batches, const int32_t* co
             m.ntpb = ntpb;
             long long grid = ((long long)m.n * ntpb + V2_WAVES - 1) / V2_WAVES;
             if (grid > h->v2_grid_cap) grid = h->v2_grid_cap;
-            jv.launch_many(jr, m, B, h->dev_err, h->v2_image, (int)grid, h->v2j_lds_bytes, st);
+            hipLaunchKernelGGL(jv.fn_many, dim3((int)grid), dim3(V2_WAVES * 64), h->v2j_lds_bytes, st, jr, m, B, h->dev_err, h->v2_image);
             return SPRK_OK;
         });
     }
@@ -314,7 +277,7 @@ static int forward_many_impl(sprk_handle h, int32_t n_batches, const int32_t* co
             m.ntpb = ntpb;
             long long grid = ((long long)m.n * ntpb + RC_WAVES - 1) / RC_WAVES;
             if (grid > h->num_cus) grid = h->num_cus;
-            rv.launch_many(rr, m, B, h->dev_err, h->rows_image, (int)grid, h->rows_lds_bytes, st);
+            hipLaunchKernelGGL(rv.fn_many, dim3((int)grid), dim3(RC_WAVES * 64), h->rows_lds_bytes, st, rr, m, B, h->dev_err, h->rows_image);
             return SPRK_OK;
         });
     }
@@ -333,12 +296,12 @@ static int forward_many_impl(sprk_handle h, int32_t n_batches, const int32_t* co
     }
     // the pairwise-dot DeepFM kernel: up to V1_MB batches per launch
     if (grouped && dense && h->route == Route::Pairs && every_batch(n_batches, present)) {
-        const V1Variant& vv = kV1Variants[h->v1_variant];
+        const size_t lds = kV1Variants[h->v1_variant].lds_bytes;
         return launch_groups<V1Many>(n_batches, many_batches < V1_MB ? many_batches : V1_MB, ids, dense, out, [&](V1Many& m, int) {
             m.ntpb = ntpb;
             long long grid = ((long long)m.n * ntpb + V1_WAVES - 1) / V1_WAVES;
             if (grid > h->num_cus) grid = h->num_cus;
-            vv.launch_many(h->v1_run, m, B, h->dev_err, (int)grid, st);
+            hipLaunchKernelGGL(h->v1_many_kernel, dim3((int)grid), dim3(V1_WAVES * 64), lds, st, h->v1_run, m, B, h->dev_err);
             return SPRK_OK;
         });
     }
@@ -364,8 +327,8 @@ static int forward_many_impl(sprk_handle h, int32_t n_batches, const int32_t* co
             int SG = S >= 2 ? S : 1;                                   // streams the groups alternate over
             while (SG > 1 && (size_t)SG * per * ws_need > workspace_bytes) --SG;
             if (SG >= 2) SPRK_TRY(fork_helpers(h, SG, st));
-            const DinTailVariant& tv = kDinTailVariants[h->din_tail_variant];
-            const int tw = din_tail_waves(h);
+            const size_t tail_lds = kDinTailVariants[h->din_tail_variant].lds_bytes;
+            const int tw = h->din_tail_waves;
             int g = 0;
             for (int32_t i0 = 0; i0 < n_batches; i0 += per, ++g) {
                 const int n = n_batches - i0 < per ? n_batches - i0 : per;
@@ -391,7 +354,8 @@ static int forward_many_impl(sprk_handle h, int32_t n_batches, const int32_t* co
                 }
                 long long tg = ((long long)n * ntpb + tw - 1) / tw;
                 if (tg > h->num_cus) tg = h->num_cus;
-                tv.launch_many(h->din_tail_run, tm, B, h->dev_err, h->din_tail_image, (int)tg, sg);
+                hipLaunchKernelGGL(h->din_tail_many_kernel, dim3((int)tg), dim3(tw * 64), tail_lds, sg, h->din_tail_run, nullptr, nullptr, nullptr, nullptr, B,
+                                   h->dev_err, h->din_tail_image, tm);
                 HIP_TRY(hipGetLastError());
             }
             if (SG >= 2) SPRK_TRY(join_helpers(h, SG, st));

@@ -57,14 +57,14 @@ __device__ __forceinline__ void dyn_split2(float x0, float x1, float scale, dyn_
     asm("v_fma_mix_f32 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(r1) : "v"(x1), "v"(scale), "v"(hb));
     lo = __builtin_convertvector(dyn_f2{r0, r1}, dyn_h2);
 }
-__device__ __forceinline__ void dyn_split8(f32x4 x, f32x4 y, float scale, din_f16x8& hi, din_f16x8& lo) {
+__device__ __forceinline__ void dyn_split8(f32x4 x, f32x4 y, float scale, f16x8& hi, f16x8& lo) {
     dyn_h2 h[4], l[4];
     dyn_split2(x[0], x[1], scale, h[0], l[0]);
     dyn_split2(x[2], x[3], scale, h[1], l[1]);
     dyn_split2(y[0], y[1], scale, h[2], l[2]);
     dyn_split2(y[2], y[3], scale, h[3], l[3]);
-    hi = din_f16x8{h[0][0], h[0][1], h[1][0], h[1][1], h[2][0], h[2][1], h[3][0], h[3][1]};
-    lo = din_f16x8{l[0][0], l[0][1], l[1][0], l[1][1], l[2][0], l[2][1], l[3][0], l[3][1]};
+    hi = f16x8{h[0][0], h[0][1], h[1][0], h[1][1], h[2][0], h[2][1], h[3][0], h[3][1]};
+    lo = f16x8{l[0][0], l[0][1], l[1][0], l[1][1], l[2][0], l[2][1], l[3][0], l[3][1]};
 }
 
 // scale = 2^(14 - exponent(m)) (1 for m == 0), inv = 1 / (scale * w_scale); m >= 0 finite

@@ -7,6 +7,8 @@
 namespace sprk_dev {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 inline thread_local std::string g_err;
 

@@ -8,6 +8,32 @@
 enum class Route { Tile, V2Joint, Rows, Pairs, MlpRows, DinTail, DinFused, DienFused };
 enum class Stage { None, DinPool, DinCols, DinFusedAttn, DienSeq, DienSeqMfma };
 
+// One function-pointer type per kernel signature.  A set-up picks the instantiation ONCE (its variant table or selector), sets the LDS limit on
+// exactly that pointer (set_max_lds) and the launch paths hand it to hipLaunchKernelGGL: the compiler checks every launch against the kernel.
+typedef void (*V2JKernel)(const V2JRun, const int*, const float*, float*, int, int*, const float*);        // k_deepfm_v2_joint, k_deepfm_v2_joint1
+typedef void (*V2JManyKernel)(const V2JRun, const V2JMany, int, int*, const float*);
+typedef void (*RowsKernel)(const RowsRun, const int*, const float*, float*, int, int*, const float*);       // k_rows_chain, k_rows_chain1
+typedef void (*RowsManyKernel)(const RowsRun, const RowsMany, int, int*, const float*);
+typedef void (*V1Kernel)(const V1Run, const int*, const float*, float*, int, int*);                         // k_deepfm_pairs, k_deepfm_pairs1
+typedef void (*V1ManyKernel)(const V1Run, const V1Many, int, int*);
+typedef void (*MlpRowsKernel)(const MlpRowsRun, const int*, const float*, float*, int, int*, const float*);
+typedef void (*MlpRowsManyKernel)(const MlpRowsRun, const MlpRowsMany, int, int*, const float*);
+typedef void (*DinTailKernel)(const DinTailRun, const int*, const float*, const float*, float*, int, int*, const float*, const DinTailMany);
+typedef void (*DinColsKernel)(const DinColsRun, const int*, float*, float*, int, int*, const DinColsOne);
+typedef void (*DinColsManyKernel)(const DinColsRun, const int*, float*, float*, int, int*, const DinColsMany);
+typedef void (*DinFusedKernel)(const DinFusedRun, const int*, const float*, float*, float*, int, int*, const DinFusedOne);
+typedef void (*DinFusedManyKernel)(const DinFusedRun, const int*, const float*, float*, float*, int, int*, const DinFusedMany);
+typedef void (*DienSeqKernel)(const DienRun, const int*, float*, int, int*);                                // k_dien_seq, k_dien_seq_mfma
+typedef void (*DienFusedKernel)(const DienRun, const DinTailRun, const int*, const float*, float*, int, int*, const float*, float*);
+// k_din_attn_cols<KC, MB> and k_din_fused<KC, MB, TAIL> for one KC: one batch, several batches
+struct DinColsKernels { DinColsKernel one; DinColsManyKernel many; };
+struct DinFusedKernels { DinFusedKernel one; DinFusedManyKernel many; };
+// the one owner of a kernel's dynamic-LDS limit
+template <class Kernel> static int set_max_lds(Kernel k, size_t bytes) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return SPRK_OK;
+}
+
 struct sprk_engine {
     sprk_plan plan;
     std::vector<void*> slot_ptr;
@@ -33,20 +59,24 @@ struct sprk_engine {
     hipEvent_t many_fork = nullptr, many_join[4] = {nullptr, nullptr, nullptr, nullptr};
     // register-chained pairwise-dot DeepFM (k_deepfm_pairs); -1 = not set up
     int v1_variant = -1;
-    bool v1_one = false;                  // one-batch launches use k_deepfm_pairs1 (one task per wave, four waves per SIMD)
+    V1Kernel v1_kernel = nullptr;         // the split-f16 or the f32 form, as the set-up's fragments came out
+    V1Kernel v1_one_kernel = nullptr;     // one-batch launches use k_deepfm_pairs1 (one task per wave, four waves per SIMD); nullptr: the looped kernel
+    V1ManyKernel v1_many_kernel = nullptr;
     V1Run v1_run;
     // DenseFeatures -> Dense -> Dense -> Dense(1) graphs with every embedding column folded through the first layer, genre tables
     // in LDS (k_mlp_rows); -1 = not set up
     int mlp_rows_nbig = -1;
     MlpRowsRun mlp_rows_run;
-    void (*mlp_rows_kernel)(const MlpRowsRun, const int*, const float*, float*, int, int*, const float*) = nullptr;
-    void (*mlp_rows_many_kernel)(const MlpRowsRun, const MlpRowsMany, int, int*, const float*) = nullptr;   // [r6] several batches per launch (nullptr: batch by batch)
+    MlpRowsKernel mlp_rows_kernel = nullptr;
+    MlpRowsManyKernel mlp_rows_many_kernel = nullptr;   // [r6] several batches per launch (nullptr: batch by batch)
     float* mlp_rows_image = nullptr;
     float* mlp_rows_small = nullptr;
     size_t mlp_rows_lds = 0;
     // register-chained DIN tail (k_din_tail); -1 = not set up
     int din_tail_variant = -1;
     DinTailRun din_tail_run;
+    DinTailKernel din_tail_kernel = nullptr, din_tail_many_kernel = nullptr;   // the f32, split-f16 or raw-row (UNF) form the set-up reached
+    int din_tail_waves = 0;               // waves per workgroup of that form (16 with raw embedding rows for emb_dim <= 16)
     float* din_tail_image = nullptr;
     // DIN launch geometry
     int din_ms = 0;
@@ -54,16 +84,22 @@ struct sprk_engine {
     int din_grid_cap = 0;
     DienRun dien_run{};
     float* dien_frag = nullptr;          // k_dien_seq_mfma's fragment image (NULL: the lane-per-sample kernel)
+    size_t dien_frag_floats = 0;
+    DienSeqKernel dien_seq_kernel = nullptr;   // k_dien_seq_mfma or k_dien_seq for the plan's emb_dim, as h->stage says (choose_route)
     SprkTuning tune;               // the environment's switches as sprk_finalize found them
     // attention on k_din_attn_cols (16 samples per MFMA tile, static weight operand; k_din_cols.h); din_cols_kc = 0: not set up
     int din_cols_kc = 0;
     DinColsRun din_cols_run;
+    DinColsKernels din_cols_kernels{};
     // the whole DIN forward in one launch (k_din_fused: attention + pooling + tail; k_din_fused.h)
     bool din_fused = false;        // TAIL instantiations usable (attention on the cols formulation AND the 128 / 64 tail recognised)
     bool din_fused_attn = false;   // TAIL = false instantiations replace k_din_attn_cols (sprk_din_pool, the unfused two-launch path)
     DinFusedRun din_fused_run;
+    DinFusedKernels din_fused_kernels[2]{};   // k_din_fused for din_cols_kc: [0] pooled vectors out (the attention stage alone), [1] scores out (TAIL)
+    DinFusedKernel din_fused_att_kernel = nullptr;   // ... attention weights out as well
     float* din_fused_image = nullptr;
     bool dien_fused = false;       // DIEN in one launch (k_dien_fused.h): dien_frag AND the 128 / 64 tail on raw split rows
+    DienFusedKernel dien_fused_kernel = nullptr;
     size_t dien_fused_lds = 0;
     // DeepFM_v2: the parsed plan's shape in kV2Variants (match_v2_chain); -1 = no folded form
     int v2_variant = -1;
@@ -78,14 +114,14 @@ struct sprk_engine {
     size_t v2_fo_floats = 0;
     // ... with the small-vocabulary fields folded into one joint table (k_deepfm_v2_joint); -1 = not set up
     int v2j_variant = -1;
-    float* v2j1_image = nullptr;          // k_deepfm_v2_joint1 (one task per wave): its LDS image; NULL = shape not available
+    V2JKernel v2j1_kernel = nullptr;      // k_deepfm_v2_joint1 (one task per wave), HOIST or not; nullptr = shape not available
+    float* v2j1_image = nullptr;          // its LDS image
     size_t v2j1_lds_bytes = 0;
-    bool v2j1_hoist = false;              // k_deepfm_v2_joint1<..., HOIST>: tables larger than the Infinity Cache (k_chain_v2j1.h)
     int v2j1_waves = 8;                   // waves per workgroup of the form chosen (V2J1_WAVES_OF)
     int many_batches = 1;                 // sprk_forward_many: batches scored per launch (sprk_set_many_batches)
     // "one row per id" chain (k_rows_chain): DeepFM_v2 with projections wider than 16 (the reference's Dense(64)) and NeuralCF; -1 = not set up
+    // (the kernels stay in kRowsVariants[rows_variant]: one-batch launches of up to V2J1_MAX_TASKS tasks use fn_one = k_rows_chain1)
     int rows_variant = -1;
-    bool rows_one = true;                 // one-batch launches use k_rows_chain1 (one task per wave)
     bool rows_from_v2 = false;            // set by match_v2_chain: h->v2 holds the parsed DeepFM_v2 plan, tables still to build
     int rows_g_emb = 0;
     RowsRun rows_run;

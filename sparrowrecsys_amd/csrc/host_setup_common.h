@@ -1,5 +1,5 @@
 // host_setup_common.h -- the attention stage's shape table, the interpreter's first-Dense fold, the static split-f16 scales (max |x| on the
-// device, the dynamic-range guard, the power of two), split-f16 fragment packing.
+// device, the dynamic-range guard, the power of two: static_scale / static_scale_host), split-f16 fragment packing.
 // Part of sparrow_hip.hip (one translation unit); included there, not compilable on its own.
 // ---- the attention shapes k_din_attn_cols / k_din_fused take ([r6] until round 6 the dispatch table of k_din_attn: k_din_attn.h) ----
 struct DinVariant { int kc, hc, max_t; };        // emb_dim in (16 (kc - 1), 16 kc], attention hidden 16 hc, history slots <= max_t
@@ -133,7 +133,7 @@ int wide_dynamic_range(const float* rows, long long nrows, int row_floats, int n
     return SPRK_OK;
 }
 
-// The same rule for weights the host already holds (pulled for packing): absmax_nan keeps a NaN that fmaxf would drop, so that the callers'
+// The same rule for weights the host already holds (pulled for packing): absmax_nan keeps a NaN that fmaxf would drop, so that
 // `mx < 3.0e38f` refuses non-finite weights; wide_dynamic_range_host counts over v[0 .. n).
 inline float absmax_nan(float m, float v) { const float a = fabsf(v); return (a > m || a != a) ? a : m; }
 bool wide_dynamic_range_host(const float* v, size_t n, float mx) {
@@ -175,6 +175,31 @@ int device_absmax(const std::vector<AbsmaxJob>& jobs, float* mx, int n_out) {
 // the grid of one job over n floats: a workgroup per 256 floats, at most `cap`
 unsigned absmax_grid(long long n, long long cap) { const long long b = (n + 255) / 256; return (unsigned)(b < cap ? b : cap); }
 
+// The static split-f16 scale of one site: `tabs` (the slot of each job is 0) share ONE power-of-two scale from their common max |x|.
+// *scale = 0 refuses the site -- NaN / Inf among the entries, or a table the dynamic-range guard calls wide -- and the caller keeps its f32
+// form; *mx_out (when given) is the maximum itself, for a caller that derives further scales from it or treats an all-zero table apart.
+int static_scale(const std::vector<AbsmaxJob>& tabs, float* scale, float* mx_out = nullptr) {
+    *scale = 0.f;
+    float mx = 0.f;
+    SPRK_TRY(device_absmax(tabs, &mx, 1));
+    if (mx_out) *mx_out = mx;
+    if (!(mx < 3.0e38f)) return SPRK_OK;
+    for (const AbsmaxJob& t : tabs) {
+        bool wide = false;
+        SPRK_TRY(wide_dynamic_range(t.x, t.rows, t.row_floats, t.ncols, mx, &wide));
+        if (wide) return SPRK_OK;
+    }
+    *scale = pow2_scale(mx);
+    return SPRK_OK;
+}
+// The same for weights the host already holds: the scale of v[0 .. n), 0 = refused
+float static_scale_host(const float* v, size_t n) {
+    float mx = 0.f;
+    for (size_t i = 0; i < n; ++i) mx = absmax_nan(mx, v[i]);
+    if (!(mx < 3.0e38f) || wide_dynamic_range_host(v, n, mx)) return 0.f;
+    return pow2_scale(mx);
+}
+
 // A Dense layer's W^T [N][ld] (K columns) as split-f16 A fragments for the per-sample dynamic-scale path (dyn_split.h):
 // static power-of-two scale putting max |W| in [2^14, 2^15).  *frag stays NULL when switched off (SPRK_DYN_F16=0), when
 // the shape does not tile (N % 16, K % 32) or the weights are not finite.
@@ -183,13 +208,9 @@ int make_dyn_fragments(sprk_engine* h, const float* W, int ld, int N, int K, flo
     *frag = nullptr;
     if (kvalid < 0) kvalid = K;
     if (!h->tune.dyn_f16 || (N & 15) || (K & 31) || kvalid < 1 || kvalid > K) return SPRK_OK;
-    float mx = 0.f;
-    SPRK_TRY(device_absmax({{W, (long long)N, ld, kvalid, 8, 0}}, &mx, 1));
-    if (!(mx < 3.0e38f)) return SPRK_OK;
-    bool wide = false;
-    SPRK_TRY(wide_dynamic_range(W, (long long)N, ld, kvalid, mx, &wide));
-    if (wide) return SPRK_OK;
-    const float w_scale = pow2_scale(mx);
+    float w_scale = 0.f;
+    SPRK_TRY(static_scale({{W, (long long)N, ld, kvalid, 8, 0}}, &w_scale));
+    if (w_scale == 0.f) return SPRK_OK;
     const size_t frag_floats = (size_t)(N / 16) * (K / 32) * 512;
     float* f = nullptr;
     SPRK_TRY(dev_alloc(h, &f, frag_floats * sizeof(float)));

@@ -11,7 +11,8 @@ int setup_dien_stage(sprk_engine* h, DevDin& d) {
     const sprk_plan& p = h->plan;
     const sprk_din& s = p.din;
     d.enabled = 1; d.T = s.T; d.hist_col = s.hist_col; d.cand_col = s.cand_col; d.row_stride = s.row_stride; d.vocab = s.vocab; d.hidden = s.hidden;
-    const size_t img = s.emb_dim == 10 ? DienLayout<10, 32>::total_pad : DienLayout<16, 32>::total_pad;
+    const bool d10 = s.emb_dim == 10;
+    const size_t img = d10 ? DienLayout<10, 32>::total_pad : DienLayout<16, 32>::total_pad;
     SPRK_TRY(need_bytes(h, s.table_slot, (size_t)s.vocab * s.row_stride * 4, "DIEN table"));
     SPRK_TRY(need_bytes(h, s.seq_slot, img * 4, "DIEN sequence weights"));
     d.table = (const float*)h->slot_ptr[s.table_slot];
@@ -20,10 +21,10 @@ int setup_dien_stage(sprk_engine* h, DevDin& d) {
     r.table = d.table;
     r.image = (const float*)h->slot_ptr[s.seq_slot];
     if (!h->tune.dien_mfma || !h->tune.dyn_f16 || s.hidden != 32 || (s.emb_dim != 10 && s.emb_dim != 16)) return SPRK_OK;
-    const bool d10 = s.emb_dim == 10;
-    const size_t fl = d10 ? DienFrag<10, 32>::total_pad : DienFrag<16, 32>::total_pad;
+    h->dien_frag_floats = d10 ? DienFrag<10, 32>::total_pad : DienFrag<16, 32>::total_pad;
     const size_t ok_at = d10 ? DienFrag<10, 32>::S_OK : DienFrag<16, 32>::S_OK;
-    DevScratch<unsigned> d_max;                               // max |E|, read on the device by k_dien_mfma_pack
+    // (open-coded, not static_scale: k_dien_mfma_pack reads max |E| from this device buffer and derives its scales there)
+    DevScratch<unsigned> d_max;
     HIP_TRY(d_max.alloc(1));
     HIP_TRY(hipMemset(d_max.p, 0, sizeof(unsigned)));
     hipLaunchKernelGGL(k_v2_absmax, dim3(1024), dim3(256), 0, 0, d.table, (long long)s.vocab, s.row_stride, s.row_stride, d_max.p);
@@ -36,9 +37,8 @@ int setup_dien_stage(sprk_engine* h, DevDin& d) {
     if (wide) return SPRK_OK;
     const bool guard_on = h->tune.half_range_guard;
     float* frag = nullptr;
-    SPRK_TRY(dev_alloc(h, &frag, fl * sizeof(float)));
-    if (d10) hipLaunchKernelGGL((k_dien_mfma_pack<10, 32>), dim3(1), dim3(256), 0, 0, r.image, (const unsigned*)d_max.p, frag, guard_on ? 1 : 0);
-    else hipLaunchKernelGGL((k_dien_mfma_pack<16, 32>), dim3(1), dim3(256), 0, 0, r.image, (const unsigned*)d_max.p, frag, guard_on ? 1 : 0);
+    SPRK_TRY(dev_alloc(h, &frag, h->dien_frag_floats * sizeof(float)));
+    hipLaunchKernelGGL((d10 ? &k_dien_mfma_pack<10, 32> : &k_dien_mfma_pack<16, 32>), dim3(1), dim3(256), 0, 0, r.image, d_max.p, frag, guard_on ? 1 : 0);
     HIP_TRY(hipGetLastError());
     float ok = 0.f;
     HIP_TRY(hipMemcpy(&ok, frag + ok_at, sizeof(float), hipMemcpyDeviceToHost));
@@ -51,6 +51,12 @@ int setup_dien_stage(sprk_engine* h, DevDin& d) {
 // (k_din_prep_w), the per-id c-term table vc, the movie table pre-split into f16 hi / lo pairs, the cols kernel's A fragments.  Refused --
 // the generic k_din_pool stays, and the tables made so far are released -- for non-finite weights, outlier rows, a split table beyond
 // 32-bit offsets, and a W4 whose range does not fit the split.
+// [kc - 1]; k_din_fused here in its attention-only forms (pooled vectors out; ATT: attention weights too) -- the TAIL forms: host_setup_din_tail.h
+const DinColsKernels kDinColsKernels[2] = {{&k_din_attn_cols<1, false>, &k_din_attn_cols<1, true>}, {&k_din_attn_cols<2, false>, &k_din_attn_cols<2, true>}};
+const DinFusedKernels kDinFusedAttnKernels[2] = {{&k_din_fused<1, false, false>, &k_din_fused<1, true, false>},
+                                                 {&k_din_fused<2, false, false>, &k_din_fused<2, true, false>}};
+const DinFusedKernel kDinFusedAttKernels[2] = {&k_din_fused<1, false, false, true>, &k_din_fused<2, false, false, true>};
+
 int setup_din_attn(sprk_engine* h, const DevDin& d) {
     const sprk_plan& p = h->plan;
     const sprk_din& s = p.din;
@@ -73,14 +79,13 @@ int setup_din_attn(sprk_engine* h, const DevDin& d) {
     hipLaunchKernelGGL(k_din_prep_w, dim3(8), dim3(256), 0, 0, d.W, s.hidden, s.row_stride, KP, 1.0f, w12, w4);
     HIP_TRY(hipGetLastError());
     // power-of-two scales from max|E|, max|W12|, max|W4|: |A_b| <= max|W12| + max|W4| max|E|
-    float mx[3];
-    SPRK_TRY(device_absmax({{d.table, (long long)s.vocab, s.row_stride, s.row_stride, absmax_grid((long long)s.vocab * s.row_stride, 8192), 0},
-                            {w12, (long long)s.hidden, KP, KP, 4, 1}, {w4, (long long)s.hidden, KP, KP, 4, 2}}, mx, 3));
-    if (!(mx[0] < 3.0e38f) || !(mx[1] < 3.0e38f) || !(mx[2] < 3.0e38f)) return refuse();   // NaN / Inf weights
-    bool wide = false;                                        // outlier rows: the ordinary rows would lose their lo halves
-    SPRK_TRY(wide_dynamic_range(d.table, (long long)s.vocab, s.row_stride, s.row_stride, mx[0], &wide));
-    if (wide) return refuse();
-    const float h_scale = pow2_scale(mx[0]), a_scale = pow2_scale(mx[1] + mx[2] * mx[0]);
+    // (the table by the rule of every static scale -- NaN / Inf, outlier rows: the ordinary rows would lose their lo halves; the two weight
+    //  maxima enter a_scale as a sum with the table's and are only checked for NaN / Inf)
+    float h_scale = 0.f, mxE = 0.f, mxW[2];
+    SPRK_TRY(static_scale({{d.table, (long long)s.vocab, s.row_stride, s.row_stride, absmax_grid((long long)s.vocab * s.row_stride, 8192), 0}}, &h_scale, &mxE));
+    SPRK_TRY(device_absmax({{w12, (long long)s.hidden, KP, KP, 4, 0}, {w4, (long long)s.hidden, KP, KP, 4, 1}}, mxW, 2));
+    if (h_scale == 0.f || !(mxW[0] < 3.0e38f) || !(mxW[1] < 3.0e38f)) return refuse();
+    const float a_scale = pow2_scale(mxW[0] + mxW[1] * mxE);
     hipLaunchKernelGGL(k_din_prep_w, dim3(8), dim3(256), 0, 0, d.W, s.hidden, s.row_stride, KP, a_scale, w12, w4);
     HIP_TRY(hipGetLastError());
     if (split_bytes >= ((size_t)4 << 30)) return refuse();
@@ -121,10 +126,9 @@ int setup_din_attn(sprk_engine* h, const DevDin& d) {
     c.coef = coef; c.idp = p.n_id_cols;
     const int lds_max = (2 * 64 * 36 + DC_WAVES * 16 * p.n_id_cols + DC_WAVES * 2 * 64 * 8) * 4;
     if (lds_max > 160 * 1024) return fail(SPRK_EINVAL, "DIN attention needs %d bytes of LDS", lds_max);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_attn_cols<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_attn_cols<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_attn_cols<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_attn_cols<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max));
+    h->din_cols_kernels = kDinColsKernels[kc - 1];
+    SPRK_TRY(set_max_lds(h->din_cols_kernels.one, lds_max));
+    SPRK_TRY(set_max_lds(h->din_cols_kernels.many, lds_max));
     h->din_cols_kc = kc;
     // k_din_fused (k_din_fused.h) takes the same tables; its tail half is set up by setup_din_tail
     // (a trip of its slot loop is four slots: for the reference's own hist_len = 5 that is 8 slots of work for 5, and
@@ -137,12 +141,11 @@ int setup_din_attn(sprk_engine* h, const DevDin& d) {
     f.tsplit = c.tsplit; f.vc = c.vc; f.frag = c.frag; f.coef = c.coef; f.idp = c.idp;
     const int lds_attn = (DF_COEF_FLOATS + DF_WAVES * 16 * p.n_id_cols + DF_WAVES * 2 * 64 * 8) * 4;
     if (lds_attn > 160 * 1024) return SPRK_OK;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<1, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attn));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<1, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attn));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<2, false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attn));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<2, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attn));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<1, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attn));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<2, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_attn));
+    h->din_fused_kernels[0] = kDinFusedAttnKernels[kc - 1];
+    h->din_fused_att_kernel = kDinFusedAttKernels[kc - 1];
+    SPRK_TRY(set_max_lds(h->din_fused_kernels[0].one, lds_attn));
+    SPRK_TRY(set_max_lds(h->din_fused_kernels[0].many, lds_attn));
+    SPRK_TRY(set_max_lds(h->din_fused_att_kernel, lds_attn));
     h->din_fused_attn = true;
     return SPRK_OK;
 }
@@ -170,7 +173,7 @@ int setup_din_stage(sprk_engine* h, DevDin& d) {
     const int hs = s.row_stride + 4;
     h->din_lds_bytes = ((size_t)ms * s.T * hs + (size_t)ms * hs + (size_t)ms * s.T) * sizeof(float);
     if (h->din_lds_bytes > 160 * 1024) return fail(SPRK_EINVAL, "DIN stage needs %zu bytes of LDS", h->din_lds_bytes);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k_din_pool), hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->din_lds_bytes));
+    SPRK_TRY(set_max_lds(k_din_pool, h->din_lds_bytes));
     h->din_grid_cap = lds_grid_cap(h, h->din_lds_bytes);
     if (h->tune.din_legacy || !h->tune.din_half || !h->tune.din_cols) return SPRK_OK;
     return setup_din_attn(h, d);

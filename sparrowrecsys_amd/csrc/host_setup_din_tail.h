@@ -6,66 +6,34 @@ constexpr int DT_WAVES = 8;
 // UNF: emb_dim <= 16 fits 128 VGPRs -> sixteen waves per CU, ONE task per wave at B = 65 536; emb_dim <= 32 holds four operand pairs
 // and would spill 81 dwords at that cap: eight waves
 constexpr int dt_waves_unf(int kpc) { return kpc >= 2 ? 8 : 16; }
-typedef void (*DinTailLaunchFn)(const DinTailRun&, const int*, const float*, const float*, float*, int, int*, const float*, int, hipStream_t);
-typedef void (*DinTailLaunchManyFn)(const DinTailRun&, const DinTailMany&, int, int*, const float*, int, hipStream_t);
-typedef void (*DinTailPackFn)(const float*, int, int, int, int, int, const float*, const float*, const float*, int, const float*,
-                              const float*, const float*, int, const float*, float*, const float*, const float*);
-template <int N0C, int N1C, int KPC>
-void din_tail_launch(const DinTailRun& a, const int* ids, const float* dense, const float* aux, float* out, int B, int* err,
-                     const float* image, int grid, hipStream_t st) {
-    const size_t lds = DinTailLds<N0C, N1C, KPC>::bytes;
-    static const DinTailMany none{};
-    if (a.e_unscale != 0.f)
-        hipLaunchKernelGGL((k_din_tail<N0C, N1C, KPC, dt_waves_unf(KPC), true, false, true>), dim3(grid), dim3(dt_waves_unf(KPC) * 64), lds, st,
-                           a, ids, dense, aux, out, B, err, image, none);
-    else if (a.inv_w1_scale != 0.f)
-        hipLaunchKernelGGL((k_din_tail<N0C, N1C, KPC, DT_WAVES, true, false>), dim3(grid), dim3(DT_WAVES * 64), lds, st,
-                           a, ids, dense, aux, out, B, err, image, none);
-    else
-        hipLaunchKernelGGL((k_din_tail<N0C, N1C, KPC, DT_WAVES, false, false>), dim3(grid), dim3(DT_WAVES * 64), lds, st,
-                           a, ids, dense, aux, out, B, err, image, none);
-}
-template <int N0C, int N1C, int KPC>
-void din_tail_launch_many(const DinTailRun& a, const DinTailMany& m, int B, int* err, const float* image, int grid, hipStream_t st) {
-    const size_t lds = DinTailLds<N0C, N1C, KPC>::bytes;
-    if (a.e_unscale != 0.f)
-        hipLaunchKernelGGL((k_din_tail<N0C, N1C, KPC, dt_waves_unf(KPC), true, true, true>), dim3(grid), dim3(dt_waves_unf(KPC) * 64), lds, st,
-                           a, (const int*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, B, err, image, m);
-    else if (a.inv_w1_scale != 0.f)
-        hipLaunchKernelGGL((k_din_tail<N0C, N1C, KPC, DT_WAVES, true, true>), dim3(grid), dim3(DT_WAVES * 64), lds, st,
-                           a, (const int*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, B, err, image, m);
-    else
-        hipLaunchKernelGGL((k_din_tail<N0C, N1C, KPC, DT_WAVES, false, true>), dim3(grid), dim3(DT_WAVES * 64), lds, st,
-                           a, (const int*)nullptr, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, B, err, image, m);
-}
-template <int N0C, int N1C, int KPC>
-void din_tail_pack(const float* W0, int ldw0, int p_off, int Dp, int n_off, int n_num, const float* b0, const float* a0,
-                   const float* W1, int ldw1, const float* b1, const float* a1, const float* hw, int n_hw, const float* w1frag,
-                   float* img, const float* w0pfrag, const float* w0efrag) {
-    hipLaunchKernelGGL((k_din_tail_pack<N0C, N1C, KPC>), dim3(1), dim3(256), 0, 0, W0, ldw0, p_off, Dp, n_off, n_num, b0, a0, W1, ldw1,
-                       b1, a1, hw, n_hw, w1frag, img, w0pfrag, w0efrag);
-}
+typedef void (*DinTailPackKernel)(const float*, int, int, int, int, int, const float*, const float*, const float*, int, const float*,
+                                  const float*, const float*, int, const float*, float*, const float*, const float*);
+enum DinTailForm { DT_F32, DT_DYN, DT_UNF };      // fc1 on f32 MFMA; split-f16 fragments; raw split rows for the embedding columns as well
 struct DinTailVariant {
     int n0c, n1c, kpc;
-    const void* fn[6];                // [DYN][MB] instantiations, then UNF [MB]
+    DinTailKernel fn[3][2];           // [DinTailForm][MB]
     size_t lds_bytes;
-    DinTailLaunchFn launch;
-    DinTailLaunchManyFn launch_many;
-    DinTailPackFn pack;
+    DinTailPackKernel pack;
 };
-#define DIN_TAIL_VARIANT(N0C, N1C, KPC) {N0C, N1C, KPC, {reinterpret_cast<const void*>(&k_din_tail<N0C, N1C, KPC, DT_WAVES, false, false>), \
-                                         reinterpret_cast<const void*>(&k_din_tail<N0C, N1C, KPC, DT_WAVES, false, true>),               \
-                                         reinterpret_cast<const void*>(&k_din_tail<N0C, N1C, KPC, DT_WAVES, true, false>),               \
-                                         reinterpret_cast<const void*>(&k_din_tail<N0C, N1C, KPC, DT_WAVES, true, true>),                \
-                                         reinterpret_cast<const void*>(&k_din_tail<N0C, N1C, KPC, dt_waves_unf(KPC), true, false, true>),     \
-                                         reinterpret_cast<const void*>(&k_din_tail<N0C, N1C, KPC, dt_waves_unf(KPC), true, true, true>)},     \
-                                         DinTailLds<N0C, N1C, KPC>::bytes, &din_tail_launch<N0C, N1C, KPC>, &din_tail_launch_many<N0C, N1C, KPC>, \
-                                         &din_tail_pack<N0C, N1C, KPC>}
+// (the cast is there for ONE reason, the order of the library's device code: it names the instantiation where it stands, so every variant's
+//  kernels are emitted ahead of the packers as they always were, and scripts/isa/device_code_diff.py -- a line-by-line comparison -- can show
+//  that a change of the host code moved no instruction.  A plain &k_din_tail<...> launches the same kernels.)
+#define DIN_TAIL_FN(...) static_cast<DinTailKernel>(&k_din_tail<__VA_ARGS__>)
+#define DIN_TAIL_VARIANT(N0C, N1C, KPC)                                                                                                   \
+    {N0C, N1C, KPC,                                                                                                                       \
+     {{DIN_TAIL_FN(N0C, N1C, KPC, DT_WAVES, false, false), DIN_TAIL_FN(N0C, N1C, KPC, DT_WAVES, false, true)},                              \
+      {DIN_TAIL_FN(N0C, N1C, KPC, DT_WAVES, true, false), DIN_TAIL_FN(N0C, N1C, KPC, DT_WAVES, true, true)},                                \
+      {DIN_TAIL_FN(N0C, N1C, KPC, dt_waves_unf(KPC), true, false, true), DIN_TAIL_FN(N0C, N1C, KPC, dt_waves_unf(KPC), true, true, true)}}, \
+     DinTailLds<N0C, N1C, KPC>::bytes, &k_din_tail_pack<N0C, N1C, KPC>}
 const DinTailVariant kDinTailVariants[] = {
     DIN_TAIL_VARIANT(8, 4, 2),        // DIN.py:161-167 widths 128 / 64, emb_dim 17..32 (BASELINE config 3)
     DIN_TAIL_VARIANT(8, 4, 1),        // ... emb_dim <= 16 (the reference's own emb_dim 10)
     DIN_TAIL_VARIANT(4, 2, 2), DIN_TAIL_VARIANT(4, 2, 1),     // half-width tails (64 / 32)
 };
+
+// k_din_fused<KC, MB, TAIL = true>: the whole DIN forward, [kc - 1] (the attention-only forms: host_setup_din.h)
+const DinFusedKernels kDinFusedTailKernels[2] = {{&k_din_fused<1, false, true>, &k_din_fused<1, true, true>},
+                                                 {&k_din_fused<2, false, true>, &k_din_fused<2, true, true>}};
 
 // Recognise the DIN tail the first-Dense fold left behind (every embedding column folded, fc0 reading only the
 // pooled history + numerics, two PReLU Dense layers, one weighted tap) and set up k_din_tail for it.
@@ -138,40 +106,25 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
             for (int g2 = 0; g2 < g && ok; ++g2) ok = raw[g2] != raw[g];
         }
         // one static scale for all columns' rows; an outlier row keeps the folded tables
-        float mx = 0.f;
+        float e_scale = 0.f;
         if (ok) {
             std::vector<AbsmaxJob> jobs;
             for (int g = 0; g < dp->n_acc; ++g)
                 jobs.push_back({(const float*)h->slot_ptr[raw[g]->slot], (long long)raw[g]->vocab, raw[g]->row_stride, 4 * raw[g]->count, 256, 0});
-            SPRK_TRY(device_absmax(jobs, &mx, 1));
-            ok = mx < 3.0e38f;
-            for (int g = 0; g < dp->n_acc && ok; ++g) {
-                bool wide = false;
-                SPRK_TRY(wide_dynamic_range((const float*)h->slot_ptr[raw[g]->slot], (long long)raw[g]->vocab, raw[g]->row_stride,
-                                            4 * raw[g]->count, mx, &wide));
-                ok = !wide;
-            }
+            SPRK_TRY(static_scale(jobs, &e_scale));
+            ok = e_scale != 0.f;
         }
         if (ok) {
-            const float e_scale = pow2_scale(mx);
             std::vector<float> W0h;
             int rcp = pull(W0h, W0full, (size_t)q0.N * q0.ldw);
             if (rcp) return rcp;
-            float amax = 0.f;
+            // fc0's raw-row columns: NaN / Inf, or an outlier weight (the ordinary columns' lo halves would be subnormal), keep the folded tables
+            std::vector<float> cols;
             for (int g = 0; g < dp->n_acc; ++g)
                 for (int n = 0; n < q0.N; ++n)
-                    for (int d = 0; d < 4 * raw[g]->count; ++d) amax = absmax_nan(amax, W0h[(size_t)n * q0.ldw + raw[g]->dst - q0.src_off + d]);
-            ok = amax < 3.0e38f;                                   // NaN / Inf in fc0's columns: the folded tables
-            // an outlier weight: the ordinary columns' lo halves would be subnormal (the rule of wide_dynamic_range over fc0's raw-row columns)
-            if (ok) {
-                std::vector<float> cols;
-                for (int g = 0; g < dp->n_acc; ++g)
-                    for (int n = 0; n < q0.N; ++n)
-                        for (int d = 0; d < 4 * raw[g]->count; ++d) cols.push_back(W0h[(size_t)n * q0.ldw + raw[g]->dst - q0.src_off + d]);
-                ok = !wide_dynamic_range_host(cols.data(), cols.size(), amax);
-            }
-            if (ok) {
-                const float w_scale = pow2_scale(amax);
+                    for (int d = 0; d < 4 * raw[g]->count; ++d) cols.push_back(W0h[(size_t)n * q0.ldw + raw[g]->dst - q0.src_off + d]);
+            const float w_scale = static_scale_host(cols.data(), cols.size());
+            if (w_scale != 0.f) {
                 std::vector<float> fr((size_t)n0c * nblk * 512, 0.f);
                 _Float16* fh = reinterpret_cast<_Float16*>(fr.data());
                 for (int nb = 0; nb < n0c; ++nb)
@@ -210,11 +163,17 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
             }
         }
     }
-    tv.pack(o0.W, o0.ldw, p_off, Dp, n_off, n_num, o0.bias, o0.alpha, o1.W, o1.ldw, o1.bias, o1.alpha, tp.w, tp.len, w1frag, h->din_tail_image, w0pfrag,
-            w0efrag);
+    hipLaunchKernelGGL(tv.pack, dim3(1), dim3(256), 0, 0, o0.W, o0.ldw, p_off, Dp, n_off, n_num, o0.bias, o0.alpha, o1.W, o1.ldw, o1.bias, o1.alpha, tp.w,
+                       tp.len, w1frag, h->din_tail_image, w0pfrag, w0efrag);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    for (int i = 0; i < 6; ++i) HIP_TRY(hipFuncSetAttribute(tv.fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int)tv.lds_bytes));
+    // the form the fragments above came to, for one batch and for several
+    const DinTailForm form = r.e_unscale != 0.f ? DT_UNF : (r.inv_w1_scale != 0.f ? DT_DYN : DT_F32);
+    h->din_tail_kernel = tv.fn[form][0];
+    h->din_tail_many_kernel = tv.fn[form][1];
+    h->din_tail_waves = form == DT_UNF ? dt_waves_unf(kpc) : DT_WAVES;
+    SPRK_TRY(set_max_lds(h->din_tail_kernel, tv.lds_bytes));
+    SPRK_TRY(set_max_lds(h->din_tail_many_kernel, tv.lds_bytes));
     h->din_tail_variant = variant;
     // k_din_fused: the same tail as the epilogue of the attention kernel (k_din_fused.h).  Needs the cols formulation of the attention
     // (set up before this function), DIN.py's widths 128 / 64, fc1 AND fc0's pooled columns as split-f16 fragments, folded rows for
@@ -269,10 +228,9 @@ int setup_din_tail(sprk_engine* h, DevPlan* dp) {
             }
             f.n_ucols = unf_pairs ? r.n_cols : n_unf;
             f.image = h->din_fused_image;
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_full));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_full));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_full));
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_din_fused<2, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_full));
+            h->din_fused_kernels[1] = kDinFusedTailKernels[kc - 1];
+            SPRK_TRY(set_max_lds(h->din_fused_kernels[1].one, lds_full));
+            SPRK_TRY(set_max_lds(h->din_fused_kernels[1].many, lds_full));     // (the persistent form: forward_many's groups and sprk_forward's large batches)
             h->din_fused = true;
         }
     }
@@ -284,10 +242,9 @@ int setup_dien_fused(sprk_engine* h) {
     if (h->plan.din.enabled != 2 || !h->dien_frag || !h->tune.dien_fused || h->din_tail_variant < 0) return SPRK_OK;
     const DinTailVariant& tv = kDinTailVariants[h->din_tail_variant];
     if (tv.n0c != 8 || tv.n1c != 4 || tv.kpc != 1 || h->din_tail_run.e_unscale == 0.f) return SPRK_OK;
-    const bool d10 = h->plan.din.emb_dim == 10;
-    h->dien_fused_lds = ((d10 ? DienFrag<10, 32>::total_pad : DienFrag<16, 32>::total_pad) + DinTailLds<8, 4, 1>::total_pad) * sizeof(float);
-    HIP_TRY(hipFuncSetAttribute(d10 ? reinterpret_cast<const void*>(&k_dien_fused<10, 32, 8, 4>) : reinterpret_cast<const void*>(&k_dien_fused<16, 32, 8, 4>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->dien_fused_lds));
+    h->dien_fused_kernel = h->plan.din.emb_dim == 10 ? &k_dien_fused<10, 32, 8, 4> : &k_dien_fused<16, 32, 8, 4>;
+    h->dien_fused_lds = (h->dien_frag_floats + DinTailLds<8, 4, 1>::total_pad) * sizeof(float);
+    SPRK_TRY(set_max_lds(h->dien_fused_kernel, h->dien_fused_lds));
     h->dien_fused = true;
     return SPRK_OK;
 }

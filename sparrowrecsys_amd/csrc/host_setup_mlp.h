@@ -2,14 +2,12 @@
 // Part of sparrow_hip.hip (one translation unit); included there, not compilable on its own.
 // ---- k_mlp_rows<8, 8, NBIG, NS, WAVES, DYN, WK> ----
 constexpr int MR_WAVES = 8;
-typedef void (*MlpRowsKernel)(const MlpRowsRun, const int*, const float*, float*, int, int*, const float*);
 // NS = 8 (EmbeddingMLP.py / WideNDeep.py as written: eight genre columns) has its own instantiations for the reference's shape
 // (two big columns, split-f16 second layer); every other shape runs the generic ones (NS = -1: the count is a run-time value).
 template <int NBIG, int NS, bool DYN>
 MlpRowsKernel mlp_rows_kernel_wk(int wk) {
     return wk == 1 ? &k_mlp_rows<8, 8, NBIG, NS, MR_WAVES, DYN, 1> : wk == 2 ? &k_mlp_rows<8, 8, NBIG, NS, MR_WAVES, DYN, 2> : &k_mlp_rows<8, 8, NBIG, NS, MR_WAVES, DYN, 0>;
 }
-typedef void (*MlpRowsManyKernel)(const MlpRowsRun, const MlpRowsMany, int, int*, const float*);
 template <int NBIG, int NS, bool DYN>
 MlpRowsManyKernel mlp_rows_many_kernel_wk(int wk) {
     return wk == 1 ? &k_mlp_rows_many<8, 8, NBIG, NS, MR_WAVES, DYN, 1> : wk == 2 ? &k_mlp_rows_many<8, 8, NBIG, NS, MR_WAVES, DYN, 2> : &k_mlp_rows_many<8, 8, NBIG, NS, MR_WAVES, DYN, 0>;
@@ -151,10 +149,9 @@ int setup_mlp_rows(sprk_engine* h) {
     r.small = h->mlp_rows_small; r.small_floats = (int)small_floats;
     if (r.n_num < 8) r.flags |= 2;                                       // b0 in the numerics' eighth K slot (k_mlp_rows_pack put it there)
     h->mlp_rows_kernel = mlp_rows_kernel(r.n_big, r.n_small, dyn, r.wide_kind);
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(h->mlp_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    SPRK_TRY(set_max_lds(h->mlp_rows_kernel, lds));
     h->mlp_rows_many_kernel = h->tune.mlp_rows_many ? mlp_rows_many_kernel(r.n_big, r.n_small, dyn, r.wide_kind) : nullptr;
-    if (h->mlp_rows_many_kernel)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(h->mlp_rows_many_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (h->mlp_rows_many_kernel) SPRK_TRY(set_max_lds(h->mlp_rows_many_kernel, lds));
     h->mlp_rows_run = r;
     h->mlp_rows_lds = lds;
     h->mlp_rows_nbig = r.n_big;

@@ -3,54 +3,27 @@
 // ---- dispatch table for k_deepfm_pairs<NF, NV, H0C, H1C, WAVES, DYN, SEP> ----
 constexpr int V1_WAVES = 8;
 constexpr int V1_ONE_MAX_TASKS = 16384;       // one-task-per-wave shape (k_deepfm_pairs1) up to B = 262 144
-typedef void (*V1LaunchFn)(const V1Run&, const int*, const float*, float*, int, int*, int, hipStream_t);
-typedef void (*V1LaunchManyFn)(const V1Run&, const V1Many&, int, int*, int, hipStream_t);
-template <int NF, int NV, bool SEP>
-void v1_launch(const V1Run& a, const int* ids, const float* dense, float* out, int B, int* err, int grid, hipStream_t st) {
-    const size_t lds = V1Lds<4, 4, (NV + 3) / 4>::bytes;
-    if (a.inv_w1_scale != 0.f)
-        hipLaunchKernelGGL((k_deepfm_pairs<NF, NV, 4, 4, V1_WAVES, true, SEP>), dim3(grid), dim3(V1_WAVES * 64), lds, st, a, ids, dense, out, B, err);
-    else
-        hipLaunchKernelGGL((k_deepfm_pairs<NF, NV, 4, 4, V1_WAVES, false, SEP>), dim3(grid), dim3(V1_WAVES * 64), lds, st, a, ids, dense, out, B, err);
-}
-// one task per wave (narrow rows, split-f16 form only): grid = ceil(tasks / waves), no cap
-template <int NF, int NV, bool SEP>
-void v1_launch_one(const V1Run& a, const int* ids, const float* dense, float* out, int B, int* err, int grid, hipStream_t st) {
-    if constexpr (NV <= 4) {
-        const size_t lds = V1Lds<4, 4, 1>::bytes;
-        hipLaunchKernelGGL((k_deepfm_pairs1<NF, NV, 4, 4, V1_WAVES, SEP>), dim3(grid), dim3(V1_WAVES * 64), lds, st, a, ids, dense, out, B, err);
-    }
-}
-template <int NF, int NV, bool SEP>
-void v1_launch_many(const V1Run& a, const V1Many& m, int B, int* err, int grid, hipStream_t st) {
-    const size_t lds = V1Lds<4, 4, (NV + 3) / 4>::bytes;
-    if (a.inv_w1_scale != 0.f)
-        hipLaunchKernelGGL((k_deepfm_pairs_many<NF, NV, 4, 4, V1_WAVES, true, SEP>), dim3(grid), dim3(V1_WAVES * 64), lds, st, a, m, B, err);
-    else
-        hipLaunchKernelGGL((k_deepfm_pairs_many<NF, NV, 4, 4, V1_WAVES, false, SEP>), dim3(grid), dim3(V1_WAVES * 64), lds, st, a, m, B, err);
-}
-template <int NF, int NV, bool SEP>
-int v1_prepare(const V1Run& r, float* img) {
-    constexpr int PC = (NV + 3) / 4;
-    hipLaunchKernelGGL((k_v1_pack_image<4, 4, PC>), dim3(1), dim3(256), 0, 0, r, img);
-    HIP_TRY(hipGetLastError());
-    const size_t lds = V1Lds<4, 4, PC>::bytes;
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_deepfm_pairs<NF, NV, 4, 4, V1_WAVES, true, SEP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_deepfm_pairs<NF, NV, 4, 4, V1_WAVES, false, SEP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_deepfm_pairs_many<NF, NV, 4, 4, V1_WAVES, true, SEP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_deepfm_pairs_many<NF, NV, 4, 4, V1_WAVES, false, SEP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    if constexpr (NV <= 4)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_deepfm_pairs1<NF, NV, 4, 4, V1_WAVES, SEP>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return SPRK_OK;
-}
-struct V1Variant { int nf, nv; bool sep; V1LaunchFn launch; V1LaunchFn launch_one; V1LaunchManyFn launch_many; int (*prepare)(const V1Run&, float*); size_t lds_bytes; };
-#define V1_VARIANT(NF, NV, SEP) {NF, NV, SEP, &v1_launch<NF, NV, SEP>, &v1_launch_one<NF, NV, SEP>, &v1_launch_many<NF, NV, SEP>, &v1_prepare<NF, NV, SEP>, V1Lds<4, 4, (NV + 3) / 4>::bytes}
-#define V1_BOTH(NF, NV) V1_VARIANT(NF, NV, true), V1_VARIANT(NF, NV, false)
+// fn / fn_many: deep1 (and deep0's embedding block) as split-f16 fragments (_dyn) or on f32 MFMA (_f32).  fn_one: one task per wave (narrow rows,
+// split-f16 form only; grid = ceil(tasks / waves), no cap) -- nullptr where a row is wider than 16 floats: k_deepfm_pairs1 has no such form
+struct V1Variant {
+    int nf, nv;
+    bool sep;
+    V1Kernel fn_dyn, fn_f32, fn_one;
+    V1ManyKernel fn_many_dyn, fn_many_f32;
+    void (*pack)(const V1Run, float*);
+    size_t lds_bytes;
+};
+#define V1_VARIANT(NF, NV, SEP, ONE)                                                                                                    \
+    {NF, NV, SEP, &k_deepfm_pairs<NF, NV, 4, 4, V1_WAVES, true, SEP>, &k_deepfm_pairs<NF, NV, 4, 4, V1_WAVES, false, SEP>, ONE,         \
+     &k_deepfm_pairs_many<NF, NV, 4, 4, V1_WAVES, true, SEP>, &k_deepfm_pairs_many<NF, NV, 4, 4, V1_WAVES, false, SEP>,                 \
+     &k_v1_pack_image<4, 4, (NV + 3) / 4>, V1Lds<4, 4, (NV + 3) / 4>::bytes}
+#define V1_ONE(NF, NV, SEP) &k_deepfm_pairs1<NF, NV, 4, 4, V1_WAVES, SEP>
+#define V1_BOTH(NF, NV) V1_VARIANT(NF, NV, true, V1_ONE(NF, NV, true)), V1_VARIANT(NF, NV, false, V1_ONE(NF, NV, false))
 const V1Variant kV1Variants[] = {
     V1_BOTH(6, 4),    // BASELINE config 2: 6 fields, emb_dim 16, deep 64-64 (sep = the deep part's own movieId / userId tables, DeepFM.py:106)
     V1_BOTH(4, 3),    // the reference's own DeepFM.py: 4 fields, emb_dim 10 (rows padded to 12)
     V1_BOTH(4, 4),
-    V1_BOTH(4, 16),   // BASELINE config 4: emb_dim 64 -- 256-byte rows gathered whole (four pieces per lane)
+    V1_VARIANT(4, 16, true, nullptr), V1_VARIANT(4, 16, false, nullptr),   // BASELINE config 4: emb_dim 64 -- 256-byte rows gathered whole (four pieces per lane)
 };
 
 // Recognise the plan models.DeepFM emits (DeepFM.py graph: pair dots + first order + 2-layer deep part) and set up
@@ -220,7 +193,8 @@ int setup_deepfm_pairs(sprk_engine* h) {
     {
         float* img = nullptr;
         SPRK_TRY(dev_alloc(h, &img, kV1Variants[variant].lds_bytes));
-        SPRK_TRY(kV1Variants[variant].prepare(r, img));
+        hipLaunchKernelGGL(kV1Variants[variant].pack, dim3(1), dim3(256), 0, 0, r, img);
+        HIP_TRY(hipGetLastError());
         HIP_TRY(hipDeviceSynchronize());
         r.image = img;
     }
@@ -233,13 +207,10 @@ int setup_deepfm_pairs(sprk_engine* h) {
                 const long long rows = (long long)r.vocab[f] + 1;
                 jobs.push_back({deep_tables[f], rows, Dp, Dp, absmax_grid(rows * Dp, 8192), 0});
             }
-            float mx = 0.f;
-            SPRK_TRY(device_absmax(jobs, &mx, 1));
-            bool wide = false;
-            for (int f = 0; f < r.n_deep && !wide && mx > 0.f && mx < 3.0e38f; ++f)
-                SPRK_TRY(wide_dynamic_range(deep_tables[f], (long long)r.vocab[f] + 1, Dp, Dp, mx, &wide));
-            if (mx > 0.f && mx < 3.0e38f && !wide) {
-                r.e_scale = pow2_scale(mx);
+            float mx = 0.f, e_scale = 0.f;
+            SPRK_TRY(static_scale(jobs, &e_scale, &mx));
+            if (e_scale != 0.f && mx > 0.f) {                       // (all-zero tables: nothing to split)
+                r.e_scale = e_scale;
                 r.e_inv = r.inv_w0_scale / r.e_scale;
             }
         }
@@ -284,9 +255,15 @@ int setup_deepfm_pairs(sprk_engine* h) {
             r.w1c = w1c;
         }
     }
-    {
-        h->v1_one = r.tab && r.w1frag && PC == 1 && h->tune.v1_one;
-    }
+    // the kernels of this handle, chosen once: DYN by the fragments; k_deepfm_pairs1 for one-batch launches where it exists
+    const V1Variant& vv = kV1Variants[variant];
+    const bool dyn = r.inv_w1_scale != 0.f;
+    h->v1_kernel = dyn ? vv.fn_dyn : vv.fn_f32;
+    h->v1_many_kernel = dyn ? vv.fn_many_dyn : vv.fn_many_f32;
+    h->v1_one_kernel = (r.tab && r.w1frag && PC == 1 && h->tune.v1_one) ? vv.fn_one : nullptr;
+    SPRK_TRY(set_max_lds(h->v1_kernel, vv.lds_bytes));
+    SPRK_TRY(set_max_lds(h->v1_many_kernel, vv.lds_bytes));
+    if (h->v1_one_kernel) SPRK_TRY(set_max_lds(h->v1_one_kernel, vv.lds_bytes));
     h->v1_run = r;
     h->v1_variant = variant;
     return SPRK_OK;

@@ -2,44 +2,25 @@
 // Part of sparrow_hip.hip (one translation unit); included there, not compilable on its own.
 // ---- dispatch table for k_rows_chain<KPC, H0C, H1C, G_BIG, NJF, HASNUM> ----
 constexpr int RC_WAVES = 8;
-typedef void (*RowsLaunchFn)(const RowsRun&, const int*, const float*, float*, int, int*, const float*, int, size_t, hipStream_t);
-typedef void (*RowsLaunchManyFn)(const RowsRun&, const RowsMany&, int, int*, const float*, int, size_t, hipStream_t);
-template <int KPC, int H0C, int H1C, int G_BIG, int NJF, bool HASNUM, bool UNF>
-void rows_launch(const RowsRun& a, const int* ids, const float* dense, float* out, int B, int* err, const float* image, int grid,
-                 size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((k_rows_chain<KPC, H0C, H1C, G_BIG, NJF, HASNUM, RC_WAVES, UNF>), dim3(grid), dim3(RC_WAVES * 64), lds, st, a, ids, dense,
-                       out, B, err, image);
-}
-template <int KPC, int H0C, int H1C, int G_BIG, int NJF, bool HASNUM, bool UNF>
-void rows_launch_one(const RowsRun& a, const int* ids, const float* dense, float* out, int B, int* err, const float* image, int grid,
-                     size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((k_rows_chain1<KPC, H0C, H1C, G_BIG, NJF, HASNUM, RC_WAVES, UNF>), dim3(grid), dim3(RC_WAVES * 64), lds, st, a, ids, dense,
-                       out, B, err, image);
-}
-template <int KPC, int H0C, int H1C, int G_BIG, int NJF, bool HASNUM, bool UNF>
-void rows_launch_many(const RowsRun& a, const RowsMany& m, int B, int* err, const float* image, int grid, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((k_rows_chain_many<KPC, H0C, H1C, G_BIG, NJF, HASNUM, RC_WAVES, UNF>), dim3(grid), dim3(RC_WAVES * 64), lds, st, a, m, B,
-                       err, image);
+// the weight image's layout as the kernels read it (RowsLds, k_rows_chain.h): the set-ups pack from these numbers
+struct RowsLayout { int image_floats, ss, rb, sn, s1, off_wn, off_bn, off_m, off_c0, off_w1, off_b1, off_hfm, off_hd, off_fn, off_cp, off_af; };
+template <class LD> constexpr RowsLayout rows_layout() {
+    return {LD::total_pad, LD::SS, LD::RB, LD::SN, LD::S1, LD::off_wn, LD::off_bn, LD::off_m, LD::off_c0, LD::off_w1, LD::off_b1, LD::off_hfm,
+            LD::off_hd, LD::off_fn, LD::off_cp, LD::off_af};
 }
 struct RowsVariant {
     int kpc, h0c, h1c, g_big, njf;
     bool hasnum;
     bool unf;                             // big fields as raw split-f16 rows, projected on the matrix pipe (k_rows_chain.h, UNF)
-    const void* fn;
-    const void* fn_many;
-    const void* fn_one;
-    RowsLaunchFn launch;
-    RowsLaunchFn launch_one;
-    RowsLaunchManyFn launch_many;
-    int image_floats, ss, rb;
+    RowsKernel fn;                        // looped
+    RowsManyKernel fn_many;
+    RowsKernel fn_one;                    // one task per wave (k_rows_chain1): every one-batch launch up to V2J1_MAX_TASKS tasks, the joint1 family's threshold
+    RowsLayout ld;
 };
-#define ROWS_VARIANT_X(KPC, H0C, H1C, G_BIG, NJF, HASNUM, UNF)                                                                          \
-    {KPC, H0C, H1C, G_BIG, NJF, HASNUM, UNF, reinterpret_cast<const void*>(&k_rows_chain<KPC, H0C, H1C, G_BIG, NJF, HASNUM, RC_WAVES, UNF>),   \
-     reinterpret_cast<const void*>(&k_rows_chain_many<KPC, H0C, H1C, G_BIG, NJF, HASNUM, RC_WAVES, UNF>),                               \
-     reinterpret_cast<const void*>(&k_rows_chain1<KPC, H0C, H1C, G_BIG, NJF, HASNUM, RC_WAVES, UNF>),                                   \
-     &rows_launch<KPC, H0C, H1C, G_BIG, NJF, HASNUM, UNF>, &rows_launch_one<KPC, H0C, H1C, G_BIG, NJF, HASNUM, UNF>,                         \
-     &rows_launch_many<KPC, H0C, H1C, G_BIG, NJF, HASNUM, UNF>,                                                                          \
-     RowsLds<KPC, H0C, H1C, HASNUM, UNF>::total_pad, RowsLds<KPC, H0C, H1C, HASNUM, UNF>::SS, RowsLds<KPC, H0C, H1C, HASNUM, UNF>::RB}
+#define ROWS_VARIANT_X(KPC, H0C, H1C, G_BIG, NJF, HASNUM, UNF)                                                                   \
+    {KPC, H0C, H1C, G_BIG, NJF, HASNUM, UNF, &k_rows_chain<KPC, H0C, H1C, G_BIG, NJF, HASNUM, RC_WAVES, UNF>,                    \
+     &k_rows_chain_many<KPC, H0C, H1C, G_BIG, NJF, HASNUM, RC_WAVES, UNF>, &k_rows_chain1<KPC, H0C, H1C, G_BIG, NJF, HASNUM, RC_WAVES, UNF>, \
+     rows_layout<RowsLds<KPC, H0C, H1C, HASNUM, UNF>>()}
 #define ROWS_VARIANT(KPC, H0C, H1C, G_BIG, NJF, HASNUM) ROWS_VARIANT_X(KPC, H0C, H1C, G_BIG, NJF, HASNUM, false)
 const RowsVariant kRowsVariants[] = {
     ROWS_VARIANT_X(4, 2, 1, 2, 2, true, true),   // DeepFM_v2.py as written, big fields unfolded (raw split rows + MFMA projection)
@@ -65,14 +46,13 @@ int pull(std::vector<float>& dst, const float* src, size_t n) {
     return SPRK_OK;
 }
 int rows_finish(sprk_engine* h, const RowsVariant& rv, const std::vector<float>& image, size_t small_floats) {
-    SPRK_TRY(dev_alloc(h, &h->rows_image, (size_t)rv.image_floats * sizeof(float)));
-    HIP_TRY(hipMemcpy(h->rows_image, image.data(), (size_t)rv.image_floats * sizeof(float), hipMemcpyHostToDevice));
-    h->rows_lds_bytes = ((size_t)rv.image_floats + RC_WAVES * 256 + small_floats) * sizeof(float);
+    SPRK_TRY(dev_alloc(h, &h->rows_image, (size_t)rv.ld.image_floats * sizeof(float)));
+    HIP_TRY(hipMemcpy(h->rows_image, image.data(), (size_t)rv.ld.image_floats * sizeof(float), hipMemcpyHostToDevice));
+    h->rows_lds_bytes = ((size_t)rv.ld.image_floats + RC_WAVES * 256 + small_floats) * sizeof(float);
     if (h->rows_lds_bytes > 160 * 1024) return fail(SPRK_EINVAL, "rows chain needs %zu bytes of LDS", h->rows_lds_bytes);
-    HIP_TRY(hipFuncSetAttribute(rv.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->rows_lds_bytes));
-    HIP_TRY(hipFuncSetAttribute(rv.fn_many, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->rows_lds_bytes));
-    HIP_TRY(hipFuncSetAttribute(rv.fn_one, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->rows_lds_bytes));
-    h->rows_one = true;
+    SPRK_TRY(set_max_lds(rv.fn, h->rows_lds_bytes));
+    SPRK_TRY(set_max_lds(rv.fn_many, h->rows_lds_bytes));
+    SPRK_TRY(set_max_lds(rv.fn_one, h->rows_lds_bytes));
     HIP_TRY(hipDeviceSynchronize());
     return SPRK_OK;
 }
@@ -100,16 +80,10 @@ int setup_rows_v2(sprk_engine* h, bool allow_unf = true) {
         if (vu >= 0) {
             std::vector<AbsmaxJob> jobs;
             for (int b = 0; b < nbig; ++b) jobs.push_back({a.table[big[b]], (long long)a.emb_vocab[big[b]] + 1, Dp, Dp, 1024, 0});
-            float mx = 0.f;
-            SPRK_TRY(device_absmax(jobs, &mx, 1));
-            bool ok = mx < 3.0e38f;
-            for (int b = 0; ok && b < nbig; ++b) {
-                bool wide = false;
-                SPRK_TRY(wide_dynamic_range(a.table[big[b]], (long long)a.emb_vocab[big[b]] + 1, Dp, Dp, mx, &wide));
-                if (wide) ok = false;                              // an outlier row: its neighbours' lo halves would be subnormal
-            }
-            if (ok) {
-                p_scale = pow2_scale(mx);
+            float e_scale = 0.f;
+            SPRK_TRY(static_scale(jobs, &e_scale));              // (refused, e.g. an outlier row: the folded rows)
+            if (e_scale != 0.f) {
+                p_scale = e_scale;
                 variant = vu;
             }
         }
@@ -139,13 +113,13 @@ int setup_rows_v2(sprk_engine* h, bool allow_unf = true) {
     size_t small_floats = 0;
     for (int f = 0; f < nsm; ++f) {
         r.s_col[f] = a.emb_col[sm[f]]; r.s_vocab[f] = a.emb_vocab[sm[f]]; r.s_off[f] = (int)small_floats;
-        small_floats += ((size_t)a.emb_vocab[sm[f]] + 1) * rv.ss;
+        small_floats += ((size_t)a.emb_vocab[sm[f]] + 1) * rv.ld.ss;
     }
     small_floats = (small_floats + 255) & ~(size_t)255;
-    SPRK_TRY(table_alloc(h, &h->rows_tab, big_rows * rv.rb + 64));
-    HIP_TRY(hipMemset(h->rows_tab, 0, big_rows * rv.rb + 64));
+    SPRK_TRY(table_alloc(h, &h->rows_tab, big_rows * rv.ld.rb + 64));
+    HIP_TRY(hipMemset(h->rows_tab, 0, big_rows * rv.ld.rb + 64));
     SPRK_TRY(dev_alloc(h, &h->rows_scal, big_rows * sizeof(float) + 16));
-    h->derived_bytes += big_rows * rv.rb + big_rows * sizeof(float);
+    h->derived_bytes += big_rows * rv.ld.rb + big_rows * sizeof(float);
     if (small_floats) {
         SPRK_TRY(dev_alloc(h, &h->rows_small, small_floats * sizeof(float)));
         HIP_TRY(hipMemset(h->rows_small, 0, small_floats * sizeof(float)));
@@ -162,7 +136,7 @@ int setup_rows_v2(sprk_engine* h, bool allow_unf = true) {
     std::vector<std::vector<float>> lin(nbig), cst(nbig);
     for (int b = 0; b < nbig; ++b) {
         if (!unf) {
-            build(big[b], h->rows_tab + (size_t)r.big_rowbase[b] * (rv.rb / 4), rv.rb / 4, h->rows_scal + r.big_scal[b]);
+            build(big[b], h->rows_tab + (size_t)r.big_rowbase[b] * (rv.ld.rb / 4), rv.ld.rb / 4, h->rows_scal + r.big_scal[b]);
             continue;
         }
         const int g = big[b];
@@ -188,7 +162,7 @@ int setup_rows_v2(sprk_engine* h, bool allow_unf = true) {
         SPRK_TRY(pull(lin[b], d_out.p, (size_t)Dp * W));
         SPRK_TRY(pull(cst[b], d_out.p + (size_t)Dp * W, W));
     }
-    for (int f = 0; f < nsm; ++f) build(sm[f], h->rows_small + r.s_off[f], rv.ss, nullptr);
+    for (int f = 0; f < nsm; ++f) build(sm[f], h->rows_small + r.s_off[f], rv.ld.ss, nullptr);
     HIP_TRY(hipGetLastError());
     // weight image (host): Wn, bn, M = W0[:, num block] Wn, c0 = b0 + W0[:, num block] bn, W1, b1, hfm, hd, fn
     std::vector<float> Wn, bn, W0, b0, W1, b1, hfm, hd, fnw;
@@ -196,69 +170,51 @@ int setup_rows_v2(sprk_engine* h, bool allow_unf = true) {
     if ((rc = pull(Wn, a.Wp[G], (size_t)KP * a.ldp_num)) || (rc = pull(bn, a.bp[G], KP)) || (rc = pull(W0, a.W0, (size_t)H0 * d0.ldw)) ||
         (rc = pull(b0, a.b0, H0)) || (rc = pull(W1, a.W1, (size_t)H1 * d1.ldw)) || (rc = pull(b1, a.b1, H1)) ||
         (rc = pull(hfm, a.hfm, a.n_hfm)) || (rc = pull(hd, a.hdeep, a.n_hdeep)) || (rc = pull(fnw, a.fo_num_w, a.n_num))) return rc;
-    std::vector<float> img(rv.image_floats, 0.f);
-    const int SN = 12, S1 = H0 + 4;
-    int off = 0;
-    const int off_wn = off; off += KP * SN;
-    const int off_bn = off; off += KP;
-    const int off_m = off; off += H0 * SN;
-    const int off_c0 = off; off += H0;
-    const int off_w1 = off; off += H1 * S1;
-    const int off_b1 = off; off += H1;
-    const int off_hfm = off; off += KP;
-    const int off_hd = off; off += H1;
-    const int off_fn = off; off += 8;
-    const int off_cp = off; if (unf) off += KP;
-    const int off_af = (off + 3) & ~3; if (unf) off = off_af + (KP + H0) / 16 * 2 * 256;
-    if (off > rv.image_floats) return fail(SPRK_EINVAL, "rows image layout mismatch");
+    std::vector<float> img(rv.ld.image_floats, 0.f);
+    const RowsLayout& L = rv.ld;
+    const int SN = L.sn, S1 = L.s1;
     for (int n = 0; n < KP; ++n) {
-        for (int k = 0; k < a.n_num && k < 8; ++k) img[off_wn + n * SN + k] = Wn[(size_t)n * a.ldp_num + k];
-        img[off_bn + n] = bn[n];
+        for (int k = 0; k < a.n_num && k < 8; ++k) img[L.off_wn + n * SN + k] = Wn[(size_t)n * a.ldp_num + k];
+        img[L.off_bn + n] = bn[n];
     }
     for (int m = 0; m < H0; ++m) {
         const float* w = &W0[(size_t)m * d0.ldw + (size_t)G * KP];
         for (int k = 0; k < a.n_num && k < 8; ++k) {
             double acc = 0.0;
             for (int n = 0; n < KP; ++n) acc += (double)w[n] * (double)Wn[(size_t)n * a.ldp_num + k];
-            img[off_m + m * SN + k] = (float)acc;
+            img[L.off_m + m * SN + k] = (float)acc;
         }
         double c = b0[m];
         for (int n = 0; n < KP; ++n) c += (double)w[n] * (double)bn[n];
-        img[off_c0 + m] = (float)c;
+        img[L.off_c0 + m] = (float)c;
     }
     for (int n = 0; n < H1; ++n) {
-        for (int k = 0; k < H0; ++k) img[off_w1 + n * S1 + k] = W1[(size_t)n * d1.ldw + k];
-        img[off_b1 + n] = b1[n];
+        for (int k = 0; k < H0; ++k) img[L.off_w1 + n * S1 + k] = W1[(size_t)n * d1.ldw + k];
+        img[L.off_b1 + n] = b1[n];
     }
-    for (int n = 0; n < a.n_hfm && n < KP; ++n) img[off_hfm + n] = hfm[n];
-    for (int n = 0; n < a.n_hdeep && n < H1; ++n) img[off_hd + n] = hd[n];
-    for (int k = 0; k < a.n_num && k < 8; ++k) img[off_fn + k] = a.h0w * fnw[k];
+    for (int n = 0; n < a.n_hfm && n < KP; ++n) img[L.off_hfm + n] = hfm[n];
+    for (int n = 0; n < a.n_hdeep && n < H1; ++n) img[L.off_hd + n] = hd[n];
+    for (int k = 0; k < a.n_num && k < 8; ++k) img[L.off_fn + k] = a.h0w * fnw[k];
     r.unscale = 1.f;
     if (unf) {
         const int W = KP + H0;
-        float amax = 0.f;
+        std::vector<float> all;
         for (int b = 0; b < nbig; ++b) {
-            for (float v : lin[b]) amax = absmax_nan(amax, v);
-            for (int n = 0; n < KP; ++n) img[off_cp + n] += cst[b][n];
-            for (int m = 0; m < H0; ++m) img[off_c0 + m] += cst[b][KP + m];
+            all.insert(all.end(), lin[b].begin(), lin[b].end());
+            for (int n = 0; n < KP; ++n) img[L.off_cp + n] += cst[b][n];
+            for (int m = 0; m < H0; ++m) img[L.off_c0 + m] += cst[b][KP + m];
         }
         // non-finite projection weights, or an outlier among them (the others' lo halves would be subnormal): like every other static-scale
         // site, keep the f32 form -- here the folded rows {P | W0^T P}, built by the same function once the raw-row tables are released
-        bool refuse = !(amax < 3.0e38f);
-        if (!refuse) {
-            std::vector<float> all;
-            for (int b = 0; b < nbig; ++b) all.insert(all.end(), lin[b].begin(), lin[b].end());
-            refuse = wide_dynamic_range_host(all.data(), all.size(), amax);
-        }
-        if (refuse) {
+        const float w_scale = static_scale_host(all.data(), all.size());
+        if (w_scale == 0.f) {
             HIP_TRY(hipDeviceSynchronize());
             dev_free(h, h->rows_tab); dev_free(h, h->rows_scal); dev_free(h, h->rows_small);
             h->rows_tab = nullptr; h->rows_scal = nullptr; h->rows_small = nullptr;
-            h->derived_bytes -= big_rows * rv.rb + big_rows * sizeof(float);
+            h->derived_bytes -= big_rows * rv.ld.rb + big_rows * sizeof(float);
             return setup_rows_v2(h, false);
         }
-        const float w_scale = pow2_scale(amax);
-        _Float16* fh = reinterpret_cast<_Float16*>(&img[off_af]);
+        _Float16* fh = reinterpret_cast<_Float16*>(&img[L.off_af]);
         for (int nb = 0; nb < W / 16; ++nb)
             for (int ln = 0; ln < 64; ++ln)
                 for (int e = 0; e < 8; ++e) {
@@ -305,9 +261,9 @@ int setup_rows_ncf(sprk_engine* h) {
         rows_total += (size_t)sg.vocab + 1;
     }
     if (rows_total >= ((size_t)1 << 31)) return SPRK_OK;
-    SPRK_TRY(table_alloc(h, &h->rows_tab, rows_total * rv.rb + 64));
-    HIP_TRY(hipMemset(h->rows_tab, 0, rows_total * rv.rb + 64));
-    h->derived_bytes += rows_total * rv.rb;
+    SPRK_TRY(table_alloc(h, &h->rows_tab, rows_total * rv.ld.rb + 64));
+    HIP_TRY(hipMemset(h->rows_tab, 0, rows_total * rv.ld.rb + 64));
+    h->derived_bytes += rows_total * rv.ld.rb;
     const float* W0 = (const float*)h->slot_ptr[o0.w_slot];
     for (int b = 0; b < 2; ++b) {
         const sprk_seg& sg = p.segs[b];
@@ -317,22 +273,22 @@ int setup_rows_ncf(sprk_engine* h) {
         hipLaunchKernelGGL(k_rows_build, dim3((unsigned)blocks), dim3(256), 0, 0, (const float*)h->slot_ptr[sg.slot], sg.row_stride, rows,
                            (const float*)nullptr, 0, (const float*)nullptr, 0, W0, o0.ldw, sg.dst - o0.src_off, H0, 4 * sg.count,
                            (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, 0.f,
-                           h->rows_tab + (size_t)r.big_rowbase[b] * (rv.rb / 4), rv.rb / 4, (float*)nullptr, 0);
+                           h->rows_tab + (size_t)r.big_rowbase[b] * (rv.ld.rb / 4), rv.ld.rb / 4, (float*)nullptr, 0);
     }
     HIP_TRY(hipGetLastError());
     std::vector<float> b0, W1, b1, hd;
     int rc;
     if ((rc = pull(b0, (const float*)h->slot_ptr[o0.b_slot], H0)) || (rc = pull(W1, (const float*)h->slot_ptr[o1.w_slot], (size_t)H1 * o1.ldw)) ||
         (rc = pull(b1, (const float*)h->slot_ptr[o1.b_slot], H1)) || (rc = pull(hd, (const float*)h->slot_ptr[tp.w_slot], tp.len))) return rc;
-    std::vector<float> img(rv.image_floats, 0.f);
-    const int S1 = H0 + 4;
-    const int off_c0 = 0, off_w1 = off_c0 + H0, off_b1 = off_w1 + H1 * S1, off_hfm = off_b1 + H1, off_hd = off_hfm + 0;
-    for (int m = 0; m < H0; ++m) img[off_c0 + m] = b0[m];
+    std::vector<float> img(rv.ld.image_floats, 0.f);
+    const RowsLayout& L = rv.ld;
+    const int S1 = L.s1;
+    for (int m = 0; m < H0; ++m) img[L.off_c0 + m] = b0[m];
     for (int n = 0; n < H1; ++n) {
-        for (int k = 0; k < H0; ++k) img[off_w1 + n * S1 + k] = W1[(size_t)n * o1.ldw + k];
-        img[off_b1 + n] = b1[n];
+        for (int k = 0; k < H0; ++k) img[L.off_w1 + n * S1 + k] = W1[(size_t)n * o1.ldw + k];
+        img[L.off_b1 + n] = b1[n];
     }
-    for (int n = 0; n < tp.len; ++n) img[off_hd + n] = hd[n];
+    for (int n = 0; n < tp.len; ++n) img[L.off_hd + n] = hd[n];
     r.rows = h->rows_tab; r.scal = nullptr; r.small = nullptr; r.small_floats = 0;
     r.bias = p.head_bias;
     if ((rc = rows_finish(h, rv, img, 0))) return rc;

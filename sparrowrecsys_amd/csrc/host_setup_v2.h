@@ -6,15 +6,11 @@ constexpr int V2_WAVES = 8;
 struct V2Variant {
     int g_emb, kpc, h0c, h1c;
     size_t lds_bytes;                 // the packed image + a staging slot per wave
-    void (*pack)(const V2Args&, float*);
+    void (*pack)(const V2Args, float*);
 };
-template <int G_EMB, int DV, int KPC, int H0C, int H1C, bool FOLD>
-void v2_pack(const V2Args& a, float* image) {
-    hipLaunchKernelGGL((k_v2_pack_image<G_EMB, DV, KPC, H0C, H1C, FOLD>), dim3(1), dim3(256), 0, 0, a, image);
-}
 #define V2_LDS(G_EMB, DV, KPC, H0C, H1C, FOLD) \
     (sizeof(float) * (V2Lds<G_EMB, DV, KPC, H0C, H1C, FOLD>::total_pad + V2_WAVES * V2Lds<G_EMB, DV, KPC, H0C, H1C, FOLD>::stage_floats))
-#define V2_VARIANT(G_EMB) {G_EMB, 1, 2, 1, V2_LDS(G_EMB, 4, 1, 2, 1, true), &v2_pack<G_EMB, 4, 1, 2, 1, true>}
+#define V2_VARIANT(G_EMB) {G_EMB, 1, 2, 1, V2_LDS(G_EMB, 4, 1, 2, 1, true), &k_v2_pack_image<G_EMB, 4, 1, 2, 1, true>}
 const V2Variant kV2Variants[] = {
     V2_VARIANT(6),    // BASELINE config 2: 6 fields, projection 16 (folded into the tables), deep 32-16
     V2_VARIANT(4),    // 4 fields (config 4 gathers 128-B projected rows instead of 256-B raw ones)
@@ -22,31 +18,14 @@ const V2Variant kV2Variants[] = {
 };
 
 // ---- dispatch table for k_deepfm_v2_joint<G_BIG, NJF, KPC, H0C, H1C, WAVES> ----
-typedef void (*V2JLaunchFn)(const V2JRun&, const int*, const float*, float*, int, int*, const float*, int, size_t, hipStream_t);
-typedef void (*V2JLaunchManyFn)(const V2JRun&, const V2JMany&, int, int*, const float*, int, size_t, hipStream_t);
-template <int G_BIG, int NJF, bool HALF>
-void v2j_launch(const V2JRun& a, const int* ids, const float* dense, float* out, int B, int* err, const float* image,
-                int grid, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((k_deepfm_v2_joint<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>), dim3(grid), dim3(V2_WAVES * 64), lds, st,
-                       a, ids, dense, out, B, err, image);
-}
-template <int G_BIG, int NJF, bool HALF>
-void v2j_launch_many(const V2JRun& a, const V2JMany& m, int B, int* err, const float* image, int grid, size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((k_deepfm_v2_joint_many<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>), dim3(grid), dim3(V2_WAVES * 64), lds, st,
-                       a, m, B, err, image);
-}
 struct V2JVariant {
     int g_big, njf, kpc;
     bool half;                            // big fields on split-f16 MFMA
-    const void* fn;
-    const void* fn_many;
-    V2JLaunchFn launch;
-    V2JLaunchManyFn launch_many;
+    V2JKernel fn;
+    V2JManyKernel fn_many;
 };
 #define V2J_VARIANT(G_BIG, NJF, HALF) \
-    {G_BIG, NJF, 1, HALF, reinterpret_cast<const void*>(&k_deepfm_v2_joint<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>), \
-     reinterpret_cast<const void*>(&k_deepfm_v2_joint_many<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>), &v2j_launch<G_BIG, NJF, HALF>, \
-     &v2j_launch_many<G_BIG, NJF, HALF>}
+    {G_BIG, NJF, 1, HALF, &k_deepfm_v2_joint<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>, &k_deepfm_v2_joint_many<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>}
 #define V2J_BOTH(G_BIG, NJF) V2J_VARIANT(G_BIG, NJF, true), V2J_VARIANT(G_BIG, NJF, false)
 const V2JVariant kV2JVariants[] = {
     V2J_BOTH(3, 3),    // BASELINE config 2: movieId, userId, userRatedMovie1 + a joint table of the three genre fields
@@ -54,18 +33,11 @@ const V2JVariant kV2JVariants[] = {
     V2J_BOTH(3, 2), V2J_BOTH(3, 1), V2J_BOTH(2, 3), V2J_BOTH(2, 1), V2J_BOTH(1, 3), V2J_BOTH(1, 2), V2J_BOTH(1, 1),
 };
 
-// k_deepfm_v2_joint1<G_BIG, NJF>: the one-task-per-wave shape of the split-f16 joint kernel (k_chain_v2j1.h)
-typedef void (*V2J1LaunchFn)(const V2JRun&, const int*, const float*, float*, int, int*, const float*, int, size_t, hipStream_t);
-template <int G_BIG, int NJF, bool HOIST>
-void v2j1_launch(const V2JRun& a, const int* ids, const float* dense, float* out, int B, int* err, const float* image, int grid,
-                 size_t lds, hipStream_t st) {
-    hipLaunchKernelGGL((k_deepfm_v2_joint1<G_BIG, NJF, HOIST>), dim3(grid), dim3(V2J1_WAVES_OF(HOIST, G_BIG) * 64), lds, st, a, ids, dense, out, B, err, image);
-}
-// (fn_h / launch_h: the HOIST form, for tables larger than the Infinity Cache)
-struct V2J1Variant { int g_big, njf; const void* fn; V2J1LaunchFn launch; int image_floats; const void* fn_h; V2J1LaunchFn launch_h; };
+// k_deepfm_v2_joint1<G_BIG, NJF, HOIST>: the one-task-per-wave shape of the split-f16 joint kernel (k_chain_v2j1.h)
+// (fn[1]: the HOIST form, for tables larger than the Infinity Cache)
+struct V2J1Variant { int g_big, njf; V2JKernel fn[2]; int image_floats; };
 #define V2J1_VARIANT(G_BIG, NJF) \
-    {G_BIG, NJF, reinterpret_cast<const void*>(&k_deepfm_v2_joint1<G_BIG, NJF, false>), &v2j1_launch<G_BIG, NJF, false>, V2J1Lds<G_BIG>::total_pad, \
-     reinterpret_cast<const void*>(&k_deepfm_v2_joint1<G_BIG, NJF, true>), &v2j1_launch<G_BIG, NJF, true>}
+    {G_BIG, NJF, {&k_deepfm_v2_joint1<G_BIG, NJF, false>, &k_deepfm_v2_joint1<G_BIG, NJF, true>}, V2J1Lds<G_BIG>::total_pad}
 const V2J1Variant kV2J1Variants[] = {
     V2J1_VARIANT(3, 3), V2J1_VARIANT(2, 2), V2J1_VARIANT(3, 2), V2J1_VARIANT(3, 1), V2J1_VARIANT(2, 3), V2J1_VARIANT(2, 1),
     V2J1_VARIANT(1, 3), V2J1_VARIANT(1, 2), V2J1_VARIANT(1, 1),
@@ -225,30 +197,14 @@ int setup_v2_joint(sprk_engine* h) {
     bool half = h->tune.v2_half;
     float p_scale = 1.f, w_scale = 1.f;
     if (half) {
-        std::vector<AbsmaxJob> jobs;
+        std::vector<AbsmaxJob> rows_jobs;
         for (int b = 0; b < nbig; ++b) {
             const long long rows = (long long)h->v2run.vocab[big[b]] + 1;
-            jobs.push_back({h->v2_folded + (size_t)h->v2run.rowbase[big[b]] * (KP + 16), rows, KP + 16, KP, absmax_grid(rows * KP, 8192), 0});
+            rows_jobs.push_back({h->v2_folded + (size_t)h->v2run.rowbase[big[b]] * (KP + 16), rows, KP + 16, KP, absmax_grid(rows * KP, 8192), 0});
         }
-        jobs.push_back({h->v2.W0, (long long)H0, (G + 1) * KP, (G + 1) * KP, 8, 1});
-        float mx[2];
-        SPRK_TRY(device_absmax(jobs, mx, 2));
-        for (int i = 0; i < 2; ++i) {
-            if (!(mx[i] < 3.0e38f)) { half = false; break; }     // NaN / Inf in the weights: keep the f32 path
-            (i == 0 ? p_scale : w_scale) = pow2_scale(mx[i]);
-        }
-        // an outlier row next to ordinary ones: the ordinary rows' lo halves would be subnormal -> keep the f32 variant
-        for (int b = 0; half && b < nbig; ++b) {
-            bool wide = false;
-            SPRK_TRY(wide_dynamic_range(h->v2_folded + (size_t)h->v2run.rowbase[big[b]] * (KP + 16),
-                                        (long long)h->v2run.vocab[big[b]] + 1, KP + 16, KP, mx[0], &wide));
-            if (wide) half = false;
-        }
-        if (half) {
-            bool wide = false;
-            SPRK_TRY(wide_dynamic_range(h->v2.W0, (long long)H0, (G + 1) * KP, (G + 1) * KP, mx[1], &wide));
-            if (wide) half = false;
-        }
+        SPRK_TRY(static_scale(rows_jobs, &p_scale));
+        if (p_scale != 0.f) SPRK_TRY(static_scale({{h->v2.W0, (long long)H0, (G + 1) * KP, (G + 1) * KP, 8, 0}}, &w_scale));
+        if (p_scale == 0.f || w_scale == 0.f) { half = false; p_scale = w_scale = 1.f; }   // refused: keep the f32 variant
     }
     int variant = -1;
     for (size_t v = 0; v < sizeof(kV2JVariants) / sizeof(kV2JVariants[0]); ++v)
@@ -309,8 +265,8 @@ int setup_v2_joint(sprk_engine* h) {
         r.tab0 = h->v2j_big;
     }
     h->v2j_lds_bytes = vv.lds_bytes + small_floats * sizeof(float);
-    HIP_TRY(hipFuncSetAttribute(kV2JVariants[variant].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->v2j_lds_bytes));
-    HIP_TRY(hipFuncSetAttribute(kV2JVariants[variant].fn_many, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->v2j_lds_bytes));
+    SPRK_TRY(set_max_lds(kV2JVariants[variant].fn, h->v2j_lds_bytes));
+    SPRK_TRY(set_max_lds(kV2JVariants[variant].fn_many, h->v2j_lds_bytes));
     h->v2j_variant = variant;
     // the one-task-per-wave shape for strict one-batch launches (k_chain_v2j1.h); SPRK_V2J_ONE=0: looped kernel only
     if (half && h->tune.v2j_one) {
@@ -322,10 +278,11 @@ int setup_v2_joint(sprk_engine* h) {
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipDeviceSynchronize());
             // rows that cannot all sit in the 256 MB Infinity Cache come from HBM: the form that reads its weight fragments first
-            h->v2j1_hoist = h->tune.v2j1_hoist >= 0 ? h->tune.v2j1_hoist != 0 : h->derived_bytes > ((size_t)256 << 20);
-            h->v2j1_waves = V2J1_WAVES_OF(h->v2j1_hoist, nbig);
+            const bool hoist = h->tune.v2j1_hoist >= 0 ? h->tune.v2j1_hoist != 0 : h->derived_bytes > ((size_t)256 << 20);
+            h->v2j1_kernel = ov.fn[hoist];
+            h->v2j1_waves = V2J1_WAVES_OF(hoist, nbig);
             h->v2j1_lds_bytes = ((size_t)ov.image_floats + small_floats + (size_t)h->v2j1_waves * 256) * sizeof(float);
-            HIP_TRY(hipFuncSetAttribute(h->v2j1_hoist ? ov.fn_h : ov.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->v2j1_lds_bytes));
+            SPRK_TRY(set_max_lds(h->v2j1_kernel, h->v2j1_lds_bytes));
         }
     }
     return SPRK_OK;
@@ -368,7 +325,7 @@ int setup_v2_fold(sprk_engine* h) {
     h->derived_bytes += rows_total * (KP + 16) * sizeof(float);   // (after the joint set-up: its HOIST choice counts only the split rows)
     SPRK_TRY(dev_alloc(h, &h->v2_image, vv.lds_bytes));
     HIP_TRY(hipMemset(h->v2_image, 0, vv.lds_bytes));
-    vv.pack(h->v2, h->v2_image);
+    hipLaunchKernelGGL(vv.pack, dim3(1), dim3(256), 0, 0, h->v2, h->v2_image);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return SPRK_OK;

@@ -354,12 +354,12 @@ __device__ __forceinline__ void v1_body(const V1Run& A, const int* __restrict__ 
             for (int nb = 0; nb < H0C; ++nb) acc[nb] = zero;
 #pragma unroll
             for (int b = 0; b < PC; ++b) {
-                din_f16x8 bh, bl;
+                f16x8 bh, bl;
                 dyn_split8(ec[2 * b], ec[2 * b + 1], scale, bh, bl);
 #pragma unroll
                 for (int nb = 0; nb < H0C; ++nb) {
-                    const din_f16x8 ah = __builtin_bit_cast(din_f16x8, ld4(smem + wfo + ((nb * PC + b) * 2 + 0) * 256));
-                    const din_f16x8 al = __builtin_bit_cast(din_f16x8, ld4(smem + wfo + ((nb * PC + b) * 2 + 1) * 256));
+                    const f16x8 ah = __builtin_bit_cast(f16x8, ld4(smem + wfo + ((nb * PC + b) * 2 + 0) * 256));
+                    const f16x8 al = __builtin_bit_cast(f16x8, ld4(smem + wfo + ((nb * PC + b) * 2 + 1) * 256));
                     acc[nb] = mfma_f16(ah, bh, acc[nb]);
                     acc[nb] = mfma_f16(ah, bl, acc[nb]);
                     acc[nb] = mfma_f16(al, bh, acc[nb]);
@@ -403,12 +403,12 @@ __device__ __forceinline__ void v1_body(const V1Run& A, const int* __restrict__ 
             asm volatile("" : "+v"(wfo));
 #pragma unroll
             for (int b = 0; b < H0C / 2; ++b) {
-                din_f16x8 bh, bl;
+                f16x8 bh, bl;
                 dyn_split8(h0[2 * b], h0[2 * b + 1], scale, bh, bl);
 #pragma unroll
                 for (int n1 = 0; n1 < H1C; ++n1) {
-                    const din_f16x8 ah = __builtin_bit_cast(din_f16x8, ld4(smem + wfo + ((n1 * (H0C / 2) + b) * 2 + 0) * 256));
-                    const din_f16x8 al = __builtin_bit_cast(din_f16x8, ld4(smem + wfo + ((n1 * (H0C / 2) + b) * 2 + 1) * 256));
+                    const f16x8 ah = __builtin_bit_cast(f16x8, ld4(smem + wfo + ((n1 * (H0C / 2) + b) * 2 + 0) * 256));
+                    const f16x8 al = __builtin_bit_cast(f16x8, ld4(smem + wfo + ((n1 * (H0C / 2) + b) * 2 + 1) * 256));
                     acc[n1] = mfma_f16(ah, bh, acc[n1]);
                     acc[n1] = mfma_f16(ah, bl, acc[n1]);
                     acc[n1] = mfma_f16(al, bh, acc[n1]);

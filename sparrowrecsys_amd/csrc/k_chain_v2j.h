@@ -72,9 +72,6 @@ struct V2JMany {
     int ntpb;                             // tasks per batch = ceil(B / 16)
 };
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
 // x*scale -> (hi, lo) halfs with hi + lo == x*scale to 22 bits
 __device__ __forceinline__ void split_half4(f32x4 w, float scale, f16x4& hi, f16x4& lo) {
 #pragma unroll

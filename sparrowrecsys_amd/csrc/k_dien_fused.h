@@ -71,9 +71,9 @@ __global__ __launch_bounds__(DNF_WAVES * 64, 4) void k_dien_fused(const DienRun 
 
     const float* fl = W + 4 * lane;                               // this lane's 16 bytes of a fragment half
     auto vec = [&](int v) { return ld4(W + FR::vec0 + v * 16 + 4 * q); };
-    auto mm = [&](int blk, din_f16x8 bh, din_f16x8 bl, f32x4 bias) __attribute__((always_inline)) {
-        const din_f16x8 ah = __builtin_bit_cast(din_f16x8, ld4(fl + blk * 512));
-        const din_f16x8 al = __builtin_bit_cast(din_f16x8, ld4(fl + blk * 512 + 256));
+    auto mm = [&](int blk, f16x8 bh, f16x8 bl, f32x4 bias) __attribute__((always_inline)) {
+        const f16x8 ah = __builtin_bit_cast(f16x8, ld4(fl + blk * 512));
+        const f16x8 al = __builtin_bit_cast(f16x8, ld4(fl + blk * 512 + 256));
         f32x4 acc = mfma_f16(al, bh, zero);
         acc = mfma_f16(ah, bl, acc);
         acc = mfma_f16(ah, bh, acc);
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(DNF_WAVES * 64, 4) void k_dien_fused(const DienRun 
         f32x4 x = qin ? ld4(A.table + (size_t)id * A.Dp + 4 * q) : zero;
         // one step of the recurrence (k_dien_seq_mfma's, statement for statement); every step but the last requests the next slot's row
         auto step_body = [&](const f32x4 xt, const bool live) __attribute__((always_inline)) {
-            din_f16x8 bh, bl;
+            f16x8 bh, bl;
             // ---- GRU step (reset_after); a masked slot (id 0) keeps the state and repeats the previous output ----
             {
                 dyn_split8(xt, h, s_xh, bh, bl);
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(DNF_WAVES * 64, 4) void k_dien_fused(const DienRun 
 #pragma unroll 1
         for (int t = 0; t + 1 < A.T; ++t) step(t, std::false_type{});
         // the tail's operands fly under the last step
-        din_f16x8 eh[LD::NBLK], el[LD::NBLK];
+        f16x8 eh[LD::NBLK], el[LD::NBLK];
         float xna, xnb;
         din_tail_unf_gather<LD>(TL, idv, q, bad, eh, el);
         {

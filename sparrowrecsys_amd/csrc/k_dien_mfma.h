@@ -170,9 +170,9 @@ __global__ __launch_bounds__(DM_WAVES * 64, 4) void k_dien_seq_mfma(const DienRu
     const float* fl = W + 4 * lane;                               // this lane's 16 bytes of a fragment half
     auto vec = [&](int v) { return ld4(W + FR::vec0 + v * 16 + 4 * q); };
     // block blk applied to the split operand (bh, bl): un-scaled, plus a bias vector
-    auto mm = [&](int blk, din_f16x8 bh, din_f16x8 bl, f32x4 bias) {
-        const din_f16x8 ah = __builtin_bit_cast(din_f16x8, ld4(fl + blk * 512));
-        const din_f16x8 al = __builtin_bit_cast(din_f16x8, ld4(fl + blk * 512 + 256));
+    auto mm = [&](int blk, f16x8 bh, f16x8 bl, f32x4 bias) {
+        const f16x8 ah = __builtin_bit_cast(f16x8, ld4(fl + blk * 512));
+        const f16x8 al = __builtin_bit_cast(f16x8, ld4(fl + blk * 512 + 256));
         f32x4 acc = mfma_f16(al, bh, zero);
         acc = mfma_f16(ah, bl, acc);
         acc = mfma_f16(ah, bh, acc);
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(DM_WAVES * 64, 4) void k_dien_seq_mfma(const DienRu
                 if (id < 0 || id >= A.vocab) { bad = true; id = 0; }
                 x = qin ? ld4(A.table + (size_t)id * A.Dp + 4 * q) : zero;
             }
-            din_f16x8 bh, bl;
+            f16x8 bh, bl;
             // ---- GRU step (reset_after); a masked slot (id 0) keeps the state and repeats the previous output ----
             {
                 dyn_split8(xt, h, s_xh, bh, bl);

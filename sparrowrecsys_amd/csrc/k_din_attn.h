@@ -146,12 +146,10 @@ __device__ __forceinline__ float row16_reduce_scatter(const float (&v)[EL], int 
 // (rows4_sum: k_chain_v2.h)
 
 // f16 MFMA over a lane's EL = 4 or 8 operand halfs (K = 16 or 32)
-typedef _Float16 din_f16x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 din_f16x8 __attribute__((ext_vector_type(8)));
-// (x0..x3 | y0..y3) * scale -> packed hi / lo halfs; defined in dyn_split.h (which follows this file and uses its typedefs)
-__device__ __forceinline__ void dyn_split8(f32x4 x, f32x4 y, float scale, din_f16x8& hi, din_f16x8& lo);
-__device__ __forceinline__ f32x4 mfma_f16(din_f16x4 a, din_f16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ f32x4 mfma_f16(din_f16x8 a, din_f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+// (x0..x3 | y0..y3) * scale -> packed hi / lo halfs; defined in dyn_split.h (which follows this file)
+__device__ __forceinline__ void dyn_split8(f32x4 x, f32x4 y, float scale, f16x8& hi, f16x8& lo);
+__device__ __forceinline__ f32x4 mfma_f16(f16x4 a, f16x4 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x16f16(a, b, c, 0, 0, 0); }
+__device__ __forceinline__ f32x4 mfma_f16(f16x8 a, f16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
 
 // d = a * f16(lo / hi half of the dword `packed`) + c in one VALU instruction (v_fma_mix_f32: per-source f32 / f16
 // selection; hipcc 7.2 emits v_cvt_f32_f16 + v_fma for fmaf(a, (float)half, c) here)
@@ -171,12 +169,12 @@ template <int KC>
 __device__ __forceinline__ void unpack_halfs(const f32x4* x, _Float16 __attribute__((ext_vector_type(4 * KC)))& hi,
                                              _Float16 __attribute__((ext_vector_type(4 * KC)))& lo) {
     if constexpr (KC == 2) {
-        hi = __builtin_bit_cast(din_f16x8, x[0]);
-        lo = __builtin_bit_cast(din_f16x8, x[1]);
+        hi = __builtin_bit_cast(f16x8, x[0]);
+        lo = __builtin_bit_cast(f16x8, x[1]);
     } else {
-        const din_f16x8 both = __builtin_bit_cast(din_f16x8, x[0]);
-        hi = din_f16x4{both[0], both[1], both[2], both[3]};
-        lo = din_f16x4{both[4], both[5], both[6], both[7]};
+        const f16x8 both = __builtin_bit_cast(f16x8, x[0]);
+        hi = f16x4{both[0], both[1], both[2], both[3]};
+        lo = f16x4{both[4], both[5], both[6], both[7]};
     }
 }
 

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(DC_WAVES * 64, 4) void k_din_attn_cols(const DinCol
         for (int k = 0; k < 4; ++k) {
             const f32x4 f = ld4(A.frag + ((nb * 4 + k) * 64 + lane) * 4);
             if constexpr (KC == 2) aW[nb][k] = __builtin_bit_cast(f16xe, f);
-            else { const din_f16x8 both = __builtin_bit_cast(din_f16x8, f); aW[nb][k] = f16xe{both[0], both[1], both[2], both[3]}; }
+            else { const f16x8 both = __builtin_bit_cast(f16x8, f); aW[nb][k] = f16xe{both[0], both[1], both[2], both[3]}; }
         }
     __builtin_amdgcn_s_waitcnt(0x0F70);                   // vmcnt(0): this wave's DMA pieces (and everything above) have landed
     __syncthreads();                                      // coefficient tables staged by every wave

@@ -424,12 +424,12 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if constexpr (KC == 2) aW[nb][k] = __builtin_bit_cast(f16xe, aWr[nb][k]);
-            else { const din_f16x8 both = __builtin_bit_cast(din_f16x8, aWr[nb][k]); aW[nb][k] = f16xe{both[0], both[1], both[2], both[3]}; }
+            else { const f16x8 both = __builtin_bit_cast(f16x8, aWr[nb][k]); aW[nb][k] = f16xe{both[0], both[1], both[2], both[3]}; }
         }
-    din_f16x8 eh[UNFK ? 2 : 1], el[UNFK ? 2 : 1];
+    f16x8 eh[UNFK ? 2 : 1], el[UNFK ? 2 : 1];
     if constexpr (UNFK && MB) {
 #pragma unroll
-        for (int u = 0; u < 2; ++u) { eh[u] = __builtin_bit_cast(din_f16x8, er[2 * u]); el[u] = __builtin_bit_cast(din_f16x8, er[2 * u + 1]); }
+        for (int u = 0; u < 2; ++u) { eh[u] = __builtin_bit_cast(f16x8, er[2 * u]); el[u] = __builtin_bit_cast(f16x8, er[2 * u + 1]); }
     }
     {
         f16xe chi, clo;
@@ -495,8 +495,8 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
                 if (u < A.n_unf) {                                // (wave-uniform)
 #pragma unroll
                     for (int nb = 0; nb < N0C; ++nb) {
-                        const din_f16x8 ah = __builtin_bit_cast(din_f16x8, ld4(wf + (u * N0C + nb) * 512));
-                        const din_f16x8 al = __builtin_bit_cast(din_f16x8, ld4(wf + (u * N0C + nb) * 512 + 256));
+                        const f16x8 ah = __builtin_bit_cast(f16x8, ld4(wf + (u * N0C + nb) * 512));
+                        const f16x8 al = __builtin_bit_cast(f16x8, ld4(wf + (u * N0C + nb) * 512 + 256));
                         f32x4 acc = mfma_f16(al, eh[u], zero);
                         acc = mfma_f16(ah, el[u], acc);
                         acc = mfma_f16(ah, eh[u], acc);
@@ -704,7 +704,7 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
             else
                 asm volatile("s_waitcnt vmcnt(%0)" :: "n"(4 * KC));
 #pragma unroll
-            for (int u = 0; u < (UNFK ? 2 : 0); ++u) { eh[u] = __builtin_bit_cast(din_f16x8, er[2 * u]); el[u] = __builtin_bit_cast(din_f16x8, er[2 * u + 1]); }
+            for (int u = 0; u < (UNFK ? 2 : 0); ++u) { eh[u] = __builtin_bit_cast(f16x8, er[2 * u]); el[u] = __builtin_bit_cast(f16x8, er[2 * u + 1]); }
             __builtin_amdgcn_s_barrier();
             step = 8;
         }
@@ -785,13 +785,13 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
             mx = rows4_max(mx);
             float scale, inv;
             dyn_scale(mx, A.inv_w0p_scale, scale, inv);
-            din_f16x8 bh, bl;
+            f16x8 bh, bl;
             dyn_split8(f32x4{xp[0], xp[1], xp[2], xp[3]}, f32x4{xp[4], xp[5], xp[6], xp[7]}, scale, bh, bl);
             const float* wf = img_s + IM::off_w0p + lane * 4;
 #pragma unroll
             for (int nb = 0; nb < N0C; ++nb) {
-                const din_f16x8 ah = __builtin_bit_cast(din_f16x8, ld4(wf + nb * 512));
-                const din_f16x8 al = __builtin_bit_cast(din_f16x8, ld4(wf + nb * 512 + 256));
+                const f16x8 ah = __builtin_bit_cast(f16x8, ld4(wf + nb * 512));
+                const f16x8 al = __builtin_bit_cast(f16x8, ld4(wf + nb * 512 + 256));
                 f32x4 acc = mfma_f16(al, bh, zero);
                 acc = mfma_f16(ah, bl, acc);
                 acc = mfma_f16(ah, bh, acc);
@@ -826,12 +826,12 @@ __global__ __launch_bounds__(DF_WAVES * 64, 2) void k_din_fused(const DinFusedRu
             const float* wf = img_s + IM::off_w1 + lane * 4;                 // this lane's 16 bytes inside a 1-KB fragment (k_dyn_pack_w: lane order)
 #pragma unroll
             for (int b = 0; b < N0C / 2; ++b) {
-                din_f16x8 bh, bl;
+                f16x8 bh, bl;
                 dyn_split8(z0[2 * b], z0[2 * b + 1], scale, bh, bl);
 #pragma unroll
                 for (int n1 = 0; n1 < N1C; ++n1) {
-                    const din_f16x8 ah = __builtin_bit_cast(din_f16x8, ld4(wf + ((n1 * (N0C / 2) + b) * 2 + 0) * 256));
-                    const din_f16x8 al = __builtin_bit_cast(din_f16x8, ld4(wf + ((n1 * (N0C / 2) + b) * 2 + 1) * 256));
+                    const f16x8 ah = __builtin_bit_cast(f16x8, ld4(wf + ((n1 * (N0C / 2) + b) * 2 + 0) * 256));
+                    const f16x8 al = __builtin_bit_cast(f16x8, ld4(wf + ((n1 * (N0C / 2) + b) * 2 + 1) * 256));
                     acc[n1] = mfma_f16(ah, bh, acc[n1]);
                     acc[n1] = mfma_f16(ah, bl, acc[n1]);
                     acc[n1] = mfma_f16(al, bh, acc[n1]);

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void k_din_tail_pack(const float* __restrict__
 // UNF: the raw split rows of the embedding columns, one 16 + 16 byte piece per K = 32 block and lane
 template <class LD>
 __device__ __forceinline__ void din_tail_unf_gather(const DinTailRun& A, const int (&idv)[DT_MAX_COLS], int q, bool& bad,
-                                                    din_f16x8 (&eh)[LD::NBLK], din_f16x8 (&el)[LD::NBLK]) {
+                                                    f16x8 (&eh)[LD::NBLK], f16x8 (&el)[LD::NBLK]) {
     constexpr int NBLK = LD::NBLK;
 #pragma unroll
     for (int pb = 0; pb < NBLK; ++pb) {
@@ -142,15 +142,15 @@ __device__ __forceinline__ void din_tail_unf_gather(const DinTailRun& A, const i
         bad |= have && !ok && id != -1;
         const char* row = reinterpret_cast<const char*>(tab) + (size_t)(ok ? id : voc) * (4 * LD::EPB) +
                           16 * (LD::EPB == 16 ? (q & 1) : q);
-        eh[pb] = *reinterpret_cast<const din_f16x8*>(row);           // (a missing id / an absent column: the all-zero row)
-        el[pb] = *reinterpret_cast<const din_f16x8*>(row + 2 * LD::EPB);
+        eh[pb] = *reinterpret_cast<const f16x8*>(row);           // (a missing id / an absent column: the all-zero row)
+        el[pb] = *reinterpret_cast<const f16x8*>(row + 2 * LD::EPB);
     }
 }
 
 // UNF: fc0's embedding part, z0 += W0e^T [rows] on the f16 matrix pipe
 template <class LD, int N0C>
-__device__ __forceinline__ void din_tail_unf_fc0(const DinTailRun& A, const float* S, int lane, const din_f16x8 (&eh)[LD::NBLK],
-                                                 const din_f16x8 (&el)[LD::NBLK], f32x4 (&z0)[N0C]) {
+__device__ __forceinline__ void din_tail_unf_fc0(const DinTailRun& A, const float* S, int lane, const f16x8 (&eh)[LD::NBLK],
+                                                 const f16x8 (&el)[LD::NBLK], f32x4 (&z0)[N0C]) {
     constexpr int NBLK = LD::NBLK;
     const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
     const float* wf = S + LD::off_w0e + 4 * lane;
@@ -158,8 +158,8 @@ __device__ __forceinline__ void din_tail_unf_fc0(const DinTailRun& A, const floa
     for (int pb = 0; pb < NBLK; ++pb)
 #pragma unroll
         for (int nb = 0; nb < N0C; ++nb) {
-            const din_f16x8 ah = __builtin_bit_cast(din_f16x8, ld4(wf + ((nb * NBLK + pb) * 2 + 0) * 256));
-            const din_f16x8 al = __builtin_bit_cast(din_f16x8, ld4(wf + ((nb * NBLK + pb) * 2 + 1) * 256));
+            const f16x8 ah = __builtin_bit_cast(f16x8, ld4(wf + ((nb * NBLK + pb) * 2 + 0) * 256));
+            const f16x8 al = __builtin_bit_cast(f16x8, ld4(wf + ((nb * NBLK + pb) * 2 + 1) * 256));
             f32x4 acc = mfma_f16(al, eh[pb], zero);
             acc = mfma_f16(ah, el[pb], acc);
             acc = mfma_f16(ah, eh[pb], acc);
@@ -197,12 +197,12 @@ __device__ __forceinline__ float din_tail_dense(const DinTailRun& A, const float
         const float* wf = S + LD::off_w0h + lane * 4;
 #pragma unroll
         for (int b = 0; b < LD::KB0; ++b) {
-            din_f16x8 bh, bl;
+            f16x8 bh, bl;
             dyn_split8(xp[2 * b], 2 * b + 1 < KPC ? xp[2 * b + 1 < KPC ? 2 * b + 1 : 0] : zero, scale, bh, bl);
 #pragma unroll
             for (int nb = 0; nb < N0C; ++nb) {
-                const din_f16x8 ah = __builtin_bit_cast(din_f16x8, ld4(wf + ((nb * LD::KB0 + b) * 2 + 0) * 256));
-                const din_f16x8 al = __builtin_bit_cast(din_f16x8, ld4(wf + ((nb * LD::KB0 + b) * 2 + 1) * 256));
+                const f16x8 ah = __builtin_bit_cast(f16x8, ld4(wf + ((nb * LD::KB0 + b) * 2 + 0) * 256));
+                const f16x8 al = __builtin_bit_cast(f16x8, ld4(wf + ((nb * LD::KB0 + b) * 2 + 1) * 256));
                 f32x4 acc = mfma_f16(al, bh, zero);
                 acc = mfma_f16(ah, bl, acc);
                 acc = mfma_f16(ah, bh, acc);
@@ -252,12 +252,12 @@ __device__ __forceinline__ float din_tail_dense(const DinTailRun& A, const float
         const float* wf = S + LD::off_w1 + lane * 4;              // this lane's 16 bytes inside a 1-KB fragment (k_dyn_pack_w: lane order)
 #pragma unroll
         for (int b = 0; b < N0C / 2; ++b) {
-            din_f16x8 bh, bl;
+            f16x8 bh, bl;
             dyn_split8(z0[2 * b], z0[2 * b + 1], scale, bh, bl);
 #pragma unroll
             for (int n1 = 0; n1 < N1C; ++n1) {
-                const din_f16x8 ah = __builtin_bit_cast(din_f16x8, ld4(wf + ((n1 * (N0C / 2) + b) * 2 + 0) * 256));
-                const din_f16x8 al = __builtin_bit_cast(din_f16x8, ld4(wf + ((n1 * (N0C / 2) + b) * 2 + 1) * 256));
+                const f16x8 ah = __builtin_bit_cast(f16x8, ld4(wf + ((n1 * (N0C / 2) + b) * 2 + 0) * 256));
+                const f16x8 al = __builtin_bit_cast(f16x8, ld4(wf + ((n1 * (N0C / 2) + b) * 2 + 1) * 256));
                 acc[n1] = mfma_f16(ah, bh, acc[n1]);
                 acc[n1] = mfma_f16(ah, bl, acc[n1]);
                 acc[n1] = mfma_f16(al, bh, acc[n1]);
@@ -366,7 +366,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES >= 16 ? 4 : 2) void k_din_tail(co
         for (int nb = 0; nb < N0C; ++nb) z0[nb] = ld4(smem + LD::off_b0 + nb * 16 + 4 * q);
         if constexpr (UNF) {
             static_assert(DYN && DT_MAX_COLS == 4, "two K = 32 blocks of two columns, or four of one");
-            din_f16x8 eh[LD::NBLK], el[LD::NBLK];
+            f16x8 eh[LD::NBLK], el[LD::NBLK];
             din_tail_unf_gather<LD>(A, idv, q, bad, eh, el);
             din_tail_unf_fc0<LD, N0C>(A, smem, lane, eh, el, z0);
         } else {

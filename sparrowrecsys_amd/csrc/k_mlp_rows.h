@@ -388,14 +388,14 @@ __device__ __forceinline__ void mr_body(const MlpRowsRun& A, const int* __restri
             const float* wf = smem + LD::off_w1 + lane * 4;              // this lane's 16 bytes inside a 1-KB fragment (k_dyn_pack_w: lane order)
             constexpr int KB = N0C / 2, NG = N1C / 4;                    // K blocks of 32; groups of four output blocks
             auto frag = [&](int n1, int b, int part) {
-                return __builtin_bit_cast(din_f16x8, ld4(wf + ((n1 * KB + b) * 2 + part) * 256));
+                return __builtin_bit_cast(f16x8, ld4(wf + ((n1 * KB + b) * 2 + part) * 256));
             };
-            din_f16x8 ah[4], al[4];
+            f16x8 ah[4], al[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) { ah[j] = frag(j, 0, 0); al[j] = frag(j, 0, 1); }
 #pragma unroll
             for (int b = 0; b < KB; ++b) {
-                din_f16x8 bh, bl;
+                f16x8 bh, bl;
                 dyn_split8(z0[2 * b], z0[2 * b + 1], scale, bh, bl);
 #pragma unroll
                 for (int gi = 0; gi < NG; ++gi) {

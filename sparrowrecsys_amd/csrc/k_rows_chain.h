@@ -151,10 +151,9 @@ static __global__ __launch_bounds__(256) void k_rows_unf_split(const float* __re
         out[v * 2 * W + W + k] = (_Float16)(x - (float)hi);
     }
 }
-typedef _Float16 rows_f16x8 __attribute__((ext_vector_type(8)));
 template <int G_BIG, int KPC, int H0C>
 struct RowsSetUnf {
-    rows_f16x8 ehi, elo;                                  // this lane's 8 halfs of the K = 32 operand (field q >> 1, half q & 1)
+    f16x8 ehi, elo;                                  // this lane's 8 halfs of the K = 32 operand (field q >> 1, half q & 1)
     int so[RC_MAX_SMALL];
     float xa, xb;
     float sc;
@@ -272,8 +271,8 @@ __device__ __forceinline__ void rows_chain_body(const RowsRun& A, const int* __r
             if (G_BIG > 1) sq = (q >> 1) ? sid[G_BIG > 1 ? 1 : 0] : sq;
             else sq = (q >> 1) ? (unsigned)A.big_vocab[0] + A.big_rowbase[0] : sq;
             const size_t ro = (size_t)sq * RB + 16u * (q & 1);
-            S.ehi = *reinterpret_cast<const rows_f16x8*>(tb + ro);
-            S.elo = *reinterpret_cast<const rows_f16x8*>(tb + ro + 32u);
+            S.ehi = *reinterpret_cast<const f16x8*>(tb + ro);
+            S.elo = *reinterpret_cast<const f16x8*>(tb + ro + 32u);
         } else {
 #pragma unroll
         for (int b = 0; b < G_BIG; ++b) {
@@ -358,8 +357,8 @@ __device__ __forceinline__ void rows_chain_body(const RowsRun& A, const int* __r
             const float* af = smem + LD::off_af + 4 * lane;
 #pragma unroll
             for (int nb = 0; nb < KPC + H0C; ++nb) {
-                const rows_f16x8 ahi = __builtin_bit_cast(rows_f16x8, ld4(af + (2 * nb) * 256));
-                const rows_f16x8 alo = __builtin_bit_cast(rows_f16x8, ld4(af + (2 * nb + 1) * 256));
+                const f16x8 ahi = __builtin_bit_cast(f16x8, ld4(af + (2 * nb) * 256));
+                const f16x8 alo = __builtin_bit_cast(f16x8, ld4(af + (2 * nb + 1) * 256));
                 f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(alo, S.ehi, zero, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, S.elo, acc, 0, 0, 0);
                 acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(ahi, S.ehi, acc, 0, 0, 0);

@@ -1349,3 +1349,144 @@ def test_dien_reference_schema_and_bad_ids(torch, samples):
         eng.check_ids()
     with pytest.raises(L.SparrowHipError):                           # DIEN has no attention-weights output
         eng.din_pool(_cuda(torch, ids), aux, torch.empty((256, 5), dtype=torch.float32, device="cuda"))
+
+
+# --------------------------------------------------------------------------------------------
+# every kernel of the dispatch tables, in every form a handle launches it: one batch per call (one task per wave, looped) and several
+# batches per launch.  The cases are the (table entry, precision) pairs with a form no test above or in the other GPU files launches.
+# --------------------------------------------------------------------------------------------
+_FORM_SWITCHES = ("SPRK_V2_HALF", "SPRK_V2J_ONE", "SPRK_V2J1_HOIST", "SPRK_V2_ROWS", "SPRK_ROWS_UNF", "SPRK_DYN_F16", "SPRK_V1_ONE",
+                  "SPRK_DIN_FUSED", "SPRK_DIN_FUSED_MB", "SPRK_TAIL_UNF")
+_BIG = [("movieId", "id", 3000), ("userId", "id", 9000), ("userRatedMovie1", "id", 3000)]
+_SMALL = [("userGenre1", "genre", 19), ("userGenre2", "genre", 19), ("movieGenre1", "genre", 19)]
+_LOOPED_ROWS_B = 16 * 16384 + 5      # k_rows_chain's looped form takes one batch only beyond V2J1_MAX_TASKS tasks of 16 rows
+
+
+def _form_cases():
+    """(id, kind, constructor arguments, [(environment, same bits as the first form)], describe()["kernel"] prefix, split_f16 site or None)"""
+    cases = []
+    # k_deepfm_v2_joint<G_BIG, NJF>: joint1, its HOIST form and the looped kernel (split-f16), the looped kernel (f32); _many of each
+    for g_big, njf in ((3, 3), (2, 2), (3, 2), (3, 1), (2, 3), (2, 1), (1, 3), (1, 2), (1, 1)):
+        fields = _BIG[:g_big] + _SMALL[:njf]
+        if (g_big, njf) != (3, 3):                               # (config 2's split-f16 entry: every form runs above)
+            cases.append(("v2j-%d-%d-split" % (g_big, njf), "v2", dict(emb_dim=16, fields=fields, proj_dim=16),
+                          [({}, True), ({"SPRK_V2J1_HOIST": "1"}, True), ({"SPRK_V2J_ONE": "0"}, True)],
+                          "k_deepfm_v2_joint<G_BIG=%d,NJF=%d,KPC=1,split-f16>" % (g_big, njf), "v2"))
+        cases.append(("v2j-%d-%d-f32" % (g_big, njf), "v2", dict(emb_dim=16, fields=fields, proj_dim=16), [({"SPRK_V2_HALF": "0"}, True)],
+                      "k_deepfm_v2_joint<G_BIG=%d,NJF=%d,KPC=1,f32>" % (g_big, njf), None))
+    # k_rows_chain<KPC, H0C, H1C, G_BIG, NJF>: raw split rows (UNF) and folded rows
+    for kpc, g_big, njf, unf in ((4, 2, 2, True), (4, 2, 1, True), (4, 1, 1, True), (2, 2, 2, True), (4, 2, 2, False), (4, 2, 1, False),
+                                 (4, 1, 1, False), (4, 3, 3, False), (4, 3, 1, False), (2, 2, 2, False), (2, 3, 3, False), (1, 3, 3, False)):
+        env = {} if unf or g_big == 3 else {"SPRK_ROWS_UNF": "0"}
+        if kpc == 1:
+            env = {"SPRK_V2_ROWS": "1"}
+        cases.append(("rows-%d-%d-%d%s" % (kpc, g_big, njf, "-unf" if unf else ""), "v2",
+                      dict(emb_dim=16, fields=_BIG[:g_big] + _SMALL[:njf], proj_dim=16 * kpc), [(env, True)],
+                      "k_rows_chain<KPC=%d,H0C=2,H1C=1,G_BIG=%d,NJF=%d%s>" % (kpc, g_big, njf, ",UNF" if unf else ""), "rows_unf" if unf else None))
+    cases.append(("rows-ncf", "ncf", dict(emb_dim=10, movie_buckets=5000, user_buckets=7000), [({}, True)],
+                  "k_rows_chain<KPC=0,H0C=1,H1C=1,G_BIG=2,NJF=0>", None))
+    # k_deepfm_pairs<NF, NV, SEP>: pairs1 and the looped kernel (split-f16), the looped kernel (f32); _many of each
+    for nf, nv, D in ((6, 4, 16), (4, 3, 10), (4, 4, 16), (4, 16, 64)):
+        for tied in (False, True):
+            kw = dict(emb_dim=D, share_deep_tables=tied)
+            if nf == 6:
+                kw.update(fields=SY.CONFIG2_FIELDS, pairs=SY.CONFIG2_PAIRS)
+            tag = "pairs-%d-%d-%s" % (nf, nv, "tied" if tied else "sep")
+            if tied or (nf, nv) in ((4, 4), (4, 16)):            # (config 2's and the reference's own-table split-f16 entries: every form runs above)
+                cases.append((tag + "-split", "pairs", kw, [({}, True), ({"SPRK_V1_ONE": "0"}, True)], "k_deepfm_pairs<NF=%d,NV=%d>" % (nf, nv), "dyn_w1"))
+            cases.append((tag + "-f32", "pairs", kw, [({"SPRK_DYN_F16": "0"}, True)], "k_deepfm_pairs<NF=%d,NV=%d>" % (nf, nv), None))
+    # k_din_tail<N0C, N1C, KPC> behind k_din_attn_cols<KC>: f32 fc1, split-f16 fragments, raw split rows (UNF)
+    for n0c, n1c, kpc in ((8, 4, 2), (8, 4, 1), (4, 2, 2), (4, 2, 1)):
+        kw = dict(emb_dim=32 if kpc == 2 else 16, hist_len=9 if kpc == 2 else 12, hidden=(16 * n0c, 16 * n1c), movie_buckets=3000, user_buckets=900)
+        for form, env in (("f32", {"SPRK_DYN_F16": "0"}), ("dyn", {"SPRK_TAIL_UNF": "0"}), ("unf", {})):
+            if (n0c, n1c, kpc, form) == (8, 4, 2, "unf"):        # (config 3's entry: one batch and several run above)
+                continue
+            cases.append(("tail-%d-%d-%d-%s" % (n0c, n1c, kpc, form), "din", kw, [(dict(env, SPRK_DIN_FUSED="0"), True)],
+                          "k_din_tail<%d,%d,%d%s>" % (n0c, n1c, kpc, ",UNF" if form == "unf" else ""),
+                          {"f32": None, "dyn": "dyn_w1", "unf": "tail_unf"}[form]))
+    # k_din_fused<KC=1, MB>: the several-batches form at emb_dim <= 16
+    cases.append(("din-fused-kc1", "din", dict(emb_dim=16, hist_len=20, movie_buckets=3000, user_buckets=900), [({}, True)], "k_din_fused<KC=1", "tail_unf"))
+    return cases
+
+
+@pytest.mark.parametrize("case", _form_cases(), ids=lambda c: c[0])
+def test_every_dispatch_table_entry_in_every_launch_form(torch, monkeypatch, case):
+    """B = 133 (a second 8-wave workgroup, a ragged last task of 5 rows), three batches at two per launch (a full group and a short one):
+    each form against the fp64 oracle at the bar of the route's tests above, the several-batches launch the same bits as a launch per batch,
+    the one-task-per-wave and looped kernels the same bits.  k_rows_chain's looped form runs one batch only beyond 16 384 tasks: that size,
+    its last 133 rows against the same rows scored alone."""
+    _, kind, kw, forms, kernel, site = case
+    B, n, per = 133, 3, 2
+    make = {"v2": M.DeepFMv2, "ncf": M.NeuralCF, "pairs": M.DeepFM, "din": M.DIN}[kind]
+
+    def synth(rows, seed):
+        if kind == "v2":
+            return SY.synth_fields(rows, kw["fields"], seed=seed)
+        if kind == "pairs":
+            return SY.synth_fields(rows, kw.get("fields") or M._default_fields(), seed=seed)
+        if kind == "ncf":
+            rng = np.random.default_rng(seed)
+            return {"movieId": rng.integers(0, kw["movie_buckets"], rows), "userId": rng.integers(0, kw["user_buckets"], rows)}
+        return SY.synth_din(rows, kw["hist_len"], kw["movie_buckets"], kw["user_buckets"], seed=seed)
+
+    def oracle(model, feats):
+        if kind == "v2":
+            return O.deepfm_v2_forward(feats, model.weights, dtype=np.float64, fields=model.fields, order=model.order)[:, 0]
+        if kind == "pairs":
+            return O.deepfm_forward(feats, model.weights, dtype=np.float64, share_deep_tables=kw["share_deep_tables"],
+                                    fields=kw.get("fields") or M._default_fields(), pairs=model.pairs)[:, 0]
+        if kind == "ncf":
+            return O.neural_cf_forward(feats, model.weights, dtype=np.float64, movie_buckets=kw["movie_buckets"], user_buckets=kw["user_buckets"])[:, 0]
+        return O.din_forward(feats, model.weights, dtype=np.float64, hist_len=kw["hist_len"], movie_buckets=kw["movie_buckets"],
+                             user_buckets=kw["user_buckets"])[:, 0]
+
+    # the bar of the route's own tests: TOL for attention -> pooled vectors -> k_din_tail (test_forward_many_several_batches_per_launch_din), TIGHT elsewhere
+    bar = TOL if kernel.startswith("k_din_tail") else TIGHT
+    feats = [synth(B, 600 + i) for i in range(n)]
+    first = None
+    for env, same_bits in forms:
+        for name in _FORM_SWITCHES:
+            monkeypatch.delenv(name, raising=False)
+        for name, value in env.items():
+            monkeypatch.setenv(name, value)
+        model = make(seed=83, **kw)
+        eng = model.engine
+        d = eng.describe()
+        assert d["kernel"].startswith(kernel), d
+        assert site is None or site in d["split_f16"].split(","), d
+        if site is None:
+            assert not set(d["split_f16"].split(",")) & {"v2", "rows_unf", "dyn_w1", "tail_unf"}, d
+        if kind == "din":
+            assert d["stage"] == ("k_din_fused" if kernel.startswith("k_din_fused") else "k_din_attn_cols"), d
+        packed = [model.pack(f) for f in feats]
+        ids = [_cuda(torch, p[0]) for p in packed]
+        dense = [_cuda(torch, p[1]) for p in packed]
+        one = [model.predict_device(ids[i], dense[i]).cpu().numpy().reshape(-1) for i in range(n)]
+        eng.set_many_batches(per)
+        ws = torch.empty(eng.many_workspace_bytes(B, per) // 4, dtype=torch.float32, device="cuda") if kind == "din" else None
+        outs = [torch.full((B,), -1.0, dtype=torch.float32, device="cuda") for _ in range(n)]
+        eng.forward_many(ids, dense, outs, ws)
+        torch.cuda.synchronize()
+        eng.check_ids()
+        for i in range(n):
+            np.testing.assert_array_equal(outs[i].cpu().numpy(), one[i])
+            err = float(np.abs(one[i] - oracle(model, feats[i])).max())
+            print("%s %s batch %d: max|err| vs fp64 oracle %.3g (bar %.3g)" % (case[0], env, i, err, bar))
+            assert err <= bar, (env, i, err)
+        if first is None:
+            first = one
+        elif same_bits:
+            for i in range(n):
+                np.testing.assert_array_equal(one[i], first[i])
+        if kernel.startswith("k_rows_chain"):
+            big = synth(_LOOPED_ROWS_B, 700)
+            bi, bd = model.pack(big)
+            ti, td = _cuda(torch, bi), _cuda(torch, bd)
+            full = model.predict_device(ti, td)
+            lo = _LOOPED_ROWS_B - B
+            assert torch.equal(model.predict_device(ti[lo:].contiguous(), td[lo:].contiguous()), full[lo:])
+            eng.check_ids()
+            err = float(np.abs(full[lo:].cpu().numpy().reshape(-1) - oracle(model, {k: v[lo:] for k, v in big.items()})).max())
+            print("%s looped, B = %d: max|err| vs fp64 oracle %.3g (bar %.3g)" % (case[0], _LOOPED_ROWS_B, err, bar))
+            assert err <= bar, err
+        eng.close()
