@@ -427,6 +427,47 @@ int sprk_pack_columns_device(const sprk_pack_col* id_cols, int32_t n_id, const s
  * SPRK_ERANGE converted the batch (1 or 2). */
 int sprk_pack_last_route(void);
 
+/* ---- feature store in HBM: (userId, movieId) pairs -> the two packed arrays, and the sort behind the scores ----
+ * The reference's ranking request carries {"userId": u, "movieId": m} x 800 and nothing else (RecForYouProcess.java:113-138); every other
+ * model input comes from two per-entity maps, the `uf:<userId>` / `mf:<movieId>` hashes that FeatureEngForRecModel.scala:127-174,208-259
+ * writes (the columns of each user's and each movie's latest sample).  Here the two maps are device tables indexed by id (row = id,
+ * `pitch` dwords per row, a multiple of 4; one `has` byte per row), holding for every column exactly the 32 bits schema.pack_ids /
+ * pack_dense produce (sparrowrecsys_amd/featurestore.py lays them out).  sprk_join_features writes output row q * C + c of
+ * `ids_out [Q*C, n_id] int32` / `dense_out [Q*C, n_dense] float32` -- the format sprk_forward* reads -- for user_ids[q] and movie_ids[q][c]
+ * (shared_candidates = 1: movie_ids[c], one list of C for every query); pairs are C = 1.  Every output column is one sprk_join_col:
+ *   source  SPRK_JOIN_PAIR_USER / PAIR_MOVIE: the pair's own id; SPRK_JOIN_USER_ROW / MOVIE_ROW: dword `offset` of that table's row
+ *   rule    SPRK_RULE_IDENTITY  the value as it is; one outside [0, vocab) is still written, and reported (below)
+ *           SPRK_RULE_GENRE     the value, -1 outside [0, vocab)
+ *           SPRK_RULE_DENSE     the 32 bits as they are (dense columns only; id columns are IDENTITY or GENRE, the pair's ids IDENTITY)
+ * A user (movie) id outside [0, n_users) ([0, n_movies)), or one whose `has` byte is 0, reads the default row -- identity 0, genre -1,
+ * dense 0.0 -- and nothing of the table; its own id still goes to the PAIR columns.  `range_key` is ONE caller-provided device word,
+ * set to ~0 before the call: the kernel atomicMin's (id column index << 32 | output row) of every identity value outside its range into
+ * it, so afterwards it names the error schema.pack_ids would raise for the same rows (first column in id_cols order, then first row).
+ * All pointers but the descriptor lists are device memory; tables and outputs 16-byte aligned; at most SPRK_PACK_MAX_COLS columns;
+ * Q * C < 2^31.  Anything else returns SPRK_EINVAL BEFORE any device call.  Asynchronous on `stream`: no synchronisation, no memory owned
+ * by the library; all index arithmetic in 64 bits.  Q, C or the column count 0: nothing is done. */
+#define SPRK_JOIN_PAIR_USER 0
+#define SPRK_JOIN_PAIR_MOVIE 1
+#define SPRK_JOIN_USER_ROW 2
+#define SPRK_JOIN_MOVIE_ROW 3
+typedef struct sprk_join_col {
+    int32_t source;      /* SPRK_JOIN_*                                                          */
+    int32_t offset;      /* USER_ROW / MOVIE_ROW: dword offset in the row (PAIR_*: unused)       */
+    int32_t rule;        /* SPRK_RULE_*                                                          */
+    int32_t vocab;       /* buckets / vocabulary size (unused for DENSE)                         */
+} sprk_join_col;
+int sprk_join_features(const int32_t* user_rows, const uint8_t* user_has, int32_t n_users, int32_t user_pitch,
+                       const int32_t* movie_rows, const uint8_t* movie_has, int32_t n_movies, int32_t movie_pitch,
+                       const int32_t* user_ids /* [Q] */, const int32_t* movie_ids /* [Q][C], or [C] shared */,
+                       int32_t Q, int32_t C, int32_t shared_candidates,
+                       const sprk_join_col* id_cols, int32_t n_id, const sprk_join_col* dense_cols, int32_t n_dense,
+                       int32_t* ids_out, float* dense_out, uint64_t* range_key, void* stream);
+/* order[q][0..C) = the candidate POSITIONS of scores[q][0..C) (float32, device memory) in the order of
+ * `sorted(comparingByValue(reverseOrder()))` (RecForYouProcess.java:69-92): descending in Float.compare order -- every NaN one greatest
+ * value, 0.0 before -0.0 -- and equal scores in candidate order: sprk_emb_rank's convention.  1 <= C <= 4096, Q >= 0, pointers not
+ * NULL, else SPRK_EINVAL before any device call.  Asynchronous on `stream`; owns no memory. */
+int sprk_rank_scores(const float* scores, int32_t Q, int32_t C, int32_t* order, void* stream);
+
 /* ---- multi-GPU: the path's one collective (the reference has no distributed path) ----
  * Batch rows are sharded over one process per GPU, tables and weights replicated; every rank ends with all scores through ONE
  * all-gather of the per-rank score slices over RCCL / xGMI, enqueued on the caller's HIP stream (no host synchronisation).

@@ -35,7 +35,7 @@ EXPORTED_SYMBOLS = [
     "sprk_check_ids", "sprk_destroy", "sprk_embedding_gather", "sprk_cross_hash", "sprk_last_error",
     "sprk_pack_csv", "sprk_pack_csv_mt", "sprk_pack_csv_device", "sprk_csv_last_path",
     "sprk_pack_columns", "sprk_pack_columns_device", "sprk_pack_last_route", "sprk_set_many_streams", "sprk_set_many_batches", "sprk_emb_rank",
-    "sprk_emb_topk", "sprk_emb_topk_workspace_bytes",
+    "sprk_emb_topk", "sprk_emb_topk_workspace_bytes", "sprk_join_features", "sprk_rank_scores",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -55,6 +55,15 @@ PACK_MAX_COLS = 128
 class PackCol(C.Structure):
     _fields_ = [("data", C.c_void_p), ("stride", C.c_int64), ("storage", C.c_int32), ("width", C.c_int32), ("on_device", C.c_int32),
                 ("rule", C.c_int32), ("vocab", C.c_int32), ("reserved", C.c_int32), ("name", C.c_char_p)]
+
+
+# sources of a JoinCol (include/sparrow_hip.h SPRK_JOIN_*)
+JOIN_PAIR_USER, JOIN_PAIR_MOVIE, JOIN_USER_ROW, JOIN_MOVIE_ROW = range(4)
+RANK_MAX_SORT = 4096
+
+
+class JoinCol(C.Structure):
+    _fields_ = [("source", C.c_int32), ("offset", C.c_int32), ("rule", C.c_int32), ("vocab", C.c_int32)]
 
 
 class Seg(C.Structure):
@@ -244,6 +253,9 @@ def load_library():
         lib.sprk_emb_topk.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]
         lib.sprk_emb_topk_workspace_bytes.argtypes = [i32, i32, i32]
         lib.sprk_emb_topk_workspace_bytes.restype = sz
+        lib.sprk_join_features.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, C.POINTER(JoinCol), i32, C.POINTER(JoinCol), i32,
+                                           vp, vp, vp, vp]
+        lib.sprk_rank_scores.argtypes = [vp, i32, i32, vp, vp]
         for name in EXPORTED_SYMBOLS:
             if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int

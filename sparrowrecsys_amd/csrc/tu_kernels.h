@@ -41,5 +41,7 @@
 #include "k_peer_gather.h"
 #include "k_csv_pack.h"
 #include "k_pack_columns.h"          // feature columns -> packed ids / dense (a template: only sparrow_hip.hip instantiates it)
+#include "k_feature_join.h"          // (userId, movieId) pairs x the feature store's tables -> packed ids / dense (reuses pk_report, the tile constants)
+#include "k_rank_scores.h"           // scores -> candidate positions best first, one workgroup per query
 #include "k_operators.h"             // stand-alone operator kernels (bit-exact gather, cross hash) -- closes the kernels' anonymous namespace
 #include "tu_instances.h"          // the heavy templates: defined in ONE family unit, `extern template` elsewhere

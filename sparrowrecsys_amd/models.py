@@ -293,6 +293,50 @@ class Engine:
             pass
 
 
+class _Joined:
+    """What one enqueued join left behind (``CTRModel._join``)."""
+    __slots__ = ("ids", "dense", "key", "plan", "Q", "C", "shared", "users", "movies")
+
+    def __init__(self, ids, dense, key, plan, Q, Cn, shared, users, movies):
+        self.ids, self.dense, self.key, self.plan, self.Q, self.C, self.shared, self.users, self.movies = ids, dense, key, plan, Q, Cn, shared, users, movies
+
+
+class JoinPlan:
+    """``sprk_join_col`` descriptors of one model over one store: ``id_cols`` / ``dense_cols`` are ``(source, offset, rule, vocab)`` tuples in
+    ``id_columns`` / ``numeric_keys`` order, ``id_array`` / ``dense_array`` the same as ctypes arrays."""
+
+    def __init__(self, id_columns: Sequence[IdColumn], numeric_keys: Sequence[str], store):
+        ulay, mlay = store.user_layout, store.movie_layout
+        roles = {"id": L.RULE_IDENTITY, "genre": L.RULE_GENRE}
+
+        def row(key, role):
+            if key in ulay and ulay[key][1] == role:
+                return L.JOIN_USER_ROW, ulay[key][0]
+            if key in mlay and mlay[key][1] == role:
+                return L.JOIN_MOVIE_ROW, mlay[key][0]
+            hint = ""
+            if key.startswith("userRatedMovie") and key[len("userRatedMovie"):].isdigit():
+                hint = " (it keeps a history of %d)" % store.hist_len
+            raise ValueError("the feature store holds no %s column %r%s" % ({"id": "identity", "genre": "genre", "dense": "numeric"}[role], key, hint))
+        self.id_cols, self.dense_cols = [], []
+        for c in id_columns:
+            if c.kind == "id" and c.key == "userId":
+                self.id_cols.append((L.JOIN_PAIR_USER, 0, L.RULE_IDENTITY, c.vocab))
+            elif c.kind == "id" and c.key == "movieId":
+                self.id_cols.append((L.JOIN_PAIR_MOVIE, 0, L.RULE_IDENTITY, c.vocab))
+            else:
+                src, off = row(c.key, c.kind)
+                self.id_cols.append((src, off, roles[c.kind], c.vocab))
+        for k in numeric_keys:
+            src, off = row(k, "dense")
+            self.dense_cols.append((src, off, L.RULE_DENSE, 0))
+        self.n_id, self.n_dense = len(self.id_cols), len(self.dense_cols)
+        if self.n_id + self.n_dense > L.PACK_MAX_COLS:
+            raise ValueError("the join takes at most %d columns (%d)" % (L.PACK_MAX_COLS, self.n_id + self.n_dense))
+        self.id_array = (L.JoinCol * max(self.n_id, 1))(*[L.JoinCol(*t) for t in self.id_cols])
+        self.dense_array = (L.JoinCol * max(self.n_dense, 1))(*[L.JoinCol(*t) for t in self.dense_cols])
+
+
 class CTRModel:
     MODEL_KIND = L.MODEL_GENERIC
     FORWARD_SYMBOL = "sprk_forward"
@@ -545,6 +589,176 @@ class CTRModel:
             self.predict_device(ids[lo:n], dense[lo:n], out[lo:n])
         self.engine.check_ids()
         return out.cpu().numpy().reshape(-1, 1)
+
+    # ---- (userId, movieId) pairs: the rest of the sample row comes from a FeatureStore, on the device ---------------------------
+    def join_plan(self, store) -> "JoinPlan":
+        """The descriptors of ``sprk_join_features`` for this model over ``store``, derived from ``id_columns`` and ``numeric_keys`` alone:
+        userId / movieId are the pair's own ids, everything else a dword of the user's or the movie's row."""
+        return JoinPlan(self.id_columns, self.numeric_keys, store)
+
+    def _pair_ids(self, v, what):
+        """A request's ids -> (host int64 array, device int32 tensor); a value beyond int32 travels as -1 (out of every range: the
+        kernel reports it, the message is made from the host value)."""
+        import torch
+        if hasattr(v, "is_cuda") and v.is_cuda:
+            if v.dtype not in (torch.int32, torch.int64):
+                raise ValueError("%s: an int32 / int64 device tensor is required, got %s" % (what, v.dtype))
+            t = v if v.dtype == torch.int32 else torch.where((v < 0) | (v >= (1 << 31)), torch.full_like(v, -1), v).to(torch.int32)
+            return None, t.contiguous()
+        a = np.asarray(v) if not hasattr(v, "detach") else v.detach().numpy()
+        shape = a.shape
+        h = to_int_column(a.reshape(-1), what).reshape(shape)
+        d = np.where((h < 0) | (h >= (1 << 31)), -1, h).astype(np.int32)
+        return h, torch.from_numpy(np.ascontiguousarray(d))
+
+    def _join(self, store, user_ids, movie_ids, shared_candidates=False):
+        """Enqueues the join -> a ``_Joined`` (device ids / dense, the range key word, what an error message needs).  No synchronisation."""
+        import torch
+        plan = getattr(self, "_join_plan_cache", None)
+        if plan is None or plan[0] is not store:
+            plan = (store, self.join_plan(store))
+            self._join_plan_cache = plan
+        plan = plan[1]
+        urows, uhas, mrows, mhas = store.tensors()
+        dev = store.device
+        uh, ut = self._pair_ids(user_ids, "userId")
+        mh, mt = self._pair_ids(movie_ids, "movieId")
+        if ut.dim() != 1:
+            raise ValueError("user_ids must be one-dimensional")
+        Q = int(ut.shape[0])
+        if mt.dim() == 2:
+            if shared_candidates or int(mt.shape[0]) != Q:
+                raise ValueError("movie_ids [Q, C] needs one row per user (%d), and shared_candidates=False" % Q)
+            Cn = int(mt.shape[1])
+        elif mt.dim() == 1:
+            Cn = int(mt.shape[0]) if shared_candidates else 1
+            if not shared_candidates and int(mt.shape[0]) != Q:
+                raise ValueError("%d movie ids for %d user ids" % (int(mt.shape[0]), Q))
+        else:
+            raise ValueError("movie_ids must be [B], [C] (shared_candidates) or [Q, C]")
+        rows = Q * Cn
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            ut = ut.to(dev, non_blocking=True)
+            mt = mt.to(dev, non_blocking=True)
+            ids = torch.empty((rows, plan.n_id), dtype=torch.int32, device=dev)
+            dense = torch.empty((rows, plan.n_dense), dtype=torch.float32, device=dev)
+            key = torch.full((1,), -1, dtype=torch.int64, device=dev)
+            if rows:
+                L.check(L.load_library().sprk_join_features(
+                    C.c_void_p(urows.data_ptr()), C.c_void_p(uhas.data_ptr()), store.n_users, store.user_pitch,
+                    C.c_void_p(mrows.data_ptr()), C.c_void_p(mhas.data_ptr()), store.n_movies, store.movie_pitch,
+                    C.c_void_p(ut.data_ptr()), C.c_void_p(mt.data_ptr()), Q, Cn, 1 if (shared_candidates and mt.dim() == 1) else 0,
+                    plan.id_array, plan.n_id, plan.dense_array, plan.n_dense,
+                    C.c_void_p(ids.data_ptr() if plan.n_id else None), C.c_void_p(dense.data_ptr() if plan.n_dense else None),
+                    C.c_void_p(key.data_ptr()), C.c_void_p(stream)))
+        return _Joined(ids, dense, key, plan, Q, Cn, bool(shared_candidates and mt.dim() == 1), (uh, ut), (mh, mt))
+
+    def _raise_join_range(self, joined, key_word: int):
+        """``schema.pack_ids``' ValueError for the identity value the join reported: its message, column and first row."""
+        col, row = int(key_word >> 32), int(key_word & 0xFFFFFFFF)
+        c = self.id_columns[col]
+        src = joined.plan.id_cols[col][0]
+        if src in (L.JOIN_PAIR_USER, L.JOIN_PAIR_MOVIE):                # the request's own value (it may not fit the int32 that travelled)
+            host, dev = joined.users if src == L.JOIN_PAIR_USER else joined.movies
+            at = row // joined.C if (src == L.JOIN_PAIR_USER) else (row % joined.C if joined.shared else row)
+            value = int(host.reshape(-1)[at]) if host is not None else int(dev.reshape(-1)[at].item())
+        else:
+            value = int(joined.ids[row, col].item())
+        raise ValueError("%s id %d outside [0, %d) (reference: assert_less_than_num_buckets)" % (c.key, value, c.vocab))
+
+    def pack_pairs_device(self, store, user_ids, movie_ids, shared_candidates: bool = False):
+        """``(userId, movieId)`` pairs -> DEVICE tensors ``(ids, dense)`` ready for ``predict_device``: every other column is joined from
+        ``store`` on the device (``sprk_join_features``).  ``movie_ids`` is ``[B]`` next to ``user_ids [B]``; with
+        ``shared_candidates`` a list ``[C]`` every user is paired with, or ``[Q, C]`` per-user lists: row ``q * C + c``.  Synchronises
+        the stream, so an identity value outside its range raises here, as ``pack_ids`` raises it for the assembled columns."""
+        j = self._join(store, user_ids, movie_ids, shared_candidates)
+        k = int(j.key.item())
+        if k != -1:
+            self._raise_join_range(j, k & 0xFFFFFFFFFFFFFFFF)
+        return j.ids, j.dense
+
+    def _pinned(self, shape, dtype):
+        """A pinned host tensor of this shape over the model's reusable staging buffer (grown to the largest result seen; the first 8
+        bytes are the key word's)."""
+        import torch
+        n = 8 + int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+        buf = getattr(self, "_pairs_staging", None)
+        if buf is None or buf.numel() < n:
+            buf = torch.empty(n + n // 4 + 256, dtype=torch.uint8).pin_memory()
+            self._pairs_staging = buf
+        return buf[:8].view(torch.int64), buf[8:n].view(dtype).view(shape)
+
+    def _finish_pairs(self, joined, extra=None):
+        """ONE synchronisation: the key word (and the device tensor ``extra``, returned as a view of the pinned staging buffer, valid until
+        the next call) come to the host behind everything enqueued; a reported id raises."""
+        import torch
+        key_h, out_h = self._pinned(extra.shape if extra is not None else (0,), extra.dtype if extra is not None else torch.float32)
+        key_h.copy_(joined.key, non_blocking=True)
+        if extra is not None:
+            out_h.copy_(extra, non_blocking=True)
+        torch.cuda.current_stream(joined.key.device).synchronize()
+        k = int(key_h.item())
+        if k != -1:
+            try:
+                self.engine.check_ids()                              # (the forward saw the same id: its flag is cleared with this one)
+            except Exception:                                        # whatever the engine says about it, the reported id is the error
+                pass
+            self._raise_join_range(joined, k & 0xFFFFFFFFFFFFFFFF)
+        return out_h if extra is not None else None
+
+    def predict_pairs(self, store, user_ids, movie_ids) -> np.ndarray:
+        """``predict`` for a request that carries nothing but ``userId`` / ``movieId`` (the Jetty server's, RecForYouProcess.java:113-138):
+        the join, the forward, one synchronisation -> ``ndarray [B, 1] float32``, the scores ``predict`` gives for the assembled dict."""
+        import torch
+        j = self._join(store, user_ids, movie_ids)
+        if j.ids.shape[0] == 0:
+            return np.zeros((0, 1), dtype=np.float32)
+        with torch.cuda.device(store.device):
+            out = self.predict_device(j.ids, j.dense)
+            scores = self._finish_pairs(j, out)
+        return scores.numpy().reshape(-1, 1).copy()
+
+    def recommend(self, store, user_ids, candidates, size: int):
+        """Per user the ``size`` best of the candidate movie ids, best first (``RecForYouProcess.getRecList`` + ``ranker``,
+        RecForYouProcess.java:32-92): the join in cross form, the forward, ``sprk_rank_scores`` -- only the first ``size`` positions
+        per user come to the host, with one synchronisation.  ``candidates`` is one list ``[C]`` for every user or ``[Q, C]`` (host or
+        device); ``size`` is clamped to C (``subList``); a user without a row in the store gets ``[]`` (``getUserById`` null).  Equal scores
+        keep candidate order."""
+        import torch
+        shape = tuple(candidates.shape) if hasattr(candidates, "shape") else np.shape(candidates)
+        if len(shape) not in (1, 2) or shape[-1] < 1 or shape[-1] > L.RANK_MAX_SORT:
+            raise ValueError("recommend: candidates must be [C] or [Q, C] with 1 <= C <= %d" % L.RANK_MAX_SORT)
+        j = self._join(store, user_ids, candidates, shared_candidates=len(shape) == 1)
+        Q, Cn = j.Q, j.C
+        if Q == 0:
+            return []
+        size = max(0, min(int(size), Cn))
+        dev = store.device
+        cand_h, cand_d = j.movies
+        with torch.cuda.device(dev):
+            out = self.predict_device(j.ids, j.dense)
+            order = torch.empty((Q, Cn), dtype=torch.int32, device=dev)
+            L.check(self.engine.lib.sprk_rank_scores(C.c_void_p(out.data_ptr()), Q, Cn, C.c_void_p(order.data_ptr()),
+                                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            top = None
+            if size:
+                top = order[:, :size]
+                if cand_h is None:                                   # candidates that live on the device: their ids are picked there
+                    top = cand_d[top.long()] if j.shared else torch.gather(cand_d, 1, top.long())
+                top = top.contiguous()
+            top = self._finish_pairs(j, top)
+        users = j.users[0] if j.users[0] is not None else j.users[1].cpu().numpy()
+        known = store.has_user(users)
+        recs = []
+        for q in range(Q):
+            if not known[q] or size == 0:
+                recs.append([])
+            elif cand_h is None:
+                recs.append(top[q].tolist())
+            else:
+                recs.append((cand_h if j.shared else cand_h[q])[top[q].numpy()].tolist())
+        return recs
 
 
 # =============================================================================================

@@ -250,6 +250,23 @@ class _MicroBatcher:
             g["done"].set()
 
 
+class StoreBackedModel:
+    """A model in front of a :class:`~sparrowrecsys_amd.featurestore.FeatureStore`, Keras-shaped for ``PredictServer`` / ``serve_workers``:
+    a request whose feature keys are exactly ``{userId, movieId}`` -- the Jetty ranker's, RecForYouProcess.java:113-138 -- is scored
+    through ``model.predict_pairs`` (every other column joined from the store on the device); any other request goes to
+    ``model.predict`` unchanged."""
+
+    def __init__(self, model, store):
+        self.model, self.store = model, store
+
+    def predict(self, feats):
+        if isinstance(feats, Mapping) and set(feats) == {"userId", "movieId"}:
+            return self.model.predict_pairs(self.store, feats["userId"], feats["movieId"])
+        return self.model.predict(feats)
+
+    __call__ = predict
+
+
 class _Headers(dict):
     """Lower-cased header names -> values: the part of email.message.Message the handler uses."""
 
@@ -705,29 +722,35 @@ def serve_workers(factory, fargs=(), n_workers: int = 4, name: str = "recmodel",
     return WorkerPool(procs, stop, port, pids, engine_pid, tmpdir)
 
 
-def _cli_model(model_name, weights_path):
+def _cli_model(model_name, weights_path, features_path=None):
     from . import models as M
     cls = {"neuralcf": M.NeuralCF, "embedding_mlp": M.EmbeddingMLP, "wide_n_deep": M.WideNDeep, "deepfm": M.DeepFM,
            "deepfm_v2": M.DeepFMv2, "din": M.DIN, "dien": M.DIEN}[model_name]
     weights = dict(np.load(weights_path)) if weights_path else None
     model = cls(weights=weights, seed=None if weights else 0)
     model.engine                                           # fail loudly now if the HIP library / device is missing
+    if features_path:                                      # {userId, movieId} requests: the other columns from the samples' latest rows
+        from .featurestore import FeatureStore
+        store = FeatureStore.from_samples(features_path, hist_len=getattr(model, "hist_len", 5))
+        model.join_plan(store)                             # (a model the store cannot feed fails here, not at the first request)
+        return StoreBackedModel(model, store)
     return model
 
 
 def _main():
-    from . import models as M
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--model", default="neuralcf", choices=["neuralcf", "embedding_mlp", "wide_n_deep", "deepfm", "deepfm_v2", "din", "dien"])
     ap.add_argument("--weights", help=".npz of reference-layout weights (keys as CTRModel.weight_shapes()); default: seeded random")
     ap.add_argument("--name", default="recmodel")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=8501)
+    ap.add_argument("--features", help="samples CSV (the schema of testSamples.csv): a feature store of every user's and movie's latest row; "
+                                       "requests that send only userId / movieId are completed from it on the device")
     ap.add_argument("--workers", type=int, default=1, help="front processes sharing the port (SO_REUSEPORT) in front of ONE engine process that owns the model and the GPU")
     args = ap.parse_args()
     if args.workers > 1:
         import signal
-        pool = serve_workers(_cli_model, (args.model, args.weights), n_workers=args.workers, name=args.name, host=args.host, port=args.port)
+        pool = serve_workers(_cli_model, (args.model, args.weights, args.features), n_workers=args.workers, name=args.name, host=args.host, port=args.port)
         print("serving %s on http://%s:%d/v1/models/%s:predict from %d workers (pids %s)" % (args.model, args.host, pool.port, args.name, args.workers, pool.pids), flush=True)
         # [r6, ADVICE r05] a plain `kill` (SIGTERM) must take the fronts and the engine along, and a dead engine must end the service
         def _term(signum, frame):
@@ -742,11 +765,7 @@ def _main():
         finally:
             pool.close()
         return
-    cls = {"neuralcf": M.NeuralCF, "embedding_mlp": M.EmbeddingMLP, "wide_n_deep": M.WideNDeep, "deepfm": M.DeepFM,
-           "deepfm_v2": M.DeepFMv2, "din": M.DIN, "dien": M.DIEN}[args.model]
-    weights = dict(np.load(args.weights)) if args.weights else None
-    model = cls(weights=weights, seed=None if weights else 0)
-    model.engine                                           # fail loudly now if the HIP library / device is missing
+    model = _cli_model(args.model, args.weights, args.features)
     srv = PredictServer(model, name=args.name, host=args.host, port=args.port)
     print("serving %s on http://%s:%d/v1/models/%s:predict" % (args.model, args.host, srv.port, args.name), flush=True)
     try:
