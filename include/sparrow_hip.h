@@ -468,6 +468,35 @@ int sprk_join_features(const int32_t* user_rows, const uint8_t* user_has, int32_
  * NULL, else SPRK_EINVAL before any device call.  Asynchronous on `stream`; owns no memory. */
 int sprk_rank_scores(const float* scores, int32_t Q, int32_t C, int32_t* order, void* stream);
 
+/* ---- model.evaluate's accumulators in device memory ----
+ * Every reference script ends with `model.evaluate(test_dataset)` -> [loss, accuracy, roc_auc, pr_auc] (DeepFM.py:117-133): binary
+ * cross-entropy, accuracy at 0.5 and tf.keras.metrics.AUC(num_thresholds=200) for ROC and PR.  Keras keeps each metric as a handful of
+ * accumulators that are updated batch by batch; here they live in ONE caller-owned block of device memory, and an update folds n
+ * float32 scores and their labels into it on the caller's stream -- no score and no label crosses to the host, and the host reads
+ * the few KB of state once, at the end (sparrowrecsys_amd/metrics.py DeviceMetrics turns it into the four numbers).
+ * The state is sprk_metrics_state_bytes(T) bytes, 16-byte aligned, laid out as 8-byte words:
+ *   [0] T (thresholds)   [1] n (samples)   [2] n_correct   [3] loss_sum (double)
+ *   pos[T + 1], neg[T + 1] (uint64)   th[T] (double)   partial[1024] (double: one update's per-workgroup loss sums, scratch)
+ * th is the table Keras compares against -- th[0] = 0 - 1e-7, th[i] = i / (T - 1), th[T - 1] = 1 + 1e-7, in float64 -- and a sample
+ * with score p (float32 widened to double) and label y counts in pos (y != 0) or neg (y == 0) at
+ *   bucket = the number of thresholds t with !(p <= t):  0 .. T; a NaN score in T, -inf in 0, +inf in T,
+ * so that true positives at threshold i = the sum of pos[b] over b > i, false positives likewise over neg.
+ * n_correct counts ((p > 0.5 ? 1 : 0) == y); loss_sum adds -(y log(pc) + (1 - y) log(1 - pc)) with pc = p clipped to
+ * [1e-7, 1 - 1e-7], in double (a NaN score makes it NaN).  The counts are integer sums and exact.  loss_sum takes no floating-point
+ * atomic: after an update it is a function of the word before, the inputs and n alone, the same bits on every run.
+ * sprk_metrics_reset zeroes the counters and writes T and th.  sprk_metrics_update reads T from the state ON THE DEVICE (the host
+ * never reads the state): on a state that was never reset, or that is shorter than its own T needs, the update does nothing.
+ * label_storage is SPRK_COL_F32 / I32 / I64 / U8 / BOOL (the column packer's storage kinds, above), label_stride the distance in BYTES between two labels, a positive multiple of the label's size: a column of a
+ * wider row-major array is read in place.  n >= 0; n == 0 does nothing.  ONE STATE IS NOT RE-ENTRANT: the calls on it must be ordered
+ * on one stream (or by events); different states are independent.  NULL or misaligned pointers (state 16 bytes, scores 4, labels
+ * their own size), a short state, an unknown storage, a bad stride or a negative n return SPRK_EINVAL BEFORE any device call.
+ * Asynchronous on `stream`; no memory owned by the library; all index arithmetic in 64 bits. */
+#define SPRK_METRICS_MAX_THRESHOLDS 1024
+size_t sprk_metrics_state_bytes(int32_t num_thresholds);   /* 0 for num_thresholds outside [2, 1024] */
+int sprk_metrics_reset(void* state, size_t state_bytes, int32_t num_thresholds, void* stream);
+int sprk_metrics_update(void* state, size_t state_bytes, const float* scores, const void* labels, int32_t label_storage,
+                        int64_t label_stride /* bytes */, int64_t n, void* stream);
+
 /* ---- multi-GPU: the path's one collective (the reference has no distributed path) ----
  * Batch rows are sharded over one process per GPU, tables and weights replicated; every rank ends with all scores through ONE
  * all-gather of the per-rank score slices over RCCL / xGMI, enqueued on the caller's HIP stream (no host synchronisation).

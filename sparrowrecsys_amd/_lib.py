@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "sprk_pack_csv", "sprk_pack_csv_mt", "sprk_pack_csv_device", "sprk_csv_last_path",
     "sprk_pack_columns", "sprk_pack_columns_device", "sprk_pack_last_route", "sprk_set_many_streams", "sprk_set_many_batches", "sprk_emb_rank",
     "sprk_emb_topk", "sprk_emb_topk_workspace_bytes", "sprk_join_features", "sprk_rank_scores",
+    "sprk_metrics_state_bytes", "sprk_metrics_reset", "sprk_metrics_update",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -60,6 +61,7 @@ class PackCol(C.Structure):
 # sources of a JoinCol (include/sparrow_hip.h SPRK_JOIN_*)
 JOIN_PAIR_USER, JOIN_PAIR_MOVIE, JOIN_USER_ROW, JOIN_MOVIE_ROW = range(4)
 RANK_MAX_SORT = 4096
+METRICS_MAX_THRESHOLDS = 1024
 
 
 class JoinCol(C.Structure):
@@ -107,7 +109,7 @@ _lib = None
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
-    """Compile csrc/sparrow_hip.hip + csrc/tu_*.hip for gfx950 into the in-tree libsparrow_hip.so
+    """Compile csrc/sparrow_hip.hip + csrc/tu_*.hip + csrc/sparrow_metrics.hip for gfx950 into the in-tree libsparrow_hip.so
     (hipcc cross-compiles without a GPU)."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc)] + [os.path.join(INCLUDE_DIR, "sparrow_hip.h")]
@@ -139,13 +141,14 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
             tmp = "%s.tmp.%d" % (LIB_PATH, os.getpid())
             # [r5] seven translation units, compiled in parallel and linked: sparrow_hip.hip (host side, light kernels) and the kernel-family
             # units tu_1.hip .. tu_6.hip (csrc/tu_kernels.h; the heavy templates' instantiations, csrc/tu_instances.h).  One unit of
-            # 57-70 s until round 4.
+            # 57-70 s until round 4.  sparrow_metrics.hip (model.evaluate's accumulators, csrc/k_metrics.h) is an eighth, independent of the engine.
             import shutil
             import tempfile
             from concurrent.futures import ThreadPoolExecutor
             units = [SRC_PATH] + sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.startswith("tu_") and f.endswith(".hip"))
             if "SPRK_SINGLE_TU" in defines:                       # one unit: sparrow_hip.hip includes every kernel header itself
                 units = [SRC_PATH]
+            units.append(os.path.join(csrc, "sparrow_metrics.hip"))   # the evaluation metrics: a unit of their own, no part of the engine's
             flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
                      "-I", INCLUDE_DIR, "-I", csrc]               # [r6] hidden by default: include/sparrow_hip.h's declarations are the only exports
             if defines:                                           # experiment builds
@@ -256,8 +259,12 @@ def load_library():
         lib.sprk_join_features.argtypes = [vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, C.POINTER(JoinCol), i32, C.POINTER(JoinCol), i32,
                                            vp, vp, vp, vp]
         lib.sprk_rank_scores.argtypes = [vp, i32, i32, vp, vp]
+        lib.sprk_metrics_state_bytes.argtypes = [i32]
+        lib.sprk_metrics_state_bytes.restype = sz
+        lib.sprk_metrics_reset.argtypes = [vp, sz, i32, vp]
+        lib.sprk_metrics_update.argtypes = [vp, sz, vp, vp, i32, C.c_int64, C.c_int64, vp]
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

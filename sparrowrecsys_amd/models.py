@@ -561,6 +561,90 @@ class CTRModel:
         labels = np.concatenate([np.asarray(b[1]).astype(np.float64).reshape(-1) for b in batches])
         return evaluate_scores(labels, self.predict(batches, batch_size)[:, 0])
 
+    def evaluate_device(self, x, y=None, batch_size: Optional[int] = None, num_thresholds: int = 200):
+        """``evaluate`` with the metrics accumulated ON THE DEVICE (``metrics.DeviceMetrics`` over ``sprk_metrics_update``): takes what
+        ``evaluate`` takes and returns its list -- accuracy and both AUCs bit for bit, the loss up to the order of a float64 sum --
+        but consumes an iterable batch by batch (a generator is read once, nothing is kept), and no score comes back to the host:
+        batches are packed and scored as ``predict`` does, each group of equal-sized batches into ONE flat score buffer that one
+        update folds in with the group's labels (uploaded as one tensor; device labels are read where they are)."""
+        import torch
+
+        from .metrics import DeviceMetrics
+        eng = self.engine
+        dm = DeviceMetrics(num_thresholds)
+        pending = []
+
+        def flush():
+            if not pending:
+                return
+            B, n = int(pending[0][0].shape[0]), len(pending)
+            flat = torch.empty(n * B, dtype=torch.float32, device=pending[0][0].device)
+            if n == 1:
+                self.predict_device(pending[0][0], pending[0][1], flat)
+                labels = pending[0][2]
+            else:
+                self.predict_device_many([b[0] for b in pending], [b[1] for b in pending], [flat[i * B:(i + 1) * B] for i in range(n)])
+                if all(isinstance(b[2], torch.Tensor) and b[2].is_cuda for b in pending):
+                    labels = torch.cat([b[2].reshape(-1) for b in pending])
+                else:
+                    labels = np.concatenate([b[2].cpu().numpy().reshape(-1) if isinstance(b[2], torch.Tensor) else np.asarray(b[2]).reshape(-1) for b in pending])
+            dm.update(flat, labels)
+            pending.clear()
+
+        def batches():
+            if isinstance(x, Mapping):
+                labels = x["label"] if y is None else y
+                B = batch_size_of(x)
+                if batch_size is None or batch_size >= B:
+                    yield x, labels
+                else:
+                    for s in range(0, B, batch_size):
+                        yield {k: v[s:s + batch_size] for k, v in x.items()}, labels[s:s + batch_size]
+                return
+            for b in x:
+                if not (isinstance(b, (tuple, list)) and len(b) == 2 and isinstance(b[0], Mapping)):
+                    raise ValueError("evaluate: an iterable of (features, labels) batches, or a feature dict with labels, is required")
+                yield b[0], b[1]
+        seen = False
+        for feats, labels in batches():
+            seen = True
+            ids_t, dense_t = self.pack_device(feats)
+            B = int(ids_t.shape[0])
+            if (labels.numel() if isinstance(labels, torch.Tensor) else np.asarray(labels).size) != B:
+                raise ValueError("evaluate: a batch of %d rows with %d labels" % (B, labels.numel() if isinstance(labels, torch.Tensor) else np.asarray(labels).size))
+            if B == 0:
+                continue
+            if pending and (B != pending[0][0].shape[0] or len(pending) == self.MANY_GROUP):
+                flush()
+            pending.append((ids_t, dense_t, labels))
+        flush()
+        if not seen:
+            raise ValueError("evaluate: an iterable of (features, labels) batches, or a feature dict with labels, is required")
+        eng.check_ids()
+        return dm.result()
+
+    def evaluate_csv(self, source, label: str = "label", batch_size: int = 65536, max_rows: Optional[int] = None, num_thresholds: int = 200):
+        """``model.evaluate(get_dataset(path))`` of the reference (DeepFM.py:14-22,117-133) without the host in the data path:
+        ``predict_csv``'s route -- raw text to the device, ``sprk_pack_csv_device`` -- with the ``label`` column tokenized on the device
+        as one more dense column (an empty field is 0.0, the tokenizer's NA rule), the forward over a contiguous copy of the model's
+        own dense columns, and ONE metrics update that reads the label column where the tokenizer wrote it.  Neither a score nor a
+        label crosses to the host -> ``[loss, accuracy, roc_auc, pr_auc]``, as ``evaluate(read_samples_csv(path))`` gives them."""
+        from .ingest import pack_csv_device, read_csv_to_device
+        from .metrics import DeviceMetrics
+        if isinstance(source, str):
+            buf, nbytes = read_csv_to_device(source)
+            source = buf[:nbytes]
+        nd = len(self.numeric_keys)
+        ids, wide = pack_csv_device(source, self.id_columns, list(self.numeric_keys) + [label], max_rows=max_rows)
+        n = int(ids.shape[0])
+        dm = DeviceMetrics(num_thresholds)
+        if n == 0:
+            return dm.result()                                    # (raises: no sample was seen)
+        out = self._score_slices(ids, wide[:, :nd].contiguous(), batch_size)
+        dm.update(out, wide[:, nd])
+        self.engine.check_ids()
+        return dm.result()
+
     def predict_csv(self, source, batch_size: int = 65536, max_rows: Optional[int] = None) -> np.ndarray:
         """``model.predict(get_dataset(path))`` of the reference (DeepFM.py:14-22,131-133) without the host in the data path:
         ``source`` = a CSV file path, its bytes, or a ``torch.uint8`` device tensor holding the text.  The raw text goes to
@@ -576,6 +660,14 @@ class CTRModel:
         n = int(ids.shape[0])
         if n == 0:
             return np.zeros((0, 1), dtype=np.float32)
+        out = self._score_slices(ids, dense, batch_size)
+        self.engine.check_ids()
+        return out.cpu().numpy().reshape(-1, 1)
+
+    def _score_slices(self, ids, dense, batch_size: int):
+        """The forward over ``batch_size``-row slices of packed device arrays -> one device tensor ``[n]`` of scores (async)."""
+        import torch
+        n = int(ids.shape[0])
         out = torch.empty(n, dtype=torch.float32, device=ids.device)
         full = n // batch_size
         for g0 in range(0, full, self.MANY_GROUP):                # [r6] the full slices in groups of up to 64: one launch per group where the graph allows
@@ -587,8 +679,7 @@ class CTRModel:
         if full * batch_size < n:
             lo = full * batch_size
             self.predict_device(ids[lo:n], dense[lo:n], out[lo:n])
-        self.engine.check_ids()
-        return out.cpu().numpy().reshape(-1, 1)
+        return out
 
     # ---- (userId, movieId) pairs: the rest of the sample row comes from a FeatureStore, on the device ---------------------------
     def join_plan(self, store) -> "JoinPlan":
