@@ -497,6 +497,42 @@ int sprk_metrics_reset(void* state, size_t state_bytes, int32_t num_thresholds, 
 int sprk_metrics_update(void* state, size_t state_bytes, const float* scores, const void* labels, int32_t label_storage,
                         int64_t label_stride /* bytes */, int64_t n, void* stream);
 
+/* ---- feature engineering on the device: ratings -> training samples and the feature store's rows ----
+ * The arithmetic of the reference's Spark job (FeatureEngForRecModel.scala:21-130): label = rating >= 3.5; per movie over ALL ratings
+ * count / average / sample stddev; per user, in (timestamp, input row) order, the window of the previous 100 ratings -- its size, average,
+ * stddev, its label-1 movies most recent first, the five genres its label-1 movies carry most often -- and the samples whose window
+ * holds more than one rating.  The definition, rule by rule, is sparrowrecsys_amd/featureeng.py samples_host;
+ * this call gives the same bits.  Averages and deviations are rounded to hundredths in INTEGER arithmetic (round half to even of the
+ * exact rational, 128-bit products where a movie's count needs them) and stored as float32(h / 100.0); every sum is an integer
+ * atomic, so the result is a function of the input alone.
+ * In, device memory: the rating columns user_id, movie_id (int32), rating (float32, on the half-star scale 0, 0.5 .. 10), timestamp
+ * (int64), n_ratings rows in any order; the movie table, n_movies rows indexed by movie id: movie_year (releaseYear; 1990 for a movie
+ * the table does not hold), movie_genre3 [n_movies][3] (movieGenre1..3 as vocabulary index or -1), movie_genre_mask (bit g = the movie
+ * carries genre g of a dictionary of at most 32 genres whose first n_vocab entries are the vocabulary).
+ * Out, device memory, each holding n_ratings rows of which the first *n_kept are written, in (userId, timestamp, input row) order:
+ * out_user, out_movie, out_rating, out_timestamp, out_label, out_source_row (the input row), out_genres [.][8] (movieGenre1..3,
+ * userGenre1..5; a genre past n_vocab is -1 in its place), out_history [.][hist_len] (userRatedMovie1.., missing 0), out_dense [.][7]
+ * (releaseYear, movieRatingCount, movieAvgRating, movieRatingStddev, userRatingCount, userAvgRating, userRatingStddev).
+ * *n_kept = the sum over users of max(0, ratings of the user - 2).  Optionally the store in sparrowrecsys_amd/featurestore.py's layout,
+ * every row written: user_rows [n_users][user_pitch], user_has [n_users], movie_rows [n_movies][8], movie_has [n_movies] -- all four
+ * or none (NULL).  `error_key` is ONE caller-provided device word, set to ~0 before the call: the kernels atomicMin
+ * (kind << 32 | input row) into it, kind 1 = user_id outside [0, n_users), 2 = movie_id outside [0, n_movies), 3 = rating off the
+ * half-star scale; when it is not ~0 afterwards the outputs hold no result.  Such rows take no further part, so no index leaves its
+ * array.  The workspace is sprk_feature_eng_workspace_bytes(n_ratings, n_users, n_movies) bytes, 16-byte aligned (0 for sizes the call
+ * rejects).  A user's ratings are sorted in LDS up to 4096 of them (SPRK_FE_SORT_CAP = a power of two in [64, 4096], read at each call,
+ * lowers that) and by chunked sort + merge passes in global memory beyond; any length up to n_ratings works.
+ * 0 <= n_ratings < 2^31 - 1, 0 <= n_users < 2^31 - 1, n_movies >= 0, 1 <= hist_len <= 100, 0 <= n_vocab <= 32, user_pitch >= hist_len + 8,
+ * no NULL or misaligned pointer, a sufficient workspace: anything else returns SPRK_EINVAL BEFORE any device call.  Asynchronous on
+ * `stream`: no synchronisation, no memory owned by the library; all index arithmetic in 64 bits. */
+size_t sprk_feature_eng_workspace_bytes(int64_t n_ratings, int32_t n_users, int32_t n_movies);
+int sprk_feature_eng(const int32_t* user_id, const int32_t* movie_id, const float* rating, const int64_t* timestamp, int64_t n_ratings,
+                     int32_t n_users, int32_t n_movies, const int32_t* movie_year, const int32_t* movie_genre3, const uint32_t* movie_genre_mask,
+                     int32_t n_vocab, int32_t hist_len,
+                     int32_t* out_user, int32_t* out_movie, float* out_rating, int64_t* out_timestamp, int32_t* out_label, int32_t* out_source_row,
+                     int32_t* out_genres, int32_t* out_history, float* out_dense,
+                     int32_t* user_rows, uint8_t* user_has, int32_t user_pitch, int32_t* movie_rows, uint8_t* movie_has,
+                     uint64_t* error_key, int64_t* n_kept, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- multi-GPU: the path's one collective (the reference has no distributed path) ----
  * Batch rows are sharded over one process per GPU, tables and weights replicated; every rank ends with all scores through ONE
  * all-gather of the per-rank score slices over RCCL / xGMI, enqueued on the caller's HIP stream (no host synchronisation).

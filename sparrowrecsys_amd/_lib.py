@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "sprk_pack_columns", "sprk_pack_columns_device", "sprk_pack_last_route", "sprk_set_many_streams", "sprk_set_many_batches", "sprk_emb_rank",
     "sprk_emb_topk", "sprk_emb_topk_workspace_bytes", "sprk_join_features", "sprk_rank_scores",
     "sprk_metrics_state_bytes", "sprk_metrics_reset", "sprk_metrics_update",
+    "sprk_feature_eng_workspace_bytes", "sprk_feature_eng",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -109,7 +110,7 @@ _lib = None
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
-    """Compile csrc/sparrow_hip.hip + csrc/tu_*.hip + csrc/sparrow_metrics.hip for gfx950 into the in-tree libsparrow_hip.so
+    """Compile csrc/sparrow_hip.hip + csrc/tu_*.hip + csrc/sparrow_metrics.hip + csrc/sparrow_feature_eng.hip for gfx950 into the in-tree libsparrow_hip.so
     (hipcc cross-compiles without a GPU)."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc)] + [os.path.join(INCLUDE_DIR, "sparrow_hip.h")]
@@ -149,6 +150,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
             if "SPRK_SINGLE_TU" in defines:                       # one unit: sparrow_hip.hip includes every kernel header itself
                 units = [SRC_PATH]
             units.append(os.path.join(csrc, "sparrow_metrics.hip"))   # the evaluation metrics: a unit of their own, no part of the engine's
+            units.append(os.path.join(csrc, "sparrow_feature_eng.hip"))   # ratings -> samples and store rows (featureeng.py): likewise
             flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
                      "-I", INCLUDE_DIR, "-I", csrc]               # [r6] hidden by default: include/sparrow_hip.h's declarations are the only exports
             if defines:                                           # experiment builds
@@ -263,8 +265,14 @@ def load_library():
         lib.sprk_metrics_state_bytes.restype = sz
         lib.sprk_metrics_reset.argtypes = [vp, sz, i32, vp]
         lib.sprk_metrics_update.argtypes = [vp, sz, vp, vp, i32, C.c_int64, C.c_int64, vp]
+        lib.sprk_feature_eng_workspace_bytes.argtypes = [C.c_int64, i32, i32]
+        lib.sprk_feature_eng_workspace_bytes.restype = sz
+        lib.sprk_feature_eng.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, i32, i32,      # ratings, sizes, movie table, n_vocab, hist_len
+                                         vp, vp, vp, vp, vp, vp, vp, vp, vp,                             # the sample columns
+                                         vp, vp, i32, vp, vp,                                            # the store's tables (or NULL)
+                                         vp, vp, vp, sz, vp]                                             # error word, sample count, workspace, stream
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

@@ -1,0 +1,390 @@
+// k_feature_eng.h -- ratings -> training samples and the feature store's rows, on the device (FeatureEngForRecModel.scala:21-130: label,
+// movie aggregates, the previous-100-ratings window of every user).  The definition these kernels equal bit for bit is
+// sparrowrecsys_amd/featureeng.py samples_host; DESIGN.md section 5.7 has the rules.  Part of sparrow_feature_eng.hip.
+//
+// Stages, one stream, no host synchronisation (api_feature_eng.h launches them in this order):
+//   k_fe_hist       per rating: validate (error word), count the user's ratings, add the movie's n / S / Q      (integer atomics)
+//   k_fe_scan_*     exclusive scans over users of len and of kept = max(0, len - 2): segment and sample offsets
+//   k_fe_scatter    per rating: (timestamp, input row) into its user's segment, any order (the sort key is total)
+//   k_fe_sort_short one workgroup per user: segments of up to `cap` ratings sorted in LDS; longer ones are listed
+//   k_fe_sort_long_chunks + k_fe_merge_pass x ceil(log2(n / cap)) (+ k_fe_long_copy): the listed segments, sorted in chunks of `cap`
+//                   and merged in global memory by rank (keys are distinct: rank in the partner run = one binary search)
+//   k_fe_movie_stats per movie: the four float32 of the store's movie row
+//   k_fe_window     per sorted position: the window's count / S / Q, last positives, 32 genre counters, top five; writes the sample
+//   k_fe_store      per user and per movie: the store's rows and `has` bytes
+// All sums are integer sums: the result is a function of the input alone.
+
+static constexpr int FE_THREADS = 256;
+static constexpr int FE_SORT_CAP = 4096;          // ratings of one user sorted in LDS: 4096 x 12 bytes = 48 KB, three workgroups per CU
+static constexpr int FE_WINDOW = 100;             // rowsBetween(-100, -1)
+static constexpr int FE_SCAN_TILE = 4 * FE_THREADS;
+static constexpr int FE_MAX_GRID = 2048;
+static constexpr int FE_POSITIVE_R2 = 7;          // label = rating >= 3.5
+static constexpr unsigned long long FE_ERR_USER = 1, FE_ERR_MOVIE = 2, FE_ERR_RATING = 3;
+
+// 2 * rating as an integer in [0, 20], or -1 for a rating off the half-star scale (NaN included)
+__device__ inline int fe_r2(float r) {
+    const float t = r * 2.0f;
+    if (!(t >= 0.0f && t <= 20.0f)) return -1;
+    const int k = (int)t;
+    return (float)k == t ? k : -1;
+}
+
+// round-half-to-even of 50 S / n: the average rating in hundredths (S = the sum of 2 * rating)
+__host__ __device__ inline unsigned fe_avg_h(unsigned long long n, unsigned long long S) {
+    if (n == 0) return 0;
+    const unsigned long long a = 50ull * S, q = a / n, r = a % n;
+    return (unsigned)(q + ((2 * r > n || (2 * r == n && (q & 1))) ? 1 : 0));
+}
+
+// round-half-to-even of 100 sqrt(N / (4 d)), N = n Q - S^2, d = n (n - 1): the sample standard deviation in hundredths, decided in
+// integers of type W (64 bits for a window of n <= 100, 128 for a movie's count up to 2^31).  h <= 708 (two ratings, 0 and 10).
+template <class W> __host__ __device__ inline unsigned fe_sd_h(unsigned long long n, unsigned long long S, unsigned long long Q) {
+    if (n < 2) return 0;
+    const W N = (W)n * (W)Q - (W)S * (W)S, d = (W)n * (W)(n - 1), R = N * (W)10000;
+    unsigned long long h = 0;
+    for (unsigned long long bit = 512; bit; bit >>= 1) {           // floor: the greatest h with (2 h)^2 d <= 10^4 N
+        const unsigned long long c = h | bit;
+        if ((W)(4 * c * c) * d <= R) h = c;
+    }
+    const W t = (W)((2 * h + 1) * (2 * h + 1)) * d;
+    if (t < R || (t == R && (h & 1))) ++h;
+    return (unsigned)h;
+}
+
+__device__ inline float fe_hundredths(unsigned h) { return (float)((double)h / 100.0); }
+
+__device__ inline bool fe_key_less(long long ta, int ra, long long tb, int rb) { return ta < tb || (ta == tb && ra < rb); }
+
+// exclusive scan of one value per thread over the workgroup (FE_THREADS); sh holds FE_THREADS words
+__device__ inline unsigned fe_block_scan(unsigned v, unsigned* sh, unsigned* total) {
+    const int t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (int d = 1; d < FE_THREADS; d <<= 1) {
+        const unsigned a = t >= d ? sh[t - d] : 0u;
+        __syncthreads();
+        sh[t] += a;
+        __syncthreads();
+    }
+    const unsigned incl = sh[t];
+    *total = sh[FE_THREADS - 1];
+    __syncthreads();
+    return incl - v;
+}
+
+__global__ __launch_bounds__(FE_THREADS) void k_fe_hist(long long n, const int* __restrict__ user, const int* __restrict__ movie, const float* __restrict__ rating,
+                                                        int n_users, int n_movies, unsigned* __restrict__ len, unsigned* __restrict__ mv_cnt,
+                                                        unsigned long long* __restrict__ mv_S, unsigned long long* __restrict__ mv_Q,
+                                                        unsigned long long* __restrict__ err) {
+    for (long long i = (long long)blockIdx.x * FE_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * FE_THREADS) {
+        const int u = user[i], m = movie[i], r2 = fe_r2(rating[i]);
+        const unsigned long long kind = (u < 0 || u >= n_users) ? FE_ERR_USER : (m < 0 || m >= n_movies) ? FE_ERR_MOVIE : r2 < 0 ? FE_ERR_RATING : 0;
+        if (kind) { atomicMin(err, kind << 32 | (unsigned long long)i); continue; }      // (the row takes no further part: every later index stays in range)
+        atomicAdd(&len[u], 1u);
+        atomicAdd(&mv_cnt[m], 1u);
+        atomicAdd(&mv_S[m], (unsigned long long)r2);
+        atomicAdd(&mv_Q[m], (unsigned long long)(r2 * r2));
+    }
+}
+
+// seg[i] = len_i, kept[i] = (unwritten) for i in [0, count): both become tile-local exclusive scans, the tiles' totals go to tops
+__global__ __launch_bounds__(FE_THREADS) void k_fe_scan_tiles(unsigned* __restrict__ seg, unsigned* __restrict__ kept, long long count, unsigned* __restrict__ tops, int n_tiles) {
+    __shared__ unsigned sh[FE_THREADS];
+    const long long base = (long long)blockIdx.x * FE_SCAN_TILE + (long long)threadIdx.x * 4;
+    unsigned a[4], b[4], sa = 0, sb = 0;
+    for (int k = 0; k < 4; ++k) {
+        a[k] = base + k < count ? seg[base + k] : 0u;
+        b[k] = a[k] > 2 ? a[k] - 2 : 0u;
+        sa += a[k]; sb += b[k];
+    }
+    unsigned ta, tb;
+    unsigned ea = fe_block_scan(sa, sh, &ta);
+    unsigned eb = fe_block_scan(sb, sh, &tb);
+    for (int k = 0; k < 4; ++k) {
+        if (base + k < count) { seg[base + k] = ea; kept[base + k] = eb; }
+        ea += a[k]; eb += b[k];
+    }
+    if (threadIdx.x == 0) { tops[blockIdx.x] = ta; tops[n_tiles + blockIdx.x] = tb; }
+}
+
+// one workgroup: tops[0..n_tiles) and tops[n_tiles..2 n_tiles) become exclusive scans
+__global__ __launch_bounds__(FE_THREADS) void k_fe_scan_tops(unsigned* __restrict__ tops, int n_tiles) {
+    __shared__ unsigned sh[FE_THREADS];
+    for (int w = 0; w < 2; ++w) {
+        unsigned* t = tops + (size_t)w * n_tiles;
+        unsigned carry = 0;
+        for (int b0 = 0; b0 < n_tiles; b0 += FE_THREADS) {
+            const int i = b0 + threadIdx.x;
+            const unsigned v = i < n_tiles ? t[i] : 0u;
+            unsigned total;
+            const unsigned e = fe_block_scan(v, sh, &total);
+            if (i < n_tiles) t[i] = carry + e;
+            carry += total;
+        }
+    }
+}
+
+// adds the tiles' offsets; element count - 1 (the one past the last user) then holds the totals: the number of kept samples goes to n_kept
+__global__ __launch_bounds__(FE_THREADS) void k_fe_scan_add(unsigned* __restrict__ seg, unsigned* __restrict__ kept, long long count, const unsigned* __restrict__ tops, int n_tiles,
+                                                            long long* __restrict__ n_kept) {
+    const long long i = (long long)blockIdx.x * FE_THREADS + threadIdx.x;
+    if (i >= count) return;
+    const int tile = (int)(i / FE_SCAN_TILE);
+    seg[i] += tops[tile];
+    const unsigned k = kept[i] + tops[n_tiles + tile];
+    kept[i] = k;
+    if (i == count - 1) *n_kept = (long long)k;
+}
+
+__global__ __launch_bounds__(FE_THREADS) void k_fe_scatter(long long n, const int* __restrict__ user, const int* __restrict__ movie, const float* __restrict__ rating,
+                                                           const long long* __restrict__ ts, int n_users, int n_movies, const unsigned* __restrict__ seg_off,
+                                                           unsigned* __restrict__ cursor, long long* __restrict__ seg_ts, int* __restrict__ seg_row, int* __restrict__ seg_user) {
+    for (long long i = (long long)blockIdx.x * FE_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * FE_THREADS) {
+        const int u = user[i], m = movie[i];
+        if (u < 0 || u >= n_users || m < 0 || m >= n_movies || fe_r2(rating[i]) < 0) continue;      // k_fe_hist's predicate
+        const size_t pos = (size_t)seg_off[u] + atomicAdd(&cursor[u], 1u);                             // < seg_off[u + 1]: the same rows were counted
+        seg_ts[pos] = ts[i];
+        seg_row[pos] = (int)i;
+        seg_user[pos] = u;
+    }
+}
+
+// sorts count <= cap keys at (gts, grow) by (timestamp, input row) in LDS: bitonic over P = the next power of two, padded with keys greater
+// than any real one (input rows are < 2^31 - 1)
+__device__ inline void fe_sort_lds(long long* __restrict__ gts, int* __restrict__ grow, int count, long long* sts, int* srow) {
+    int P = 2;
+    while (P < count) P <<= 1;
+    for (int i = threadIdx.x; i < P; i += FE_THREADS) {
+        sts[i] = i < count ? gts[i] : 0x7fffffffffffffffll;
+        srow[i] = i < count ? grow[i] : 0x7fffffff;
+    }
+    __syncthreads();
+    for (int k = 2; k <= P; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = threadIdx.x; i < P; i += FE_THREADS) {
+                const int x = i ^ j;
+                if (x > i) {
+                    const long long ta = sts[i], tb = sts[x];
+                    const int ra = srow[i], rb = srow[x];
+                    const bool up = (i & k) == 0;
+                    if (fe_key_less(tb, rb, ta, ra) == up) { sts[i] = tb; sts[x] = ta; srow[i] = rb; srow[x] = ra; }
+                }
+            }
+            __syncthreads();
+        }
+    for (int i = threadIdx.x; i < count; i += FE_THREADS) { gts[i] = sts[i]; grow[i] = srow[i]; }
+    __syncthreads();
+}
+
+// dynamic LDS: cap x 8 bytes of timestamps, then cap x 4 bytes of rows
+__global__ __launch_bounds__(FE_THREADS) void k_fe_sort_short(int n_users, int cap, const unsigned* __restrict__ seg_off, long long* __restrict__ seg_ts, int* __restrict__ seg_row,
+                                                              int* __restrict__ long_list, unsigned* __restrict__ n_long) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char fe_lds[];
+    long long* sts = (long long*)fe_lds;
+    int* srow = (int*)(fe_lds + (size_t)cap * 8);
+    for (int u = blockIdx.x; u < n_users; u += gridDim.x) {
+        const unsigned base = seg_off[u], len = seg_off[u + 1] - base;
+        if (len < 2) continue;
+        if (len <= (unsigned)cap) fe_sort_lds(seg_ts + base, seg_row + base, (int)len, sts, srow);
+        else if (threadIdx.x == 0) long_list[atomicAdd(n_long, 1u)] = u;        // at most n / (cap + 1) users: the list holds n / 64 + 1
+    }
+}
+
+__global__ __launch_bounds__(FE_THREADS) void k_fe_sort_long_chunks(int cap, const unsigned* __restrict__ seg_off, long long* __restrict__ seg_ts, int* __restrict__ seg_row,
+                                                                    const int* __restrict__ long_list, const unsigned* __restrict__ n_long) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char fe_lds[];
+    long long* sts = (long long*)fe_lds;
+    int* srow = (int*)(fe_lds + (size_t)cap * 8);
+    const unsigned nl = *n_long;
+    for (unsigned s = 0; s < nl; ++s) {
+        const int u = long_list[s];
+        const unsigned base = seg_off[u], len = seg_off[u + 1] - base;
+        const unsigned chunks = (len + cap - 1) / cap;
+        for (unsigned c = blockIdx.x; c < chunks; c += gridDim.x) {
+            const unsigned o = c * (unsigned)cap, cnt = len - o < (unsigned)cap ? len - o : (unsigned)cap;
+            fe_sort_lds(seg_ts + base + o, seg_row + base + o, (int)cnt, sts, srow);
+        }
+    }
+}
+
+// one merge level of every listed segment: sorted runs of `width` keys pair up; a key's place in the merged pair is its index in its own
+// run plus its rank in the partner run.  A run without a partner (and a segment of one run) is copied, so all segments move src -> dst together.
+__global__ __launch_bounds__(FE_THREADS) void k_fe_merge_pass(long long width, const unsigned* __restrict__ seg_off, const long long* __restrict__ src_ts, const int* __restrict__ src_row,
+                                                              long long* __restrict__ dst_ts, int* __restrict__ dst_row, const int* __restrict__ long_list,
+                                                              const unsigned* __restrict__ n_long) {
+    const unsigned nl = *n_long;
+    for (unsigned s = 0; s < nl; ++s) {
+        const int u = long_list[s];
+        const long long base = seg_off[u], len = (long long)seg_off[u + 1] - base;
+        for (long long p = (long long)blockIdx.x * FE_THREADS + threadIdx.x; p < len; p += (long long)gridDim.x * FE_THREADS) {
+            const long long run = p / width, rs = run * width, ps = (run ^ 1) * width;
+            const long long t = src_ts[base + p];
+            const int r = src_row[base + p];
+            long long out = p;
+            if (ps < len) {
+                long long lo = ps, hi = ps + width < len ? ps + width : len;            // the partner's keys less than this one: [ps, lo)
+                while (lo < hi) {
+                    const long long mid = (lo + hi) >> 1;
+                    if (fe_key_less(src_ts[base + mid], src_row[base + mid], t, r)) lo = mid + 1; else hi = mid;
+                }
+                out = (rs < ps ? rs : ps) + (p - rs) + (lo - ps);                         // < the pair's end <= len
+            }
+            dst_ts[base + out] = t;
+            dst_row[base + out] = r;
+        }
+    }
+}
+
+__global__ __launch_bounds__(FE_THREADS) void k_fe_long_copy(const unsigned* __restrict__ seg_off, const long long* __restrict__ src_ts, const int* __restrict__ src_row,
+                                                             long long* __restrict__ dst_ts, int* __restrict__ dst_row, const int* __restrict__ long_list,
+                                                             const unsigned* __restrict__ n_long) {
+    const unsigned nl = *n_long;
+    for (unsigned s = 0; s < nl; ++s) {
+        const int u = long_list[s];
+        const long long base = seg_off[u], len = (long long)seg_off[u + 1] - base;
+        for (long long p = (long long)blockIdx.x * FE_THREADS + threadIdx.x; p < len; p += (long long)gridDim.x * FE_THREADS) {
+            dst_ts[base + p] = src_ts[base + p];
+            dst_row[base + p] = src_row[base + p];
+        }
+    }
+}
+
+// mv_dense[m] = {releaseYear, movieRatingCount, movieAvgRating, movieRatingStddev} as float32 bits
+__global__ __launch_bounds__(FE_THREADS) void k_fe_movie_stats(int n_movies, const int* __restrict__ mv_year, const unsigned* __restrict__ mv_cnt,
+                                                               const unsigned long long* __restrict__ mv_S, const unsigned long long* __restrict__ mv_Q, float* __restrict__ mv_dense) {
+    const int m = blockIdx.x * FE_THREADS + threadIdx.x;
+    if (m >= n_movies) return;
+    const unsigned long long n = mv_cnt[m], S = mv_S[m], Q = mv_Q[m];
+    float* o = mv_dense + (size_t)m * 4;
+    o[0] = (float)mv_year[m];
+    o[1] = (float)(unsigned)n;
+    o[2] = fe_hundredths(fe_avg_h(n, S));
+    o[3] = fe_hundredths(fe_sd_h<unsigned __int128>(n, S, Q));
+}
+
+// bit g of b (8 bits) -> byte g of the result = 1
+__device__ inline unsigned long long fe_spread8(unsigned b) {
+    const unsigned long long x = ((unsigned long long)b * 0x0101010101010101ull) & 0x8040201008040201ull;
+    return ((x + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;
+}
+
+// One thread per sorted position.  The workgroup's FE_THREADS positions and the FE_WINDOW before them sit in LDS (movie, genre mask,
+// 2 * rating); a thread walks its window backwards: most recent first, which is the order of userRatedMovie1.. .  The 32 genre counters
+// (<= 100 each) are bytes of four 64-bit registers.
+__global__ __launch_bounds__(FE_THREADS) void k_fe_window(const unsigned* __restrict__ seg_off, const unsigned* __restrict__ kept_off, int n_users,
+                                                          const long long* __restrict__ seg_ts, const int* __restrict__ seg_row, const int* __restrict__ seg_user,
+                                                          const int* __restrict__ movie, const float* __restrict__ rating,
+                                                          const int* __restrict__ mv_genre3, const unsigned* __restrict__ mv_mask, const float* __restrict__ mv_dense,
+                                                          unsigned* __restrict__ mv_flag, int n_vocab, int H,
+                                                          int* __restrict__ out_user, int* __restrict__ out_movie, float* __restrict__ out_rating, long long* __restrict__ out_ts,
+                                                          int* __restrict__ out_label, int* __restrict__ out_src, int* __restrict__ out_genres, int* __restrict__ out_hist,
+                                                          float* __restrict__ out_dense) {
+    __shared__ int s_movie[FE_THREADS + FE_WINDOW];
+    __shared__ unsigned s_mask[FE_THREADS + FE_WINDOW];
+    __shared__ unsigned char s_r2[FE_THREADS + FE_WINDOW];
+    const long long total = seg_off[n_users];
+    const long long b0 = (long long)blockIdx.x * FE_THREADS;
+    if (b0 >= total) return;                                                   // (the whole workgroup)
+    const long long lo = b0 - FE_WINDOW;
+    for (int i = threadIdx.x; i < FE_THREADS + FE_WINDOW; i += FE_THREADS) {
+        const long long q = lo + i;
+        if (q >= 0 && q < total) {
+            const int row = seg_row[q], m = movie[row];
+            s_movie[i] = m;
+            s_mask[i] = mv_mask[m];
+            s_r2[i] = (unsigned char)fe_r2(rating[row]);
+        }
+    }
+    __syncthreads();
+    const long long pos = b0 + threadIdx.x;
+    if (pos >= total) return;
+    const int u = seg_user[pos];
+    const long long start = seg_off[u], p = pos - start;
+    if (p < 2) return;                                                         // userRatingCount <= 1: dropped
+    const size_t j = (size_t)kept_off[u] + (size_t)(p - 2);
+    const int me = (int)(pos - lo);
+    const int first = (int)((pos - FE_WINDOW > start ? pos - FE_WINDOW : start) - lo);
+    unsigned S = 0, Q = 0;
+    int n_pos = 0;
+    unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    int* hist = out_hist + j * (size_t)H;
+    for (int i = me - 1; i >= first; --i) {
+        const unsigned r2 = s_r2[i];
+        S += r2; Q += r2 * r2;
+        if (r2 >= FE_POSITIVE_R2) {
+            if (n_pos < H) hist[n_pos] = s_movie[i];
+            ++n_pos;
+            const unsigned g = s_mask[i];
+            c0 += fe_spread8(g & 255u); c1 += fe_spread8((g >> 8) & 255u); c2 += fe_spread8((g >> 16) & 255u); c3 += fe_spread8(g >> 24);
+        }
+    }
+    for (int k = n_pos; k < H; ++k) hist[k] = 0;
+    // top five of (count desc, dictionary id asc) among count > 0: keys count << 5 | (31 - id), kept sorted by insertion
+    unsigned top[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+    for (int g = 0; g < 32; ++g) {
+        const unsigned long long w = g < 8 ? c0 : g < 16 ? c1 : g < 24 ? c2 : c3;
+        const unsigned c = (unsigned)(w >> ((g & 7) * 8)) & 255u;
+        unsigned key = c ? (c << 5 | (unsigned)(31 - g)) : 0u;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const unsigned hi = top[k] > key ? top[k] : key;
+            key = top[k] > key ? key : top[k];
+            top[k] = hi;
+        }
+    }
+    const int row = seg_row[pos], m = s_movie[me];
+    const unsigned r2 = s_r2[me];
+    const int count = me - first;
+    out_user[j] = u;
+    out_movie[j] = m;
+    out_rating[j] = rating[row];
+    out_ts[j] = seg_ts[pos];
+    out_label[j] = r2 >= FE_POSITIVE_R2 ? 1 : 0;
+    out_src[j] = row;
+    int* og = out_genres + j * 8;
+    for (int k = 0; k < 3; ++k) og[k] = mv_genre3[(size_t)m * 3 + k];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int id = 31 - (int)(top[k] & 31u);
+        og[3 + k] = (top[k] && id < n_vocab) ? id : -1;                        // a genre outside the vocabulary holds its place as -1
+    }
+    float* od = out_dense + j * 7;
+    const float* md = mv_dense + (size_t)m * 4;
+    for (int k = 0; k < 4; ++k) od[k] = md[k];
+    od[4] = (float)count;
+    od[5] = fe_hundredths(fe_avg_h((unsigned long long)count, S));
+    od[6] = fe_hundredths(fe_sd_h<unsigned long long>((unsigned long long)count, S, Q));
+    mv_flag[m] = 1u;                                                           // (every writer stores the same word)
+}
+
+// The store (featurestore.py's layout).  User row = the user's last kept sample: history | userGenre1..5 | count avg stddev | zeros.
+// Movie row = movieGenre1..3 | year count avg stddev | 0 of any kept sample that names the movie: these columns depend on the movie
+// alone, so the latest such sample's are every such sample's.  An id without a kept sample: the NA defaults and has = 0.
+__global__ __launch_bounds__(FE_THREADS) void k_fe_store(int n_users, int n_movies, int H, int user_pitch, const unsigned* __restrict__ kept_off,
+                                                         const int* __restrict__ out_genres, const int* __restrict__ out_hist, const float* __restrict__ out_dense,
+                                                         const int* __restrict__ mv_genre3, const float* __restrict__ mv_dense, const unsigned* __restrict__ mv_flag,
+                                                         int* __restrict__ user_rows, unsigned char* __restrict__ user_has, int* __restrict__ movie_rows,
+                                                         unsigned char* __restrict__ movie_has) {
+    const long long i = (long long)blockIdx.x * FE_THREADS + threadIdx.x;
+    if (i < n_users) {
+        int* row = user_rows + (size_t)i * user_pitch;
+        const unsigned k0 = kept_off[i], k1 = kept_off[i + 1];
+        const bool has = k1 > k0;
+        const size_t j = has ? (size_t)k1 - 1 : 0;
+        for (int k = 0; k < H; ++k) row[k] = has ? out_hist[j * (size_t)H + k] : 0;
+        for (int k = 0; k < 5; ++k) row[H + k] = has ? out_genres[j * 8 + 3 + k] : -1;
+        for (int k = 0; k < 3; ++k) row[H + 5 + k] = has ? __float_as_int(out_dense[j * 7 + 4 + k]) : 0;
+        for (int k = H + 8; k < user_pitch; ++k) row[k] = 0;
+        user_has[i] = has ? 1 : 0;
+    }
+    if (i < n_movies) {
+        int* row = movie_rows + (size_t)i * 8;
+        const bool has = mv_flag[i] != 0;
+        for (int k = 0; k < 3; ++k) row[k] = has ? mv_genre3[(size_t)i * 3 + k] : -1;
+        for (int k = 0; k < 4; ++k) row[3 + k] = has ? __float_as_int(mv_dense[(size_t)i * 4 + k]) : 0;
+        row[7] = 0;
+        movie_has[i] = has ? 1 : 0;
+    }
+}

@@ -1,0 +1,26 @@
+// sparrow_feature_eng.hip -- ratings -> training samples and the feature store's rows on the device: the kernels (k_feature_eng.h) and
+// their C ABI (api_feature_eng.h: sprk_feature_eng_workspace_bytes / sprk_feature_eng).  A translation unit of its own, like
+// sparrow_metrics.hip: nothing here is used by the forward engine and nothing of the engine is used here.  Shares with the other units
+// only host_common.h (the thread's error string behind sprk_last_error, HIP_TRY, the roctx ranges), which opens the kernels' namespace
+// this file closes.
+#include <hip/hip_runtime.h>
+#include <dlfcn.h>
+#include <unistd.h>
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "sparrow_hip.h"
+
+#include "host_common.h"
+#include "k_feature_eng.h"
+
+}  // namespace sprk_dev
+#pragma GCC visibility pop
+using namespace sprk_dev;
+
+#include "api_feature_eng.h"

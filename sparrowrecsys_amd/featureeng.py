@@ -1,0 +1,420 @@
+"""Feature engineering: ``ratings.csv`` + ``movies.csv`` -> the training samples and the feature store, without Spark.
+
+The reference builds its samples (``testSamples.csv``) and its ``uf:`` / ``mf:`` feature hashes with a Spark job,
+``FeatureEngForRecModel`` (FeatureEngForRecModel.scala:21-130; the PySpark twin is the same).  This module is that job's arithmetic:
+:func:`samples_host` is the DEFINITION, in numpy and integer arithmetic, and :func:`build` computes the same bits on the device
+(``sprk_feature_eng``, csrc/k_feature_eng.h).  The rules (DESIGN.md section 5.7 has them with their sources):
+
+* ``label = rating >= 3.5``.
+* Movie side: ``releaseYear`` from the title -- with ``t = title.trim``: 1990 if ``len(t) < 6``, else ``int(t[len(title) - 5 : len(title) - 1])``,
+  the indices taken from the UNTRIMMED length as the reference does; ``movieGenre1..3`` = the first three ``|``-separated genres; a rating
+  whose movie the table does not hold gets 1990 and no genres.  Per movie over ALL ratings: ``movieRatingCount``, ``movieAvgRating``,
+  ``movieRatingStddev`` (sample stddev; 0 for a single rating).
+* User side: within a user the ratings are ordered by timestamp; the window of the rating at position p is positions
+  ``[max(0, p - 100), p - 1]`` (rows, not time).  ``userRatingCount`` is its size, ``userAvgRating`` / ``userRatingStddev`` its ratings' average
+  and sample stddev, ``userRatedMovie1..`` its label-1 movies, most recent first, ``userGenre1..5`` the genres of its label-1 movies (a
+  movie's WHOLE genre list counts) by count descending.  Rows with ``userRatingCount <= 1`` are dropped.
+* ``userAvgReleaseYear`` and ``userReleaseYearStddev``, which the reference also writes, are no columns of ``schema.py`` and no model
+  reads them: they are left out.
+
+Two places where Spark leaves the result open are fixed here (deviations):
+
+* equal timestamps within a user are ordered by input row: the sort key ``(userId, timestamp, input row)`` is total;
+* equal genre counts: the genre with the lower id in the genre dictionary wins (Scala iterates a hash map).  The dictionary is
+  ``schema.GENRE_VOCAB`` in its order, then every other genre string of the movie table in order of first appearance ("(no genres
+  listed)" in MovieLens); at most 32 entries.  A genre outside the vocabulary competes for its place as in the reference and is
+  written as -1, which is what the column packer makes of it.
+
+Rounding is decided in integers.  Ratings are on the half-star scale, ``r2 = 2 rating`` an integer in [0, 20]; for n ratings with
+``S = sum r2``, ``Q = sum r2^2``: :func:`avg_h` ``= RHE(50 S / n)`` and :func:`sd_h` ``= RHE(100 sqrt(N / (4 d)))``, ``N = n Q - S^2``,
+``d = n (n - 1)``, both in hundredths, RHE = round half to even of the exact value; the stored float32 is ``float32(h / 100.0)``, which
+equals ``float32("%.2f" % (h / 100))``.  Counts and ``releaseYear`` are ``float32(int)``; missing history is 0, a missing genre -1.
+
+Parity with the reference: the movie side and the rounding are pinned by the reference's own data (tests/test_featureeng.py); the
+reference does not ship ``ratings.csv``, so the user windows are pinned by this definition and hand-worked examples.
+
+Out of scope: feeding the device-resident samples straight into ``evaluate_device`` (use ``.to_host()``), and updating an existing
+store incrementally from new ratings.
+"""
+from __future__ import annotations
+
+import csv
+import re
+from collections import namedtuple
+from typing import Mapping, Optional
+
+import numpy as np
+
+from . import schema as S
+
+WINDOW = 100
+POSITIVE_R2 = 7                       # label = rating >= 3.5
+DEFAULT_YEAR = 1990
+MAX_GENRES = 32
+_ID_LIMIT = (1 << 31) - 1
+_JAVA_BLANKS = "".join(chr(c) for c in range(33))          # String.trim strips every char <= U+0020
+DENSE_KEYS = ["releaseYear", "movieRatingCount", "movieAvgRating", "movieRatingStddev", "userRatingCount", "userAvgRating", "userRatingStddev"]
+ERR_USER, ERR_MOVIE, ERR_RATING = 1, 2, 3                   # the device error word's kinds, in the order the host checks them
+
+# year [n] int32, genre [n, 3] int32 (vocabulary index or -1), mask [n] uint32 (bit g = dictionary id g), has [n] uint8, dictionary [str];
+# row = movieId; a movie the table does not hold: 1990, -1, 0, 0
+MovieTable = namedtuple("MovieTable", "year genre mask has dictionary")
+
+
+def avg_h(n: int, s: int) -> int:
+    """Round-half-to-even of 50 S / n: the average of n half-star ratings (S = the sum of 2 * rating) in hundredths.  Exact."""
+    n, s = int(n), int(s)
+    if n == 0:
+        return 0
+    q, r = divmod(50 * s, n)
+    return q + (1 if 2 * r > n or (2 * r == n and q & 1) else 0)
+
+
+def sd_h(n: int, s: int, q: int) -> int:
+    """Round-half-to-even of 100 sqrt(N / (4 d)), N = n Q - S^2, d = n (n - 1): the sample stddev in hundredths.  Exact for any n."""
+    n, s, q = int(n), int(s), int(q)
+    if n < 2:
+        return 0
+    N, d = n * q - s * s, n * (n - 1)
+    h = 0
+    for bit in (512, 256, 128, 64, 32, 16, 8, 4, 2, 1):       # floor: the greatest h with (2 h)^2 d <= 10^4 N (h <= 708)
+        if 4 * (h | bit) * (h | bit) * d <= 10000 * N:
+            h |= bit
+    t = (2 * h + 1) * (2 * h + 1) * d
+    if t < 10000 * N or (t == 10000 * N and h & 1):
+        h += 1
+    return h
+
+
+def hundredths(h) -> np.ndarray:
+    """The stored float32 of h hundredths: ``float32(h / 100.0)``, dividing in double."""
+    return (np.asarray(h, dtype=np.float64) / 100.0).astype(np.float32)
+
+
+def _avg_h_vec(n, s):
+    a = 50 * s
+    nn = np.maximum(n, 1)
+    q, r = a // nn, a % nn
+    return np.where(n == 0, 0, q + ((2 * r > nn) | ((2 * r == nn) & (q & 1 == 1))))
+
+
+def _sd_h_vec(n, s, q):
+    """:func:`sd_h` for int64 arrays with n <= 100 (a window): every product fits 64 bits."""
+    N, d = n * q - s * s, np.maximum(n * (n - 1), 1)
+    R = 10000 * N
+    h = np.zeros_like(n)
+    for bit in (512, 256, 128, 64, 32, 16, 8, 4, 2, 1):
+        c = h | bit
+        h = np.where(4 * c * c * d <= R, c, h)
+    t = (2 * h + 1) * (2 * h + 1) * d
+    h = h + ((t < R) | ((t == R) & (h & 1 == 1)))
+    return np.where(n < 2, 0, h)
+
+
+def release_year(title, movie_id=None) -> int:
+    """``extractReleaseYearUdf`` (FeatureEngForRecModel.scala:36-44), its untrimmed indices included; where the reference's UDF throws
+    (no number at that place) this raises ``ValueError`` naming the movie."""
+    if title is None:
+        return DEFAULT_YEAR
+    t = title.strip(_JAVA_BLANKS)
+    if len(t) < 6:
+        return DEFAULT_YEAR
+    b, e = len(title) - 5, len(title) - 1
+    text = t[b:e] if e <= len(t) else None
+    if text is None or not re.fullmatch(r"[+-]?[0-9]+", text):
+        raise ValueError("movie %s: no release year at the end of the title %r" % (movie_id, title))
+    return int(text)
+
+
+def _host_column(col):
+    if hasattr(col, "detach"):
+        col = col.detach().cpu().numpy()
+    return np.asarray(col)
+
+
+def _read_csv_columns(path, names):
+    with open(path, newline="", encoding="utf-8") as f:
+        reader = csv.reader(f)
+        header = next(reader)
+        at = [header.index(k) for k in names]
+        cols = [[] for _ in names]
+        for row in reader:
+            if len(row) != len(header):
+                continue
+            for c, j in zip(cols, at):
+                c.append(row[j])
+    return dict(zip(names, cols))
+
+
+def movie_table(movies) -> MovieTable:
+    """The per-movie inputs of the job from ``movies.csv`` (a path) or ``{movieId, title, genres}`` columns."""
+    if isinstance(movies, MovieTable):
+        return movies
+    cols = _read_csv_columns(movies, ["movieId", "title", "genres"]) if isinstance(movies, str) else movies
+    ids = [int(v) for v in _host_column(cols["movieId"]).tolist()]
+    titles, genres = list(_host_column(cols["title"]).tolist()), list(_host_column(cols["genres"]).tolist())
+    if any(i < 0 or i >= _ID_LIMIT for i in ids):
+        raise ValueError("movieId %d cannot index a table" % next(i for i in ids if i < 0 or i >= _ID_LIMIT))
+    if len(set(ids)) != len(ids):
+        raise ValueError("the movie table names a movieId twice")
+    n = max(ids) + 1 if ids else 0
+    dictionary = list(S.GENRE_VOCAB)
+    index = {g: i for i, g in enumerate(dictionary)}
+    year = np.full(n, DEFAULT_YEAR, dtype=np.int32)
+    genre = np.full((n, 3), -1, dtype=np.int32)
+    mask = np.zeros(n, dtype=np.uint32)
+    has = np.zeros(n, dtype=np.uint8)
+    for i, title, g in zip(ids, titles, genres):
+        title = None if title is None else (title.decode() if isinstance(title, bytes) else str(title))
+        year[i] = release_year(title, i)
+        pieces = [] if g is None else (g.decode() if isinstance(g, bytes) else str(g)).split("|")
+        bits = 0
+        for k, piece in enumerate(pieces):
+            if piece == "":
+                continue                                     # (an empty piece is a missing genre)
+            if piece not in index:
+                if len(dictionary) == MAX_GENRES:
+                    raise ValueError("more than %d distinct genres (movie %d: %r)" % (MAX_GENRES, i, piece))
+                index[piece] = len(dictionary)
+                dictionary.append(piece)
+            gid = index[piece]
+            bits |= 1 << gid
+            if k < 3 and gid < S.N_GENRES:
+                genre[i, k] = gid
+        mask[i] = bits
+        has[i] = 1
+    return MovieTable(year, genre, mask, has, dictionary)
+
+
+def _padded(table: MovieTable, n_movies: int) -> MovieTable:
+    n = len(table.year)
+    if n_movies <= n:
+        return MovieTable(table.year[:n_movies], table.genre[:n_movies], table.mask[:n_movies], table.has[:n_movies], table.dictionary)
+    extra = n_movies - n
+    return MovieTable(np.concatenate([table.year, np.full(extra, DEFAULT_YEAR, np.int32)]), np.concatenate([table.genre, np.full((extra, 3), -1, np.int32)]),
+                      np.concatenate([table.mask, np.zeros(extra, np.uint32)]), np.concatenate([table.has, np.zeros(extra, np.uint8)]), table.dictionary)
+
+
+RATING_KEYS = ["userId", "movieId", "rating", "timestamp"]
+
+
+def _rating_columns(ratings):
+    """-> userId, movieId (int64), rating (float32: the sample column's type), timestamp (int64) as numpy arrays."""
+    cols = _read_csv_columns(ratings, RATING_KEYS) if isinstance(ratings, str) else ratings
+    for k in RATING_KEYS:
+        if k not in cols:
+            raise KeyError("missing ratings column %r" % k)
+    def ints(col):
+        a = _host_column(col)
+        return a.astype(np.int64) if a.dtype.kind in "iub" else np.array([int(v) for v in a.tolist()], dtype=np.int64)
+    def floats(col):
+        a = _host_column(col)
+        return a.astype(np.float32) if a.dtype.kind in "iubf" else np.array([float(v) for v in a.tolist()], dtype=np.float64).astype(np.float32)
+    u, m, r, t = ints(cols["userId"]), ints(cols["movieId"]), floats(cols["rating"]), ints(cols["timestamp"])
+    if not (len(u) == len(m) == len(r) == len(t)):
+        raise ValueError("the ratings columns differ in length")
+    if len(u) >= _ID_LIMIT:
+        raise ValueError("at most 2^31 - 2 ratings")
+    return u, m, r, t
+
+
+def _error_message(kind: int, row: int) -> str:
+    what = {ERR_USER: "userId outside the user table", ERR_MOVIE: "movieId outside the movie table",
+            ERR_RATING: "rating off the half-star scale 0, 0.5 .. 10"}[kind]
+    return "ratings row %d: %s" % (row, what)
+
+
+def _half_stars(r: np.ndarray) -> np.ndarray:
+    """2 * rating as int64, -1 where the float32 rating is off the half-star scale."""
+    t = r.astype(np.float32) * np.float32(2.0)
+    ok = (t >= 0) & (t <= 20) & (np.floor(t) == t)             # (NaN fails every comparison)
+    return np.where(ok, np.where(ok, t, 0).astype(np.int64), -1)
+
+
+def _validate(u, m, r2, n_users, n_movies):
+    """Raises the ValueError the device's error word names: the lowest kind, then the first input row."""
+    for kind, bad in ((ERR_USER, (u < 0) | (u >= n_users)), (ERR_MOVIE, (m < 0) | (m >= n_movies)), (ERR_RATING, r2 < 0)):
+        if bad.any():
+            raise ValueError(_error_message(kind, int(np.flatnonzero(bad)[0])))
+
+
+def _table_sizes(u, m, table: MovieTable, n_users, n_movies):
+    """Default table sizes: the greatest id + 1 (the movie table's rows at least); a given size that does not hold the movie table is an error."""
+    if n_users is None:
+        n_users = int(u.max()) + 1 if len(u) and int(u.max()) >= 0 else 0
+    if n_movies is None:
+        n_movies = max(len(table.year), int(m.max()) + 1 if len(m) and int(m.max()) >= 0 else 0)
+    if not 0 <= n_users < _ID_LIMIT or not 0 <= n_movies <= _ID_LIMIT:
+        raise ValueError("n_users / n_movies outside [0, 2^31 - 1)")
+    if n_movies < len(table.year) and table.has[n_movies:].any():
+        raise ValueError("movieId %d of the movie table does not fit a table of %d rows" % (int(np.flatnonzero(table.has)[-1]), n_movies))
+    return int(n_users), int(n_movies)
+
+
+def sample_keys(hist_len: int = 5):
+    """The columns of a samples dict, in order."""
+    return (["userId", "movieId", "rating", "timestamp", "label"] + S.MOVIE_GENRE_KEYS + S.USER_GENRE_KEYS
+            + ["userRatedMovie%d" % (k + 1) for k in range(hist_len)] + DENSE_KEYS + ["source_row"])
+
+
+def _columns_dict(hist_len, user, movie, rating, ts, label, src, genres, hist, dense):
+    out = {"userId": user, "movieId": movie, "rating": rating, "timestamp": ts, "label": label}
+    for k, key in enumerate(S.MOVIE_GENRE_KEYS + S.USER_GENRE_KEYS):
+        out[key] = genres[:, k]
+    for k in range(hist_len):
+        out["userRatedMovie%d" % (k + 1)] = hist[:, k]
+    for k, key in enumerate(DENSE_KEYS):
+        out[key] = dense[:, k]
+    out["source_row"] = src
+    return out
+
+
+def samples_host(ratings, movies, hist_len: int = 5, n_users: Optional[int] = None, n_movies: Optional[int] = None) -> dict:
+    """The definition (module docstring): ``ratings`` = ``{userId, movieId, rating, timestamp}`` columns or a CSV path, ``movies`` a
+    :class:`MovieTable` (or what :func:`movie_table` takes) -> a dict of columns in ``(userId, timestamp, input row)`` order, the dropped
+    rows removed: ``userId, movieId, rating, timestamp, label``, ``movieGenre1..3`` and ``userGenre1..5`` as vocabulary indices (-1 = none),
+    ``userRatedMovie1..hist_len`` (0 = none), the seven numeric columns as float32 and ``source_row``, the input row.  ``model.predict``,
+    ``model.evaluate`` and ``FeatureStore.from_samples`` accept it as it is.  A rating off the half-star scale, or an id outside
+    ``[0, n_users)`` / ``[0, n_movies)`` (default: any non-negative id), raises ``ValueError`` naming the first such input row."""
+    if not 1 <= hist_len <= WINDOW:
+        raise ValueError("hist_len = %d outside [1, %d]" % (hist_len, WINDOW))
+    table = movie_table(movies)
+    u, m, r, t = _rating_columns(ratings)
+    r2 = _half_stars(r)
+    _validate(u, m, r2, _ID_LIMIT if n_users is None else n_users, _ID_LIMIT if n_movies is None else n_movies)
+    n_users, n_movies = _table_sizes(u, m, table, n_users, n_movies)
+    table = _padded(table, n_movies)
+    n = len(u)
+    # movie side, over ALL ratings (bincount sums in float64: exact, S <= 20 n and Q <= 400 n stay below 2^53)
+    cnt = np.bincount(m, minlength=n_movies).astype(np.int64)
+    sm = np.bincount(m, weights=r2, minlength=n_movies).astype(np.int64)
+    qm = np.bincount(m, weights=r2 * r2, minlength=n_movies).astype(np.int64)
+    m_avg, m_sd = np.zeros(n_movies, dtype=np.int64), np.zeros(n_movies, dtype=np.int64)
+    for i in np.flatnonzero(cnt):
+        m_avg[i], m_sd[i] = avg_h(cnt[i], sm[i]), sd_h(cnt[i], sm[i], qm[i])
+    # user side: one sort, then every window as a difference of prefix sums over the sorted order
+    order = np.lexsort((np.arange(n), t, u))
+    us, ms, r2s = u[order], m[order], r2[order]
+    pos = np.arange(n, dtype=np.int64)
+    new = np.ones(n, dtype=bool)
+    new[1:] = us[1:] != us[:-1]
+    start = np.maximum.accumulate(np.where(new, pos, 0))
+    first = np.maximum(start, pos - WINDOW)                                  # the window is [first, pos)
+    count = pos - first
+    def window_sum(v):
+        c = np.concatenate([[0], np.cumsum(v, dtype=np.int64)])
+        return c[pos] - c[first]
+    s_w, q_w = window_sum(r2s), window_sum(r2s * r2s)
+    positive = r2s >= POSITIVE_R2
+    bits = ((table.mask[ms].astype(np.int64)[:, None] >> np.arange(MAX_GENRES)) & 1) * positive[:, None]
+    prefix = np.concatenate([np.zeros((1, MAX_GENRES), np.int64), np.cumsum(bits, axis=0, dtype=np.int64)])
+    counts = prefix[pos] - prefix[first]                                     # [n, 32]
+    key = np.where(counts > 0, counts * MAX_GENRES + (MAX_GENRES - 1 - np.arange(MAX_GENRES)), 0)   # count desc, dictionary id asc
+    top = -np.sort(-key, axis=1)[:, :5]
+    gid = MAX_GENRES - 1 - top % MAX_GENRES
+    user_genres = np.where((top > 0) & (gid < S.N_GENRES), gid, -1)
+    where_pos = np.flatnonzero(positive)
+    hi, lo = np.searchsorted(where_pos, pos), np.searchsorted(where_pos, first)    # the window's positives: where_pos[lo:hi]
+    hist = np.zeros((n, hist_len), dtype=np.int64)
+    for k in range(hist_len):
+        at = hi - 1 - k
+        ok = at >= lo
+        if where_pos.size:
+            hist[:, k] = np.where(ok, ms[where_pos[np.clip(at, 0, where_pos.size - 1)]], 0)
+    keep = count > 1
+    sel = order[keep]
+    genres = np.concatenate([table.genre[ms[keep]], user_genres[keep]], axis=1).astype(np.int32)
+    mk = ms[keep]
+    dense = np.stack([table.year[mk].astype(np.float32), cnt[mk].astype(np.float32), hundredths(m_avg[mk]), hundredths(m_sd[mk]),
+                      count[keep].astype(np.float32), hundredths(_avg_h_vec(count[keep], s_w[keep])),
+                      hundredths(_sd_h_vec(count[keep], s_w[keep], q_w[keep]))], axis=1) if n else np.zeros((0, 7), np.float32)
+    return _columns_dict(hist_len, u[sel].astype(np.int32), m[sel].astype(np.int32), r[sel], t[sel], positive[keep].astype(np.int32), sel.astype(np.int32),
+                         genres, hist[keep].astype(np.int32), dense.astype(np.float32))
+
+
+class DeviceSamples:
+    """What :func:`build` returns: the sample columns as device tensors (``columns``: the dict of :func:`samples_host`, every tensor cut to
+    ``n_samples`` rows) and the feature store's tables, which were written by the same call and never left the device."""
+
+    def __init__(self, columns, n_samples, hist_len, store_tensors, device):
+        self.columns, self.n_samples, self.hist_len, self.device = columns, int(n_samples), int(hist_len), device
+        self._store_tensors = store_tensors
+
+    def to_host(self) -> dict:
+        """The dict :func:`samples_host` returns, bit for bit."""
+        return {k: v.cpu().numpy() for k, v in self.columns.items()}
+
+    def store(self):
+        """A :class:`~sparrowrecsys_amd.featurestore.FeatureStore` over the tables this build wrote on the device."""
+        from .featurestore import FeatureStore
+        return FeatureStore._from_device_tables(self._store_tensors, self.hist_len, self.device)
+
+
+def build(ratings, movies, hist_len: int = 5, device=None, n_users: Optional[int] = None, n_movies: Optional[int] = None) -> DeviceSamples:
+    """Samples and store on the device.  ``ratings``: a CSV path or ``{userId, movieId, rating, timestamp}`` columns, numpy arrays or
+    device tensors (tensors on ``device`` are used where they are); ``movies``: what :func:`movie_table` takes.  ``n_users`` /
+    ``n_movies`` size the store's tables (default: the greatest id + 1, which costs one reduction over the id columns).  Errors are the
+    ``ValueError`` of :func:`samples_host`.  One host synchronisation: the error word and the sample count."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib as L
+    from .featurestore import user_pitch
+    if not 1 <= hist_len <= WINDOW:
+        raise ValueError("hist_len = %d outside [1, %d]" % (hist_len, WINDOW))
+    lib = L.load_library()
+    if not torch.cuda.is_available():
+        raise RuntimeError("featureeng.build needs a HIP device: no HIP device is visible (samples_host is the host definition)")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    table = movie_table(movies)
+    if isinstance(ratings, Mapping) and all(hasattr(ratings.get(k), "detach") for k in RATING_KEYS):
+        cols = [ratings[k].detach().to(dev) for k in RATING_KEYS]
+        if not all(c.ndim == 1 and c.numel() == cols[0].numel() for c in cols):
+            raise ValueError("the ratings columns differ in length")
+        if any(c.dtype.is_floating_point for c in (cols[0], cols[1], cols[3])):
+            raise TypeError("userId, movieId and timestamp must be integer tensors")
+        # (an id beyond int32 must not wrap into range: it becomes -1, which the kernel reports)
+        ids = [torch.where((c < 0) | (c >= _ID_LIMIT), torch.full_like(c, -1), c).to(torch.int32).contiguous() for c in cols[:2]]
+        u_d, m_d, r_d, t_d = ids[0], ids[1], cols[2].to(torch.float32).contiguous(), cols[3].to(torch.int64).contiguous()
+        n = u_d.numel()
+        um, mm = (int(u_d.max()), int(m_d.max())) if n and (n_users is None or n_movies is None) else (-1, -1)
+    else:
+        u, m, r, t = _rating_columns(ratings)
+        n = len(u)
+        clip = lambda a: np.where((a < 0) | (a >= _ID_LIMIT), -1, a).astype(np.int32)
+        u, m = clip(u), clip(m)
+        um, mm = (int(u.max()), int(m.max())) if n else (-1, -1)
+        u_d, m_d = torch.from_numpy(u).to(dev), torch.from_numpy(m).to(dev)
+        r_d, t_d = torch.from_numpy(np.ascontiguousarray(r)).to(dev), torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+    if n >= _ID_LIMIT:
+        raise ValueError("at most 2^31 - 2 ratings")
+    n_users, n_movies = _table_sizes(np.array([um]), np.array([mm]), table, n_users, n_movies)
+    table = _padded(table, n_movies)
+    pitch = user_pitch(hist_len)
+    with torch.cuda.device(dev):
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        year_d, genre_d, mask_d = up(table.year), up(table.genre), up(table.mask.view(np.int32))
+        new = lambda shape, dtype: torch.empty(shape, dtype=dtype, device=dev)
+        rows = max(n, 1)
+        o_user, o_movie, o_rating, o_ts = new(rows, torch.int32), new(rows, torch.int32), new(rows, torch.float32), new(rows, torch.int64)
+        o_label, o_src = new(rows, torch.int32), new(rows, torch.int32)
+        o_genres, o_hist, o_dense = new((rows, 8), torch.int32), new((rows, hist_len), torch.int32), new((rows, 7), torch.float32)
+        # (one spare row each, zero: an empty table still has an address -- FeatureStore's convention)
+        user_rows, user_has = torch.zeros((n_users + 1, pitch), dtype=torch.int32, device=dev), torch.zeros(n_users + 1, dtype=torch.uint8, device=dev)
+        movie_rows, movie_has = torch.zeros((n_movies + 1, 8), dtype=torch.int32, device=dev), torch.zeros(n_movies + 1, dtype=torch.uint8, device=dev)
+        words = torch.tensor([-1, 0], dtype=torch.int64, device=dev)            # the error word (~0), the sample count
+        ws_bytes = lib.sprk_feature_eng_workspace_bytes(n, n_users, n_movies)
+        ws = torch.empty(max(ws_bytes, 16) // 8 + 2, dtype=torch.int64, device=dev)   # (torch's allocations are 512-byte aligned)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        L.check(lib.sprk_feature_eng(p(u_d), p(m_d), p(r_d), p(t_d), n, n_users, n_movies, p(year_d), p(genre_d), p(mask_d), S.N_GENRES, hist_len,
+                                     p(o_user), p(o_movie), p(o_rating), p(o_ts), p(o_label), p(o_src), p(o_genres), p(o_hist), p(o_dense),
+                                     p(user_rows), p(user_has), pitch, p(movie_rows), p(movie_has),
+                                     C.c_void_p(words.data_ptr()), C.c_void_p(words.data_ptr() + 8), p(ws), ws.numel() * 8,
+                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        err, kept = (int(v) for v in words.cpu().numpy())                        # the one synchronisation
+    if err != -1:
+        raise ValueError(_error_message((err >> 32) & 0xffffffff, err & 0xffffffff))
+    cut = lambda x: x[:kept]
+    columns = _columns_dict(hist_len, cut(o_user), cut(o_movie), cut(o_rating), cut(o_ts), cut(o_label), cut(o_src), cut(o_genres), cut(o_hist), cut(o_dense))
+    return DeviceSamples(columns, kept, hist_len, (user_rows, user_has, movie_rows, movie_has), dev)

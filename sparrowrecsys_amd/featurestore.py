@@ -207,7 +207,7 @@ class FeatureStore:
     they were uploaded from (a :class:`RowImages`), ``user_layout`` / ``movie_layout`` map a column to its dword and role."""
 
     def __init__(self, images: RowImages, device=None):
-        self.images = images
+        self._images = images
         self.hist_len = int(images.hist_len)
         self.n_users, self.user_pitch = int(images.user_rows.shape[0]), int(images.user_rows.shape[1])
         self.n_movies, self.movie_pitch = int(images.movie_rows.shape[0]), int(images.movie_rows.shape[1])
@@ -228,6 +228,43 @@ class FeatureStore:
             self._tensors = (up(images.user_rows, (1, self.user_pitch)), up(images.user_has, (1,)),
                              up(images.movie_rows, (1, self.movie_pitch)), up(images.movie_has, (1,)))
             self.device = dev
+
+    @property
+    def images(self) -> RowImages:
+        """The host copy of the tables; a store whose tables were written on the device (:meth:`from_ratings`) downloads it at first use."""
+        if self._images is None:
+            ur, uh, mr, mh = (t.cpu().numpy() for t in self.tensors())
+            self._images = RowImages(ur[:self.n_users], uh[:self.n_users], mr[:self.n_movies], mh[:self.n_movies], self.hist_len)
+        return self._images
+
+    @classmethod
+    def _from_device_tables(cls, tensors, hist_len: int, device):
+        """A store over tables that are on the device already, one spare row each: ``(user_rows, user_has, movie_rows, movie_has)``."""
+        self = cls.__new__(cls)
+        self._images = None
+        self.hist_len = int(hist_len)
+        self.n_users, self.user_pitch = int(tensors[0].shape[0]) - 1, int(tensors[0].shape[1])
+        self.n_movies, self.movie_pitch = int(tensors[2].shape[0]) - 1, int(tensors[2].shape[1])
+        if self.user_pitch != user_pitch(self.hist_len) or self.movie_pitch != MOVIE_PITCH:
+            raise ValueError("the tables do not have the store's pitches")
+        self.user_layout, self.movie_layout = user_layout(self.hist_len), movie_layout()
+        self._tensors, self.device = tuple(tensors), device
+        return self
+
+    @classmethod
+    def from_ratings(cls, ratings, movies, hist_len: int = 5, device=None, n_users: Optional[int] = None, n_movies: Optional[int] = None):
+        """From ``ratings.csv`` and ``movies.csv`` (paths or columns, as ``featureeng.build`` takes them) without the reference's Spark
+        job: the samples are computed on ``device`` and the tables written there (``sprk_feature_eng``).  ``device="cpu"`` builds the images
+        from the host definition ``featureeng.samples_host``: no GPU involved, like the other constructors.  ``n_users`` / ``n_movies``
+        default to the greatest id of the RATINGS + 1 (the movie table's rows at least)."""
+        from . import featureeng as FE
+        if device is not None and str(device) == "cpu":
+            table = FE.movie_table(movies)
+            u, m, _, _ = cols = FE._rating_columns(ratings)
+            samples = FE.samples_host(dict(zip(FE.RATING_KEYS, cols)), table, hist_len, n_users, n_movies)
+            n_users, n_movies = FE._table_sizes(u, m, table, n_users, n_movies)
+            return cls(row_images_from_samples(samples, hist_len, n_users, n_movies), "cpu")
+        return FE.build(ratings, movies, hist_len, device, n_users, n_movies).store()
 
     @classmethod
     def from_samples(cls, features_or_csv_path, hist_len: int = 5, device=None, n_users: Optional[int] = None, n_movies: Optional[int] = None):

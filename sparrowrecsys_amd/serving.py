@@ -722,7 +722,7 @@ def serve_workers(factory, fargs=(), n_workers: int = 4, name: str = "recmodel",
     return WorkerPool(procs, stop, port, pids, engine_pid, tmpdir)
 
 
-def _cli_model(model_name, weights_path, features_path=None):
+def _cli_model(model_name, weights_path, features_path=None, ratings_path=None, movies_path=None):
     from . import models as M
     cls = {"neuralcf": M.NeuralCF, "embedding_mlp": M.EmbeddingMLP, "wide_n_deep": M.WideNDeep, "deepfm": M.DeepFM,
            "deepfm_v2": M.DeepFMv2, "din": M.DIN, "dien": M.DIEN}[model_name]
@@ -733,6 +733,11 @@ def _cli_model(model_name, weights_path, features_path=None):
         from .featurestore import FeatureStore
         store = FeatureStore.from_samples(features_path, hist_len=getattr(model, "hist_len", 5))
         model.join_plan(store)                             # (a model the store cannot feed fails here, not at the first request)
+        return StoreBackedModel(model, store)
+    if ratings_path:                                       # the same store from ratings.csv + movies.csv, computed and kept on the device
+        from .featurestore import FeatureStore
+        store = FeatureStore.from_ratings(ratings_path, movies_path, hist_len=getattr(model, "hist_len", 5))
+        model.join_plan(store)
         return StoreBackedModel(model, store)
     return model
 
@@ -746,11 +751,18 @@ def _main():
     ap.add_argument("--port", type=int, default=8501)
     ap.add_argument("--features", help="samples CSV (the schema of testSamples.csv): a feature store of every user's and movie's latest row; "
                                        "requests that send only userId / movieId are completed from it on the device")
+    ap.add_argument("--ratings", help="ratings.csv (userId,movieId,rating,timestamp): with --movies, the same feature store computed from the raw ratings on the "
+                                      "device (featureeng.py) instead of read from a samples CSV; not together with --features")
+    ap.add_argument("--movies", help="movies.csv (movieId,title,genres), the movie table of --ratings")
     ap.add_argument("--workers", type=int, default=1, help="front processes sharing the port (SO_REUSEPORT) in front of ONE engine process that owns the model and the GPU")
     args = ap.parse_args()
+    if args.features and (args.ratings or args.movies):
+        ap.error("--features and --ratings / --movies are mutually exclusive")
+    if bool(args.ratings) != bool(args.movies):
+        ap.error("--ratings and --movies come together")
     if args.workers > 1:
         import signal
-        pool = serve_workers(_cli_model, (args.model, args.weights, args.features), n_workers=args.workers, name=args.name, host=args.host, port=args.port)
+        pool = serve_workers(_cli_model, (args.model, args.weights, args.features, args.ratings, args.movies), n_workers=args.workers, name=args.name, host=args.host, port=args.port)
         print("serving %s on http://%s:%d/v1/models/%s:predict from %d workers (pids %s)" % (args.model, args.host, pool.port, args.name, args.workers, pool.pids), flush=True)
         # [r6, ADVICE r05] a plain `kill` (SIGTERM) must take the fronts and the engine along, and a dead engine must end the service
         def _term(signum, frame):
@@ -765,7 +777,7 @@ def _main():
         finally:
             pool.close()
         return
-    model = _cli_model(args.model, args.weights, args.features)
+    model = _cli_model(args.model, args.weights, args.features, args.ratings, args.movies)
     srv = PredictServer(model, name=args.name, host=args.host, port=args.port)
     print("serving %s on http://%s:%d/v1/models/%s:predict" % (args.model, args.host, srv.port, args.name), flush=True)
     try:
