@@ -257,3 +257,138 @@ def test_feature_eng_abi_rejects_bad_arguments_before_any_device_call(lib):
     import torch
     if not torch.cuda.is_available():
         assert call() == L.EHIP                                 # a good call reaches the device, and there is none
+
+
+# ---- the definition against its row-by-row restatement, and the properties of the rating sets the device tests rely on ----
+def _assert_same_bytes(got, want):
+    assert list(got) == list(want)
+    for k in want:
+        assert got[k].dtype == want[k].dtype and got[k].shape == want[k].shape, k
+        assert got[k].tobytes() == want[k].tobytes(), (k, np.flatnonzero(got[k] != want[k])[:8])
+
+
+def _restated_sets():
+    synthetic = (cases.synthetic_ratings(), cases.synthetic_movies())
+    return {
+        "hand": (cases.HAND_RATINGS, cases.HAND_MOVIES, 5),
+        "synthetic-5": synthetic + (5,),
+        "synthetic-12": synthetic + (12,),
+        "synthetic-1": synthetic + (1,),
+        "synthetic-100": synthetic + (100,),
+        "all_genres": (cases.all_genres_ratings(), cases.all_genres_movies(), 5),
+        "merge_shapes": (cases.merge_shapes_ratings(), cases.synthetic_movies(), 5),
+        "scale_ends": (cases.scale_ends_ratings(), cases.synthetic_movies(), 5),
+        "scale_ends-100": (cases.scale_ends_ratings(), cases.synthetic_movies(), 100),
+        "sparse_users": (cases.sparse_users_ratings(), cases.synthetic_movies(), 5),
+    }
+
+
+@pytest.mark.parametrize("name", ["hand", "synthetic-5", "synthetic-12", "synthetic-1", "synthetic-100", "all_genres", "merge_shapes", "scale_ends",
+                                  "scale_ends-100", "sparse_users"])
+def test_definition_equals_its_restatement_row_by_row(name):
+    """samples_host (prefix sums, searchsorted, a sort of packed keys) against featureeng_cases.definition_by_rows (DESIGN.md section 5.7
+    with loops, fractions and a dict), every column byte for byte.  The restatement loops over the users that have ratings."""
+    ratings, movies, hist_len = _restated_sets()[name]
+    _assert_same_bytes(FE.samples_host(ratings, movies, hist_len), cases.definition_by_rows(ratings, movies, hist_len))
+
+
+def _top_fives(got, user):
+    return np.stack([got["userGenre%d" % k][got["userId"] == user] for k in range(1, 6)], axis=1)
+
+
+def test_all_genres_set_holds_the_cases_it_names():
+    ratings, movies = cases.all_genres_ratings(), cases.all_genres_movies()
+    table = FE.movie_table(movies)
+    assert len(table.dictionary) == 32 and table.dictionary[:S.N_GENRES] == S.GENRE_VOCAB
+    assert [int(table.mask[g]) for g in range(32)] == [1 << g for g in range(32)]
+    assert [int(table.mask[32 + k]) for k in range(8)] == [0x01010101 << k for k in range(8)]
+    assert int(ratings["userId"].max()) < cases.ALL_GENRES_USERS and int(ratings["movieId"].max()) < cases.ALL_GENRES_MOVIES
+    got = FE.samples_host(ratings, movies)
+    name = lambda g: g if g < S.N_GENRES else -1
+    for g in range(32):                                        # id g leads with count 3; vocabulary genres follow, so losing g's count shows
+        last = _top_fives(got, g)[-1].tolist()
+        others = [x for x in range(4) if x != g]
+        assert last == ([name(g)] + others + [-1] * 5)[:5], (g, last)
+        assert last != (others + [-1] * 5)[:5]
+    registers = set()
+    for k, (a, b) in enumerate(cases.ALL_GENRES_TIES):
+        assert a < b and a // 8 != b // 8                      # a tie across two counter registers: the lower id wins
+        registers.add((a // 8, b // 8))
+        lead = _top_fives(got, 40 + k)[-1].tolist()
+        assert lead == [name(a), name(b), -1, -1, -1], (a, b, lead)
+        fifth = _top_fives(got, 50 + k)[-1].tolist()
+        assert fifth == [1, 2, 3, 4, name(a)], (a, b, fifth)
+        if a < S.N_GENRES <= b:                                # the other order would write -1 here
+            assert lead[0] != name(b) and fifth[4] != name(b)
+    assert {(0, 1), (1, 2), (2, 3), (0, 3)} <= registers
+    for k in range(8):                                         # four registers in one window: ids k (3), k + 8, k + 16 (2 each; k + 24 is unnamed)
+        assert _top_fives(got, 60 + k)[-1].tolist() == [k, k + 8, name(k + 16), -1, -1]
+
+
+def test_merge_shapes_set_holds_the_cases_it_names():
+    ratings = cases.merge_shapes_ratings()
+    lens = np.bincount(ratings["userId"], minlength=cases.MERGE_USERS)
+    assert lens[1:12].tolist() == [64, 65, 128, 129, 192, 320, 321, 1000, 300, 200, 70]
+    of = lambda u: ratings["timestamp"][ratings["userId"] == u]
+    assert len(set(of(9).tolist())) == 1
+    assert (np.diff(of(10)) < 0).all()
+    t11 = of(11)
+    assert (t11 == cases.INT64_MAX).sum() == 2 and (t11 == cases.INT64_MIN).sum() == 2 and len(set(t11.tolist())) > 20
+    got = FE.samples_host(ratings, cases.synthetic_movies())
+    assert len(got["userId"]) == int(np.maximum(lens - 2, 0).sum())
+    src = lambda u: got["source_row"][got["userId"] == u]
+    assert (np.diff(src(9)) > 0).all() and (np.diff(src(10)) < 0).all()
+    assert got["timestamp"][got["userId"] == 11][-2:].tolist() == [cases.INT64_MAX] * 2 and (np.diff(src(11)[-2:]) > 0).all()
+    assert not np.array_equal(ratings["userId"], np.sort(ratings["userId"]))                  # shuffled
+
+
+def test_scale_ends_set_holds_the_cases_it_names():
+    ratings = cases.scale_ends_ratings()
+    one = ratings["rating"][ratings["userId"] == 1]
+    assert set(one.tolist()) == {0.0, 10.0} and np.signbit(one).any() and (one == 0).sum() > np.signbit(one).sum()
+    got = FE.samples_host(ratings, cases.synthetic_movies())
+    first = np.flatnonzero(got["userId"] == 1)[0]
+    assert got["userRatingCount"][first] == 2 and got["userAvgRating"][first] == np.float32(5.0) and got["userRatingStddev"][first] == np.float32(7.07)
+    assert np.signbit(got["rating"][got["userId"] == 1]).any()                               # -0.0 is written as it came
+    two = got["userId"] == 2
+    full = two & (got["userRatingCount"] == 100) & (got["userAvgRating"] == np.float32(10.0)) & (got["userRatingStddev"] == 0)
+    assert full.sum() == 2 and two.sum() == 110               # positions 100 and 101: windows of a hundred 10.0, S = 2000, Q = 40000
+
+
+def test_sparse_users_set_holds_the_cases_it_names():
+    n_users = 300_000
+    ratings = cases.sparse_users_ratings(n_users)
+    lens = np.bincount(ratings["userId"], minlength=n_users)
+    assert len(lens) == n_users and 2000 <= len(ratings["userId"]) <= 6000
+    for u in cases.SPARSE_EDGE_IDS + [n_users - 1]:
+        assert 3 <= lens[u] <= 150, u
+    assert 50 <= (lens >= 3).sum() <= 55 and (lens == 1).sum() >= 1 and (lens == 2).sum() >= 1
+    assert (n_users + 1 + 1023) // 1024 > 256                 # the scan over the tiles' totals takes a second round
+
+
+def test_singletons_popular_movie_tells_64_bit_products_from_128():
+    """The (n, S, Q) of the popular movie of the device test: the exact rule and the same steps wrapped to 64 bits differ."""
+    case = cases.singletons_ratings()
+    n, s, q = case["popular"]
+    assert n >= 4_500_000 and 4 * 512 * 512 * n * (n - 1) > 2**64
+    exact, narrow = FE.sd_h(n, s, q), cases.sd_h_in_64_bits(n, s, q)
+    print("popular movie: n = %d, S = %d, Q = %d: exact h = %d, 64-bit h = %d" % (n, s, q, exact, narrow))
+    assert exact == _decimal_avg_sd(n, s, q)[1] and exact != narrow
+    assert cases.sd_h_in_64_bits(100, 1234, 20000) == FE.sd_h(100, 1234, 20000)              # (the emulation is the rule where nothing wraps)
+    # the issue's alternating 0.0 / 10.0 figures
+    assert [(FE.sd_h(k, 10 * k, 200 * k), cases.sd_h_in_64_bits(k, 10 * k, 200 * k)) for k in (4_000_000, 4_300_000)] == [(500, 500), (500, 24)]
+    users = case["ordinary_users"]
+    grid = cases.SHORT_SORT_GRID
+    assert (users < grid).sum() >= 9 and ((users >= grid) & (users < 2 * grid)).sum() >= 9 and (users >= 2 * grid).sum() >= 9
+    lens = np.bincount(case["ratings"]["userId"][case["ordinary_rows"]], minlength=case["n_users"])[users]
+    assert lens.min() >= 3 and lens.max() <= 300
+    popular = case["ratings"]["movieId"][case["ordinary_rows"]] == cases.POPULAR_MOVIE
+    assert 5 <= popular.sum() and n == 4_500_000 + popular.sum()
+
+
+def test_singletons_expectation_equals_the_definition_on_a_reduced_copy():
+    case = cases.singletons_ratings(n_single=20_000)
+    movies = cases.synthetic_movies()
+    whole = FE.samples_host(case["ratings"], movies, 5, n_users=case["n_users"], n_movies=case["n_movies"])
+    _assert_same_bytes(cases.singletons_expectation(case, movies, 5), whole)
+    assert len(whole["userId"]) > 1000 and (whole["movieId"] == cases.POPULAR_MOVIE).sum() >= 5
