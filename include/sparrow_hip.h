@@ -533,6 +533,36 @@ int sprk_feature_eng(const int32_t* user_id, const int32_t* movie_id, const floa
                      int32_t* user_rows, uint8_t* user_has, int32_t user_pitch, int32_t* movie_rows, uint8_t* movie_has,
                      uint64_t* error_key, int64_t* n_kept, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- user embeddings on the device: ratings + item embeddings -> one vector per user ----
+ * The arithmetic of the reference's Embedding.generateUserEmb (Embedding.scala:53-101), which writes userEmb.csv, the "emb" ranker's user
+ * side.  The definition, rule by rule, is sparrowrecsys_amd/userembedding.py user_emb_host; this call gives the
+ * same bits.  Per user: acc = +0.0f in every dimension; the user's rating rows are walked in INPUT ORDER FROM THE LAST TO THE FIRST (the
+ * Scala folds with foldRight) and every row whose item has an embedding does acc = acc + item_emb[row], one float32 add per dimension
+ * per row, never reassociated (no float atomics, nothing split along a user's rows: the result is a function of the input alone).  A
+ * row "has an embedding" when 0 <= item_row[i] < n_items and item_has[item_row[i]] != 0; any other row is skipped -- no zero row is
+ * added, a table row with item_has == 0 may hold anything -- and is no error.  Subnormals are kept.
+ *   mode 0 (the Scala)        user_count = ALL the user's rows, user_emb = acc / (float)user_count (IEEE division, round to nearest even)
+ *   mode 1 (the PySpark twin) user_count = the user's rows that have an embedding, user_emb = acc
+ * user_has = (user_count > 0); a user whose count is 0 gets zeros.  So in mode 0 a user none of whose items has an embedding has
+ * user_has 1 and an all-zero vector.
+ * In, device memory: user_id and item_row (int32, the item table's row of the rated movie), n_ratings rows in any order; item_emb
+ * [n_items][item_stride] float32 of which D per row are read, item_has [n_items].  Out, device memory, EVERY row written: user_emb
+ * [n_users][user_stride] (D floats per row; the floats between D and user_stride are left alone), user_has [n_users], user_count
+ * [n_users].  `error_key` is ONE caller-provided device word, set to ~0 before the call: the kernels atomicMin (1 << 32 | input row)
+ * into it for a user_id outside [0, n_users); such a row takes no further part, and when the word is not ~0 afterwards the outputs
+ * hold no result.  Input that is grouped by user (every user's rows adjacent) is summed where it lies; any other input is scattered
+ * into per-user segments and sorted by input row -- in LDS up to 4096 rows of one user (SPRK_FE_SORT_CAP, as for sprk_feature_eng),
+ * by chunked sort + merge passes beyond.  The workspace is sprk_user_emb_workspace_bytes(n_ratings, n_users) bytes, 16-byte aligned
+ * (0 for sizes the call rejects).
+ * 0 <= n_ratings < 2^31 - 1, 0 <= n_users < 2^31 - 1, n_items >= 0, 1 <= D <= 1024, item_stride >= D, user_stride >= D, mode 0 or 1, no
+ * NULL or misaligned pointer, a sufficient workspace (the message names the bytes needed): anything else returns SPRK_EINVAL BEFORE
+ * any device call.  Asynchronous on `stream`: no synchronisation, no memory owned by the library; all index arithmetic in 64 bits. */
+size_t sprk_user_emb_workspace_bytes(int64_t n_ratings, int32_t n_users);
+int sprk_user_emb(const int32_t* user_id, const int32_t* item_row, int64_t n_ratings, int32_t n_users,
+                  const float* item_emb, const uint8_t* item_has, int32_t n_items, int32_t D, int32_t item_stride,
+                  int32_t mode, float* user_emb, int32_t user_stride, uint8_t* user_has, int32_t* user_count,
+                  uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- multi-GPU: the path's one collective (the reference has no distributed path) ----
  * Batch rows are sharded over one process per GPU, tables and weights replicated; every rank ends with all scores through ONE
  * all-gather of the per-rank score slices over RCCL / xGMI, enqueued on the caller's HIP stream (no host synchronisation).

@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = [
     "sprk_pack_columns", "sprk_pack_columns_device", "sprk_pack_last_route", "sprk_set_many_streams", "sprk_set_many_batches", "sprk_emb_rank",
     "sprk_emb_topk", "sprk_emb_topk_workspace_bytes", "sprk_join_features", "sprk_rank_scores",
     "sprk_metrics_state_bytes", "sprk_metrics_reset", "sprk_metrics_update",
-    "sprk_feature_eng_workspace_bytes", "sprk_feature_eng",
+    "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_user_emb_workspace_bytes", "sprk_user_emb",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -271,8 +271,12 @@ def load_library():
                                          vp, vp, vp, vp, vp, vp, vp, vp, vp,                             # the sample columns
                                          vp, vp, i32, vp, vp,                                            # the store's tables (or NULL)
                                          vp, vp, vp, sz, vp]                                             # error word, sample count, workspace, stream
+        lib.sprk_user_emb_workspace_bytes.argtypes = [C.c_int64, i32]
+        lib.sprk_user_emb_workspace_bytes.restype = sz
+        lib.sprk_user_emb.argtypes = [vp, vp, C.c_int64, i32, vp, vp, i32, i32, i32,                     # ratings, sizes, item table, D, item_stride
+                                      i32, vp, i32, vp, vp, vp, vp, sz, vp]                              # mode, the three outputs, error word, workspace, stream
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

@@ -65,6 +65,30 @@ inline unsigned fe_grid(long long items) {
     return (unsigned)(g < 1 ? 1 : g);
 }
 inline unsigned fe_grid_capped(long long items) { const unsigned g = fe_grid(items); return g < (unsigned)FE_MAX_GRID ? g : (unsigned)FE_MAX_GRID; }
+
+// The segments k_fe_sort_short listed (longer than `cap`), sorted where they are: chunks of `cap` in LDS, then merge passes between
+// (seg_ts, seg_row) and (tmp_ts, tmp_row), and a copy back after an odd number of passes.  n = all keys: no segment is longer.
+int fe_sort_long_segments(int cap, long long n, const unsigned* seg_off, long long* seg_ts, int* seg_row, long long* tmp_ts, int* tmp_row, const int* long_list,
+                          const unsigned* n_long, hipStream_t st) {
+    if (n <= cap) return SPRK_OK;                                           // no segment can be longer than the LDS sort holds
+    const size_t sort_lds = (size_t)cap * 12;
+    const unsigned lg = fe_grid_capped(n);
+    const unsigned cg = (unsigned)((n + cap - 1) / cap) < (unsigned)FE_MAX_GRID ? (unsigned)((n + cap - 1) / cap) : (unsigned)FE_MAX_GRID;
+    hipLaunchKernelGGL(k_fe_sort_long_chunks, dim3(cg), dim3(FE_THREADS), sort_lds, st, cap, seg_off, seg_ts, seg_row, long_list, n_long);
+    HIP_TRY(hipGetLastError());
+    long long* ts[2] = {seg_ts, tmp_ts};
+    int* row[2] = {seg_row, tmp_row};
+    int at = 0;
+    for (long long width = cap; width < n; width *= 2, at ^= 1) {
+        hipLaunchKernelGGL(k_fe_merge_pass, dim3(lg), dim3(FE_THREADS), 0, st, width, seg_off, (const long long*)ts[at], (const int*)row[at], ts[at ^ 1], row[at ^ 1], long_list, n_long);
+        HIP_TRY(hipGetLastError());
+    }
+    if (at) {
+        hipLaunchKernelGGL(k_fe_long_copy, dim3(lg), dim3(FE_THREADS), 0, st, seg_off, (const long long*)tmp_ts, (const int*)tmp_row, seg_ts, seg_row, long_list, n_long);
+        HIP_TRY(hipGetLastError());
+    }
+    return SPRK_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -128,26 +152,7 @@ int sprk_feature_eng(const int32_t* user_id, const int32_t* movie_id, const floa
         const unsigned ug = n_users < 1 ? 1u : (unsigned)n_users < 65536u * 16u ? (unsigned)n_users : 65536u * 16u;
         hipLaunchKernelGGL(k_fe_sort_short, dim3(ug), dim3(FE_THREADS), sort_lds, st, (int)n_users, cap, (const unsigned*)w.seg_off, w.seg_ts, w.seg_row, w.long_list, w.n_long);
         HIP_TRY(hipGetLastError());
-        if (n > cap) {                                                      // a segment can be longer than the LDS sort holds
-            const unsigned lg = fe_grid_capped(n);
-            const unsigned cg = (unsigned)((n + cap - 1) / cap) < (unsigned)FE_MAX_GRID ? (unsigned)((n + cap - 1) / cap) : (unsigned)FE_MAX_GRID;
-            hipLaunchKernelGGL(k_fe_sort_long_chunks, dim3(cg), dim3(FE_THREADS), sort_lds, st, cap, (const unsigned*)w.seg_off, w.seg_ts, w.seg_row, (const int*)w.long_list,
-                               (const unsigned*)w.n_long);
-            HIP_TRY(hipGetLastError());
-            long long* ts[2] = {w.seg_ts, w.tmp_ts};
-            int* row[2] = {w.seg_row, w.tmp_row};
-            int at = 0;
-            for (long long width = cap; width < n; width *= 2, at ^= 1) {
-                hipLaunchKernelGGL(k_fe_merge_pass, dim3(lg), dim3(FE_THREADS), 0, st, width, (const unsigned*)w.seg_off, (const long long*)ts[at], (const int*)row[at], ts[at ^ 1], row[at ^ 1],
-                                   (const int*)w.long_list, (const unsigned*)w.n_long);
-                HIP_TRY(hipGetLastError());
-            }
-            if (at) {
-                hipLaunchKernelGGL(k_fe_long_copy, dim3(lg), dim3(FE_THREADS), 0, st, (const unsigned*)w.seg_off, (const long long*)w.tmp_ts, (const int*)w.tmp_row, w.seg_ts, w.seg_row,
-                                   (const int*)w.long_list, (const unsigned*)w.n_long);
-                HIP_TRY(hipGetLastError());
-            }
-        }
+        SPRK_TRY(fe_sort_long_segments(cap, n, w.seg_off, w.seg_ts, w.seg_row, w.tmp_ts, w.tmp_row, w.long_list, w.n_long, st));
     }
     if (n_movies > 0) {
         hipLaunchKernelGGL(k_fe_movie_stats, dim3(fe_grid(n_movies)), dim3(FE_THREADS), 0, st, (int)n_movies, movie_year, (const unsigned*)w.mv_cnt, (const unsigned long long*)w.mv_S,

@@ -1,5 +1,6 @@
 // sparrow_feature_eng.hip -- ratings -> training samples and the feature store's rows on the device: the kernels (k_feature_eng.h) and
-// their C ABI (api_feature_eng.h: sprk_feature_eng_workspace_bytes / sprk_feature_eng).  A translation unit of its own, like
+// their C ABI (api_feature_eng.h: sprk_feature_eng_workspace_bytes / sprk_feature_eng); and ratings + item embeddings -> user embeddings
+// (k_user_emb.h, api_user_emb.h: sprk_user_emb_workspace_bytes / sprk_user_emb), which shares the per-user scan, sort and merge.  A translation unit of its own, like
 // sparrow_metrics.hip: nothing here is used by the forward engine and nothing of the engine is used here.  Shares with the other units
 // only host_common.h (the thread's error string behind sprk_last_error, HIP_TRY, the roctx ranges), which opens the kernels' namespace
 // this file closes.
@@ -18,9 +19,11 @@
 
 #include "host_common.h"
 #include "k_feature_eng.h"
+#include "k_user_emb.h"
 
 }  // namespace sprk_dev
 #pragma GCC visibility pop
 using namespace sprk_dev;
 
 #include "api_feature_eng.h"
+#include "api_user_emb.h"

@@ -1,0 +1,257 @@
+"""User embeddings on the device (sprk_user_emb, csrc/k_user_emb.h) against their definition, userembedding.user_emb_host: the three
+outputs byte for byte -- the order of the float32 sum and the rounding of the division included -- on both routes (input grouped by
+user: summed where it lies; any other input: scattered and sorted by input row), and the recommendations built on them."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from sparrowrecsys_amd import _lib as L
+from sparrowrecsys_amd import ranker as R
+from sparrowrecsys_amd import userembedding as UE
+from tests import userembedding_cases as cases
+
+pytestmark = pytest.mark.gpu
+
+
+def _device(user, row, emb, has, n_users, mode="mean", D=None, user_stride=None):
+    """sprk_user_emb through userembedding.user_emb_device -> (emb [n_users, D], has, count) on the host, the error word."""
+    import torch
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).cuda()
+    D = emb.shape[1] if D is None else D
+    e, h, c, word = UE.user_emb_device(up(user, np.int32), up(row, np.int32), up(emb, np.float32), up(has, np.uint8), n_users, mode, D=D, user_stride=user_stride)
+    return (np.ascontiguousarray(e.cpu().numpy()[:, :D]), h.cpu().numpy(), c.cpu().numpy()), int(word.cpu()[0])
+
+
+def _assert_same(got, want):
+    for g, w, name in zip(got, want, ("emb", "has", "count")):
+        assert g.dtype == w.dtype and g.shape == w.shape, name
+        assert g.tobytes() == w.tobytes(), (name, np.flatnonzero((g != w).reshape(len(g), -1).any(axis=1))[:8])
+
+
+def _check(case, mode, D=None, user_stride=None):
+    D = case["emb"].shape[1] if D is None else D
+    want = UE.user_emb_host(case["user"], case["row"], case["emb"][:, :D], case["has"], case["n_users"], mode)
+    got, err = _device(case["user"], case["row"], case["emb"], case["has"], case["n_users"], mode, D, user_stride)
+    assert err == -1
+    _assert_same(got, want)
+    return got
+
+
+@pytest.fixture(scope="module")
+def synthetic(lib):
+    return {grouped: cases.synthetic(grouped=grouped) for grouped in (False, True)}
+
+
+@pytest.mark.parametrize("sort_cap", [None, 64])
+@pytest.mark.parametrize("grouped", [False, True])
+@pytest.mark.parametrize("mode", ["mean", "sum"])
+def test_synthetic_set_equals_the_host_definition(synthetic, monkeypatch, mode, grouped, sort_cap):
+    """tests/test_userembedding.py asserts the cases the set holds and that a forward sum changes most of its words.  Shuffled input
+    takes the scatter and the sort -- with SPRK_FE_SORT_CAP = 64 the user of 300 ratings, like every user above 64, in chunks and
+    merge passes --, grouped input is summed where it lies."""
+    if sort_cap is not None:
+        monkeypatch.setenv("SPRK_FE_SORT_CAP", str(sort_cap))
+    _check(synthetic[grouped], mode, D=10)
+
+
+@pytest.mark.parametrize("sort_cap", [None, 64])
+@pytest.mark.parametrize("interleaved", [False, True])
+@pytest.mark.parametrize("mode", ["mean", "sum"])
+def test_hand_worked_user(lib, monkeypatch, mode, interleaved, sort_cap):
+    """The words written out in tests/userembedding_cases.py; interleaved with a second user's rows the input is not grouped."""
+    if sort_cap is not None:
+        monkeypatch.setenv("SPRK_FE_SORT_CAP", str(sort_cap))
+    case = cases.hand_worked()
+    user, row, n_users = case["user"], case["row"], 1
+    if interleaved:
+        user, row, n_users = np.array([0, 1, 0, 1, 0, 1, 0]), np.array([0, 3, 1, 2, 2, 0, 3]), 2
+    got, err = _device(user, row, case["emb"], case["has"], n_users, mode)
+    assert err == -1
+    assert got[0][:1].view(np.uint32).tolist() == (cases.HAND_MEAN_WORDS if mode == "mean" else cases.HAND_SUM_WORDS).tolist()
+    assert got[1][0] == 1 and got[2][0] == cases.HAND_COUNT[mode]
+    _assert_same(got, UE.user_emb_host(user, row, case["emb"], case["has"], n_users, mode))
+
+
+@pytest.mark.parametrize("pad", [0, 3])
+@pytest.mark.parametrize("D", [1, 10, 16, 17, 64, 65])
+def test_widths_across_the_lane_group_switch_and_the_64_step(lib, D, pad):
+    """D <= 16: 16 lanes a user; above: a wave a user, D = 65 in two walks.  Both strides D + pad; shuffled input, both modes."""
+    case = cases.synthetic(D=D, stride=D + pad)
+    _check(case, "mean", D=D, user_stride=D + pad)
+    _check(case, "sum", D=D, user_stride=D + pad)
+
+
+def test_subnormals_are_summed_and_kept(lib):
+    """1e-40 is a float32 subnormal: three of them sum to 3e-40, and the mean of (1e-40, 1e-40, 1.5e-45) is subnormal too; a kernel
+    that flushes gives 0."""
+    emb = np.array([[1e-40, 1e-40], [1e-40, 1.5e-45]], dtype=np.float32)
+    assert (emb != 0).all() and (np.abs(emb) < np.finfo(np.float32).tiny).all()
+    case = {"user": np.array([0, 0, 0, 1]), "row": np.array([0, 0, 1, 1]), "emb": emb, "has": np.ones(2, np.uint8), "n_users": 2}
+    for mode in ("mean", "sum"):
+        got = _check(case, mode)
+        assert (got[0] != 0).all()
+
+
+def test_no_ratings_and_one_user(lib):
+    emb, has = cases.HAND_EMB, cases.HAND_HAS
+    empty = np.zeros(0, np.int32)
+    for n_users in (1, 5):
+        got, err = _device(empty, empty, emb, has, n_users)
+        assert err == -1 and not got[0].any() and not got[1].any() and not got[2].any() and got[0].shape == (n_users, 3)
+    _check({"user": np.zeros(3, np.int32), "row": np.array([3, 0, 2]), "emb": emb, "has": has, "n_users": 1}, "mean")
+    got, err = _device(empty, empty, emb, has, 0)
+    assert err == -1 and got[0].shape == (0, 3)
+    _check({"user": np.array([0, 1, 0]), "row": np.array([0, 0, 0]), "emb": np.zeros((0, 4), np.float32), "has": np.zeros(0, np.uint8), "n_users": 2}, "mean")
+
+
+@pytest.mark.parametrize("cap", [64, 4096])
+def test_segments_at_the_sort_capacity_and_one_past(lib, monkeypatch, cap):
+    """Users of cap and of cap + 1 ratings, interleaved row by row: the first is the longest segment the LDS sort takes, the second
+    the shortest that goes through two chunks and a merge pass."""
+    monkeypatch.setenv("SPRK_FE_SORT_CAP", str(cap))
+    rng = np.random.RandomState(cap)
+    base = cases.synthetic()
+    user = np.concatenate([np.tile([0, 1], cap), [1, 2]])
+    case = dict(base, user=user, row=rng.randint(0, cases.N_ITEMS, len(user)), n_users=3)
+    assert np.bincount(user).tolist() == [cap, cap + 1, 1]
+    _check(case, "mean", D=10)
+
+
+def test_error_word_names_the_lowest_bad_row_and_other_users_are_untouched(synthetic):
+    case = synthetic[False]
+    user = case["user"].copy()
+    bad = [4000, 123, 2500]
+    user[bad] = [97, -1, 2**31 - 1]
+    got, err = _device(user, case["row"], case["emb"], case["has"], 97, D=10)
+    assert (err >> 32, err & 0xffffffff) == (1, 123)
+    keep = np.ones(len(user), dtype=bool)
+    keep[bad] = False
+    _assert_same(got, UE.user_emb_host(user[keep], case["row"][keep], case["emb"][:, :10], case["has"], 97))     # the bad rows took no part
+    with pytest.raises(ValueError) as host:
+        UE.user_emb_host(user, case["row"], case["emb"][:, :10], case["has"], 97)
+    assert str(host.value) == "ratings row 123: userId outside the user table"
+
+
+FILL = 0xA5
+GUARD_ROWS, GUARD_BYTES = 64, 4096
+
+
+def _is_fill(a):
+    return bool((np.ascontiguousarray(a).view(np.uint8) == FILL).all())
+
+
+@pytest.mark.parametrize("grouped,sort_cap", [(False, 64), (False, None), (True, None)])
+def test_nothing_is_written_outside_the_outputs_or_the_workspace(lib, synthetic, monkeypatch, grouped, sort_cap):
+    """Guard bands of a fill pattern after the three outputs, between D and the stride of every user_emb row, and on both sides of a
+    workspace of exactly the advertised length keep their fill."""
+    import torch
+    if sort_cap is not None:
+        monkeypatch.setenv("SPRK_FE_SORT_CAP", str(sort_cap))
+    case = synthetic[grouped]
+    n, n_users, D, stride = len(case["user"]), case["n_users"], 10, 13
+    dev = torch.device("cuda", torch.cuda.current_device())
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    def filled(shape, dtype):
+        n_bytes = int(np.prod(shape)) * torch.empty(0, dtype=dtype).element_size()
+        return torch.full((n_bytes,), FILL, dtype=torch.uint8, device=dev).view(dtype).reshape(shape)
+    u_d, r_d, e_d, h_d = up(case["user"]), up(case["row"]), up(case["emb"]), up(case["has"])
+    o_emb, o_has, o_count = filled((n_users + GUARD_ROWS, stride), torch.float32), filled((n_users + GUARD_ROWS,), torch.uint8), filled((n_users + GUARD_ROWS,), torch.int32)
+    word = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    ws_bytes = lib.sprk_user_emb_workspace_bytes(n, n_users)
+    assert ws_bytes > 0 and ws_bytes % 16 == 0
+    arena = torch.full((GUARD_BYTES + ws_bytes + GUARD_BYTES,), FILL, dtype=torch.uint8, device=dev)
+    assert arena.data_ptr() % 16 == 0
+    p = lambda x: C.c_void_p(x.data_ptr())
+    L.check(lib.sprk_user_emb(p(u_d), p(r_d), n, n_users, p(e_d), p(h_d), cases.N_ITEMS, D, case["emb"].shape[1], 0, p(o_emb), stride, p(o_has), p(o_count), p(word),
+                              C.c_void_p(arena.data_ptr() + GUARD_BYTES), ws_bytes, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    assert int(word.cpu()[0]) == -1
+    arena, emb, has, count = arena.cpu().numpy(), o_emb.cpu().numpy(), o_has.cpu().numpy(), o_count.cpu().numpy()
+    assert _is_fill(arena[:GUARD_BYTES]) and _is_fill(arena[GUARD_BYTES + ws_bytes:])
+    assert _is_fill(emb[n_users:]) and _is_fill(has[n_users:]) and _is_fill(count[n_users:]) and _is_fill(emb[:n_users, D:])
+    want = UE.user_emb_host(case["user"], case["row"], case["emb"][:, :D], case["has"], n_users)
+    _assert_same((np.ascontiguousarray(emb[:n_users, :D]), has[:n_users], count[:n_users]), want)
+
+
+def test_two_runs_give_the_same_bytes(synthetic):
+    case = synthetic[False]
+    runs = [[a.tobytes() for a in _device(case["user"], case["row"], case["emb"], case["has"], 97, D=10)[0]] for _ in range(2)]
+    assert runs[0] == runs[1]
+
+
+def test_side_stream_and_no_synchronisation(synthetic):
+    """The call is enqueued behind a spin of some milliseconds on a side stream and returns while the stream is still busy; the event
+    recorded after it orders the read."""
+    import torch
+    case = synthetic[False]
+    want = UE.user_emb_host(case["user"], case["row"], case["emb"][:, :10], case["has"], 97)
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).cuda()
+    args = (up(case["user"], np.int32), up(case["row"], np.int32), up(case["emb"], np.float32), up(case["has"], np.uint8))
+    torch.cuda.synchronize()
+    side, done = torch.cuda.Stream(), torch.cuda.Event()
+    with torch.cuda.stream(side):
+        torch.cuda._sleep(40_000_000)
+        e, h, c, word = UE.user_emb_device(*args, 97, "mean", D=10)
+        done.record(side)
+        returned_early = not done.query()
+    done.synchronize()
+    assert returned_early
+    assert int(word.cpu()[0]) == -1
+    _assert_same((np.ascontiguousarray(e.cpu().numpy()), h.cpu().numpy(), c.cpu().numpy()), want)
+
+
+@pytest.fixture(scope="module")
+def recommender(lib):
+    """A ranker over 300 movies (ids 3 i + 1, D = 10) and ratings of users 0 .. 51 -- user 50 none, user 51 only movies the ranker does
+    not hold --, the embeddings built on the device and by the definition."""
+    rng = np.random.RandomState(5)
+    ids = 3 * np.arange(300) + 1
+    ranker = R.EmbRanker({int(m): rng.standard_normal(10).astype(np.float32) for m in ids})
+    n = 3000
+    user = rng.randint(0, 50, n)
+    movie = np.where(rng.rand(n) < 0.9, ids[rng.randint(0, 300, n)], rng.randint(-5, 1200, n))
+    user, movie = np.concatenate([user, [51, 51, 51]]), np.concatenate([movie, [0, 2, 5000]])
+    ratings = {"userId": user, "movieId": movie, "rating": np.full(len(user), 4.0), "timestamp": np.arange(len(user))}
+    built = UE.build(ratings, ranker, n_users=52)
+    host = UE.user_emb_host(user, ranker.rows(movie), ranker.table.cpu().numpy(), ranker.has.cpu().numpy(), 52)
+    return ranker, ratings, built, host
+
+
+def test_build_from_ratings_equals_the_definition(recommender):
+    import torch
+    ranker, ratings, built, host = recommender
+    _assert_same(built.to_host(), host)
+    assert host[1].tolist() == [1] * 50 + [0, 1] and not host[0][51].any()
+    on_device = {k: torch.from_numpy(v).cuda() for k, v in ratings.items()}
+    _assert_same(UE.build(on_device, ranker).to_host(), host)                    # device columns, the default table size
+    assert built.vector(50) is None and built.vector(3).tobytes() == host[0][3].tobytes()
+    bad = dict(ratings, userId=ratings["userId"].copy())
+    bad["userId"][[2000, 17]] = [52, 2**40]
+    with pytest.raises(ValueError) as e:
+        UE.build(bad, ranker, n_users=52)
+    assert str(e.value) == "ratings row 17: userId outside the user table"
+
+
+def test_recommend_equals_topk_on_the_host_embeddings(recommender):
+    ranker, ratings, built, host = recommender
+    users = list(range(52))
+    got = built.recommend(ranker, users, 10)
+    scores, rows = ranker.topk(host[0], 10, query_has=host[1])
+    mine, my_rows = ranker.topk(built.table, 10, query_has=built.has)
+    assert my_rows.cpu().numpy().tobytes() == rows.cpu().numpy().tobytes()
+    assert mine.cpu().numpy().tobytes() == scores.cpu().numpy().tobytes()        # the score doubles, bit for bit
+    rows = rows.cpu().numpy()
+    for u in users:
+        assert got[u] == ([] if u == 50 else ranker.ids[rows[u]].tolist()), u
+    assert len(got[51]) == 10                                                     # the all-zero vector: what topk gives for it
+    assert built.recommend(ranker, [50, -1, 52, 7], 10) == [[], [], [], got[7]]
+    assert built.recommend(ranker, [7], 10, largest=False) == [ranker.ids[ranker.topk(host[0][7:8], 10, largest=False)[1][0].cpu().numpy()].tolist()]
+    ranker2, built2 = R.EmbRanker.from_ratings_and_items({int(m): ranker.table[i].cpu().numpy() for i, m in enumerate(ranker.ids)}, ratings, n_users=52)
+    _assert_same(built2.to_host(), host)
+
+
+def test_row_lut_refuses_an_id_that_would_make_a_huge_table(lib):
+    ranker = R.EmbRanker({1: np.ones(4, np.float32), 1 << 28: np.ones(4, np.float32)})
+    with pytest.raises(ValueError, match="movie id 268435456"):
+        ranker.row_lut()
+    assert R.EmbRanker({1: np.ones(4, np.float32), 7: np.ones(4, np.float32)}).row_lut().cpu().tolist() == [-1, 0, -1, -1, -1, -1, -1, 1, -1]
