@@ -563,6 +563,60 @@ int sprk_user_emb(const int32_t* user_id, const int32_t* item_row, int64_t n_rat
                   int32_t mode, float* user_emb, int32_t user_stride, uint8_t* user_has, int32_t* user_count,
                   uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the movie catalogue on the device: average ratings, sorted lists, candidates and the default similarity ranker ----
+ * The arithmetic of the reference's DataManager and SimilarMovieProcess (Movie.java:93-98, DataManager.java:253-283,
+ * SimilarMovieProcess.java:39-83 and :145-159).  The definition, rule by rule, is sparrowrecsys_amd/catalog.py catalog_host / similar_host
+ * (DESIGN.md section 5.9); these calls give the same bits.
+ *
+ * sprk_catalog_build.  In, device memory: the rating columns movie_id (int32) and rating (float32), n_ratings rows in input order; the
+ * movie table, n_movies rows indexed by movie id: movie_genre_mask (bit g = genre g of a dictionary of n_genres <= 32 genres), movie_has
+ * (the table holds the movie), movie_year (DataManager's releaseYear, 0 = none), movie_file_pos (the movie's position in movies.csv) and
+ * movie_hash_pos (its position in the iteration order of Java's HashMap), the last two permutations of [0, movies held) over the
+ * movies held.  A rating whose movie lies outside the table, or is not held, is skipped (movieMap.get == null): no error.
+ * Out, device memory, every row written: avg_rating [n_movies] float64 -- per movie, over its ratings in input order from avg = 0.0,
+ * n = 0: avg = (avg * (double)n + (double)rating) / (double)(n + 1), one multiply, one add and one IEEE division per rating, never fused
+ * or reassociated, which is NOT sum / n in general; 0.0 for a movie without a rating -- and rating_count [n_movies].  The 2 (G + 1)
+ * lists, G = n_genres, as list_offsets [2 (G + 1) + 1] into list_movies [list_capacity]: list g < G = the movies of genre g by
+ * average rating, list G = every movie held by average rating, list G + 1 + g = genre g by year, list 2 G + 1 = every movie by year;
+ * all descending (the rating in Double.compare order), ties by file position in a genre list and by hash position in the whole
+ * catalogue's, as Java's stable sort leaves them.  list_capacity >= the lists' total, 2 (sum of the movies' genre counts + movies
+ * held); the entries past the total are -1.  Input grouped by movie (every movie's rows adjacent) is walked where it lies; any other
+ * input is scattered into per-movie segments and sorted by input row, in LDS up to 4096 rows of one movie (SPRK_FE_SORT_CAP, as for
+ * the feature engineering call) and by chunked sort + merge passes beyond; so are the lists.  A movie of fewer than 128 ratings is
+ * walked by one lane, a longer one by a wave of its own.
+ * `error_key` is ONE caller-provided device word, set to ~0 before the call: the kernels atomicMin (3 << 32 | input row) into it for a
+ * rating that is not finite (the row takes no further part) and (4 << 32) when the lists do not fit list_capacity (every list is then
+ * empty); when it is not ~0 afterwards the outputs hold no result.
+ * 0 <= n_ratings < 2^31 - 1, 0 <= n_movies < 2^31 - 1, 0 <= list_capacity < 2^31 - 1, 0 <= n_genres <= 32, no NULL or misaligned pointer, a
+ * workspace of sprk_catalog_build_workspace_bytes bytes (0 for sizes the call rejects; the message names the bytes needed), 16-byte
+ * aligned: anything else returns SPRK_EINVAL BEFORE any device call.
+ *
+ * sprk_catalog_similar: one workgroup per query movie.  In: query_movie [n_queries]; the table columns above with movie_n_genres
+ * (uint8, the movie's number of genres) and the build's avg_rating, list_offsets and list_movies (list_entries of them).
+ * mode 0 (candidateGenerator): the union over the query's genres of the first top_n entries of that genre's rating list; mode 1
+ * (multipleRetrievalCandidates): those, the first extra_n of the whole catalogue's rating list and the first extra_n of its year
+ * list; minus the query itself, in ascending movie id order.  A query the table does not hold has no candidates.
+ * score_kind 0: out_ids [n_queries][out_stride] = the candidates, padded with -1, out_count = their number (ids past out_stride are
+ * not written: a count above out_stride tells); out_scores is not used.  score_kind 1: per candidate c of query q, in doubles, every
+ * operation rounded on its own: same = popcount(mask_q & mask_c), score = ((same / (n_genres_q + n_genres_c)) / 2.0) * 0.7 +
+ * (avg_c / 5.0) * 0.3 (0 / 0 = NaN); the candidates sorted by score descending in Double.compare order (every NaN one greatest value,
+ * written as 0x7ff8000000000000), equal scores by ascending id; the first `size` ids and scores are written, padded with -1 / 0.0, and
+ * out_count = min(size, candidates).  n_queries >= 0, n_movies >= 0, 0 <= n_genres <= 32, top_n >= 0, extra_n >= 0,
+ * 32 top_n + 2 extra_n <= 4096, out_stride >= 1, 0 <= size (<= out_stride for score_kind 1), no NULL or misaligned pointer: anything else
+ * returns SPRK_EINVAL BEFORE any device call.  No workspace.
+ * Both are asynchronous on `stream`: no synchronisation, no memory owned by the library; all index arithmetic in 64 bits. */
+size_t sprk_catalog_build_workspace_bytes(int64_t n_ratings, int32_t n_movies, int64_t list_capacity);
+int sprk_catalog_build(const int32_t* movie_id, const float* rating, int64_t n_ratings, int32_t n_movies,
+                       const uint32_t* movie_genre_mask, const uint8_t* movie_has, const int32_t* movie_year,
+                       const int32_t* movie_file_pos, const int32_t* movie_hash_pos, int32_t n_genres,
+                       double* avg_rating, int32_t* rating_count, int32_t* list_offsets, int32_t* list_movies, int64_t list_capacity,
+                       uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+int sprk_catalog_similar(const int32_t* query_movie, int32_t n_queries, int32_t n_movies,
+                         const uint32_t* movie_genre_mask, const uint8_t* movie_has, const uint8_t* movie_n_genres, const double* avg_rating, int32_t n_genres,
+                         const int32_t* list_offsets, const int32_t* list_movies, int64_t list_entries,
+                         int32_t mode, int32_t top_n, int32_t extra_n, int32_t score_kind, int32_t size,
+                         int32_t* out_ids, double* out_scores, int32_t out_stride, int32_t* out_count, void* stream);
+
 /* ---- multi-GPU: the path's one collective (the reference has no distributed path) ----
  * Batch rows are sharded over one process per GPU, tables and weights replicated; every rank ends with all scores through ONE
  * all-gather of the per-rank score slices over RCCL / xGMI, enqueued on the caller's HIP stream (no host synchronisation).

@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = [
     "sprk_emb_topk", "sprk_emb_topk_workspace_bytes", "sprk_join_features", "sprk_rank_scores",
     "sprk_metrics_state_bytes", "sprk_metrics_reset", "sprk_metrics_update",
     "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_user_emb_workspace_bytes", "sprk_user_emb",
+    "sprk_catalog_build_workspace_bytes", "sprk_catalog_build", "sprk_catalog_similar",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -275,8 +276,14 @@ def load_library():
         lib.sprk_user_emb_workspace_bytes.restype = sz
         lib.sprk_user_emb.argtypes = [vp, vp, C.c_int64, i32, vp, vp, i32, i32, i32,                     # ratings, sizes, item table, D, item_stride
                                       i32, vp, i32, vp, vp, vp, vp, sz, vp]                              # mode, the three outputs, error word, workspace, stream
+        lib.sprk_catalog_build_workspace_bytes.argtypes = [C.c_int64, i32, C.c_int64]
+        lib.sprk_catalog_build_workspace_bytes.restype = sz
+        lib.sprk_catalog_build.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, vp, vp, i32,                  # ratings, sizes, movie table, n_genres
+                                           vp, vp, vp, vp, C.c_int64, vp, vp, sz, vp]                       # the outputs, list_capacity, error word, workspace, stream
+        lib.sprk_catalog_similar.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, C.c_int64,           # queries, movie table, n_genres, the lists
+                                             i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]                  # mode, top_n, extra_n, score_kind, size, the outputs, stream
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib
