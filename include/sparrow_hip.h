@@ -617,6 +617,64 @@ int sprk_catalog_similar(const int32_t* query_movie, int32_t n_queries, int32_t 
                          int32_t mode, int32_t top_n, int32_t extra_n, int32_t score_kind, int32_t size,
                          int32_t* out_ids, double* out_scores, int32_t out_stride, int32_t* out_count, void* stream);
 
+/* ---- ALS collaborative filtering on the device: ratings -> factors, scores and a top-K for every row ----
+ * The reference's offline/spark/model/CollaborativeFiltering.scala (Spark ALS, explicit feedback, no non-negativity, maxIter 5, regParam
+ * 0.01, rank 10; then the RMSE of held-out pairs, recommendForAllUsers and recommendForAllItems).  The definition, rule by rule, is
+ * sparrowrecsys_amd/als.py als_host / predict_host / topk_host (with the deviations from Spark); these calls give
+ * the same bits.
+ *
+ * sprk_als_fit.  Every iteration recomputes the item factors from the user factors, then the user factors from the new item factors, so
+ * only the initial USER factors are read.  One destination row (a movie, then a user) walks its ratings in ascending order of the
+ * other side's id, a repeated pair by ascending input row, and accumulates in doubles from +0.0, with x = the other side's factor row
+ * widened to double: the packed upper triangle ata[i, j] += x[i] * x[j] (entry (i, j), i <= j, at j (j + 1) / 2 + i) and atb[i] +=
+ * (double)rating * x[i], the product rounded, then the sum; adds (double)n * reg (n = the row's ratings) to the diagonal; factors
+ * U^T U = ata column by column (netlib's dpptrf), solves by forward and back substitution (dpptrs) in als.py cholesky_solve_host's
+ * operation order, nothing fused, division and square root correctly rounded; and rounds the solution to float32.  A row's ratings
+ * are never split and there is no float or double atomic: the result is a function of the input alone.  A row without ratings gets
+ * has 0 and zeros.
+ * In, device memory: user_id, movie_id (int32) and rating (float32), n_ratings rows in any order; init_user [n_users][init_stride]
+ * float32 of which `rank` per row are read.  Out, device memory, EVERY row written: user_factors [n_users][user_stride] and item_factors
+ * [n_items][item_stride] (`rank` floats per row; the floats between rank and the stride are left alone), user_has / item_has (the row
+ * has a rating), user_count / item_count.  iters = 0 writes init_user to user_factors, zeros to item_factors, and has and the counts.
+ * `error_key` is ONE caller-provided device word, set to ~0 before the call, into which the kernels atomicMin (kind << 32 | index):
+ * kind 1, 2, 3 = a user id outside [0, n_users), a movie id outside [0, n_items), a rating that is not finite, index = the input row
+ * (such a row takes no further part); kind 7 = a value of init_user that is not finite, index = its row; kind 5 / 6 = the normal
+ * equations of a user / a movie are not positive definite (some d = A[j, j] - sum is not > 0; with reg = 0 and fewer ratings than rank
+ * the ordinary outcome), index = the id, the smallest of the first half-sweep that has one.  Once the word is set no further half-sweep
+ * runs; when it is not ~0 afterwards the outputs hold no result.  The ratings are scattered into per-movie and per-user segments once
+ * and sorted by (other id, input row) -- in LDS up to 4096 ratings of one row (SPRK_FE_SORT_CAP, as for the feature engineering call), by
+ * chunked sort + merge passes beyond.  The workspace is sprk_als_workspace_bytes bytes, 16-byte aligned (0 for sizes the call rejects).
+ * 0 <= n_ratings < 2^31 - 1, 0 <= n_users < 2^31 - 1, 0 <= n_items < 2^31 - 1, 1 <= rank <= 16, iters >= 0, reg finite and >= 0, every
+ * stride >= rank, no NULL or misaligned pointer, a sufficient workspace (the message names the bytes needed): anything else returns
+ * SPRK_EINVAL BEFORE any device call.
+ *
+ * sprk_als_predict: out[i] = the float32 dot of user_factors[user[i]] and item_factors[item[i]] in index order from 0.0f, every product
+ * and every sum rounded on its own (ALSModel's sdot); NaN (0x7fc00000) when either id lies outside its table or has has == 0 -- Spark's
+ * cold-start NaN, which coldStartStrategy = "drop" drops.  n >= 0, n_users >= 0, n_items >= 0, 1 <= rank <= 16, strides >= rank.
+ *
+ * sprk_als_topk: for every row of query [n_queries][query_stride] the K rows of table [n_rows][table_stride] with the largest such dot:
+ * descending score, equal scores by ascending row (a NaN score, possible only with non-finite factors, sorts greatest); table rows with
+ * table_has == 0 are left out.  scores / rows [n_queries][K]; the places past the rows available, and every place of a query with
+ * query_has == 0, hold NaN (0x7fc00000) / -1.  The selection is sprk_emb_topk's: chunks of 4096 rows (SPRK_EMB_TOPK_CHUNK) sorted in
+ * LDS, then a merge tree.  1 <= K <= 1024, 1 <= rank <= 16, n_rows >= 0, n_queries >= 0; the workspace is
+ * sprk_als_topk_workspace_bytes bytes (0 when the table is one chunk, and for sizes the call rejects), 16-byte aligned.
+ * All are asynchronous on `stream`: no synchronisation, no memory owned by the library; all index arithmetic in 64 bits. */
+size_t sprk_als_workspace_bytes(int64_t n_ratings, int32_t n_users, int32_t n_items, int32_t rank);
+int sprk_als_fit(const int32_t* user_id, const int32_t* movie_id, const float* rating, int64_t n_ratings,
+                 int32_t n_users, int32_t n_items, int32_t rank, double reg, int32_t iters,
+                 const float* init_user, int32_t init_stride,
+                 float* user_factors, int32_t user_stride, float* item_factors, int32_t item_stride,
+                 uint8_t* user_has, uint8_t* item_has, int32_t* user_count, int32_t* item_count,
+                 uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+int sprk_als_predict(const int32_t* user, const int32_t* item, int64_t n,
+                     const float* user_factors, int32_t user_stride, const uint8_t* user_has,
+                     const float* item_factors, int32_t item_stride, const uint8_t* item_has,
+                     int32_t n_users, int32_t n_items, int32_t rank, float* out, void* stream);
+size_t sprk_als_topk_workspace_bytes(int32_t n_rows, int32_t n_queries, int32_t K);
+int sprk_als_topk(const float* table, const uint8_t* table_has, int32_t n_rows, int32_t rank, int32_t table_stride,
+                  const float* query, const uint8_t* query_has, int32_t n_queries, int32_t query_stride,
+                  int32_t K, float* scores, int32_t* rows, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- multi-GPU: the path's one collective (the reference has no distributed path) ----
  * Batch rows are sharded over one process per GPU, tables and weights replicated; every rank ends with all scores through ONE
  * all-gather of the per-rank score slices over RCCL / xGMI, enqueued on the caller's HIP stream (no host synchronisation).

@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = [
     "sprk_metrics_state_bytes", "sprk_metrics_reset", "sprk_metrics_update",
     "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_user_emb_workspace_bytes", "sprk_user_emb",
     "sprk_catalog_build_workspace_bytes", "sprk_catalog_build", "sprk_catalog_similar",
+    "sprk_als_workspace_bytes", "sprk_als_fit", "sprk_als_predict", "sprk_als_topk_workspace_bytes", "sprk_als_topk",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -282,8 +283,17 @@ def load_library():
                                            vp, vp, vp, vp, C.c_int64, vp, vp, sz, vp]                       # the outputs, list_capacity, error word, workspace, stream
         lib.sprk_catalog_similar.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, C.c_int64,           # queries, movie table, n_genres, the lists
                                              i32, i32, i32, i32, i32, vp, vp, i32, vp, vp]                  # mode, top_n, extra_n, score_kind, size, the outputs, stream
+        lib.sprk_als_workspace_bytes.argtypes = [C.c_int64, i32, i32, i32]
+        lib.sprk_als_workspace_bytes.restype = sz
+        lib.sprk_als_fit.argtypes = [vp, vp, vp, C.c_int64, i32, i32, i32, C.c_double, i32,                  # ratings, sizes, rank, reg, iters
+                                     vp, i32, vp, i32, vp, i32, vp, vp, vp, vp,                              # init_user, the factor tables, has, counts
+                                     vp, vp, sz, vp]                                                         # error word, workspace, stream
+        lib.sprk_als_predict.argtypes = [vp, vp, C.c_int64, vp, i32, vp, vp, i32, vp, i32, i32, i32, vp, vp]
+        lib.sprk_als_topk_workspace_bytes.argtypes = [i32, i32, i32]
+        lib.sprk_als_topk_workspace_bytes.restype = sz
+        lib.sprk_als_topk.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

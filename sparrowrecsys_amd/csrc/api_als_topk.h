@@ -1,0 +1,91 @@
+// api_als_topk.h -- C ABI: sprk_als_topk / sprk_als_topk_workspace_bytes, the K best rows of a factor table for every query factor row
+// (k_als_topk.h).  Part of sparrow_hip.hip, after api_emb_topk.h, whose chunk length (SPRK_EMB_TOPK_CHUNK), merge plan and merge kernel it uses.
+namespace {
+inline bool at_sizes_ok(int32_t n_rows, int32_t n_queries, int32_t K) { return n_rows >= 0 && n_queries >= 0 && K >= 1 && K <= 1024; }
+// the workspace: the merge tree's runs (api_emb_topk.h's layout), then the last level's [n_queries][K] doubles and rows; 0 when the table is one chunk
+size_t at_tree_bytes(const EtPlan& p, int32_t n_queries) { return ((size_t)n_queries * (p.pairs[0] + p.pairs[1]) * 12 + 15) / 16 * 16; }
+size_t at_workspace_bytes(const EtPlan& p, int32_t n_queries, int32_t K) {
+    if (p.n_levels == 1) return 0;
+    return at_tree_bytes(p, n_queries) + (size_t)n_queries * K * 12;
+}
+}  // namespace
+
+extern "C" {
+
+size_t sprk_als_topk_workspace_bytes(int32_t n_rows, int32_t n_queries, int32_t K) {
+    if (!at_sizes_ok(n_rows, n_queries, K) || n_rows == 0) return 0;
+    return at_workspace_bytes(et_plan(n_rows, K, et_chunk_len()), n_queries, K);
+}
+
+int sprk_als_topk(const float* table, const uint8_t* table_has, int32_t n_rows, int32_t rank, int32_t table_stride,
+                  const float* query, const uint8_t* query_has, int32_t n_queries, int32_t query_stride,
+                  int32_t K, float* scores, int32_t* rows, void* workspace, size_t workspace_bytes, void* stream) {
+    RoctxRange roctx_range_("sprk_als_topk");
+    // every check before any device call
+    if (n_rows < 0 || n_queries < 0 || rank < 1 || rank > 16 || table_stride < rank || query_stride < rank)
+        return fail(SPRK_EINVAL, "als_topk: bad sizes (need n_rows >= 0, n_queries >= 0, 1 <= rank <= 16, strides >= rank)");
+    if (K < 1 || K > 1024) return fail(SPRK_EINVAL, "als_topk: K = %d outside [1, 1024]", K);
+    if (n_rows > 0 && (!table || !table_has)) return fail(SPRK_EINVAL, "als_topk: NULL table");
+    if (n_queries > 0 && (!query || !query_has || !scores || !rows)) return fail(SPRK_EINVAL, "als_topk: NULL queries / scores / rows");
+    if (((uintptr_t)table & 3) || ((uintptr_t)query & 3) || ((uintptr_t)scores & 3) || ((uintptr_t)rows & 3)) return fail(SPRK_EINVAL, "als_topk: misaligned column");
+    const int CH = et_chunk_len();
+    const EtPlan p = n_rows > 0 ? et_plan(n_rows, K, CH) : EtPlan();
+    const size_t need = n_rows > 0 ? at_workspace_bytes(p, n_queries, K) : 0;
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(SPRK_EINVAL, "als_topk: needs a workspace of %zu bytes (sprk_als_topk_workspace_bytes), got %zu", need, workspace ? workspace_bytes : (size_t)0);
+    if (need && ((uintptr_t)workspace & 15)) return fail(SPRK_EINVAL, "als_topk: the workspace must start on a 16-byte boundary");
+    if (n_queries == 0) return SPRK_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const long long n_out = (long long)n_queries * K;
+    const unsigned fg = (unsigned)((n_out + ET_THREADS - 1) / ET_THREADS < 2048 ? (n_out + ET_THREADS - 1) / ET_THREADS : 2048);
+    if (n_rows == 0) {                                                      // no candidate: every place is -1 / NaN
+        hipLaunchKernelGGL(k_als_topk_finish, dim3(fg), dim3(ET_THREADS), 0, st, (const int*)nullptr, n_out, (int)K, 0, table, (int)rank, (int)table_stride, query,
+                           (int)query_stride, scores, rows);
+        HIP_TRY(hipGetLastError());
+        return SPRK_OK;
+    }
+    // workspace: keys of the even levels | keys of the odd levels | rows of the even levels | rows of the odd levels | last level: doubles | rows
+    unsigned long long* keys[2];
+    int* runs[2];
+    keys[0] = (unsigned long long*)workspace;
+    keys[1] = keys[0] + (size_t)n_queries * p.pairs[0];
+    runs[0] = (int*)(keys[1] + (size_t)n_queries * p.pairs[1]);
+    runs[1] = runs[0] + (size_t)n_queries * p.pairs[0];
+    double* last_score = (double*)((unsigned char*)workspace + at_tree_bytes(p, n_queries));
+    int* last_row = (int*)(last_score + (size_t)n_out);
+    const bool one = p.n_levels == 1;
+    {
+        const EtLevel& l0 = p.lv[0];
+        const int P = et_pow2(n_rows < CH ? n_rows : CH);
+        const size_t lds = (size_t)P * 12 + (size_t)rank * 4;
+        for (int u0 = 0; u0 < n_queries; u0 += 65535) {
+            const int nq = n_queries - u0 < 65535 ? n_queries - u0 : 65535;
+            hipLaunchKernelGGL(k_als_topk_chunk, dim3((unsigned)l0.n_runs, (unsigned)nq), dim3(ET_THREADS), lds, st, table, table_has, (int)n_rows, (int)rank, (int)table_stride,
+                               query, query_has, (int)query_stride, u0, CH, P, (int)K, one ? 0 : l0.slot, keys[0], runs[0], scores, rows);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    if (one) return SPRK_OK;
+    for (int l = 0; l + 1 < p.n_levels; ++l) {
+        const EtLevel& in = p.lv[l];
+        const EtLevel& out = p.lv[l + 1];
+        const bool last = l + 2 == p.n_levels;
+        const int F = ET_CH / in.slot;
+        const int P = et_pow2((long long)(in.n_runs < F ? in.n_runs : F) * in.slot);
+        const size_t lds = (size_t)P * 12;
+        for (int u0 = 0; u0 < n_queries; u0 += 65535) {
+            const int nq = n_queries - u0 < 65535 ? n_queries - u0 : 65535;
+            hipLaunchKernelGGL(k_emb_topk_merge, dim3((unsigned)out.n_runs, (unsigned)nq), dim3(ET_THREADS), lds, st, (const unsigned long long*)keys[l & 1],
+                               (const int*)runs[l & 1], in.n_runs, in.slot, in.span, F, P, (int)n_rows, (int)K, 1, u0, out.slot,
+                               last ? (unsigned long long*)nullptr : keys[(l + 1) & 1], last ? (int*)nullptr : runs[(l + 1) & 1], table, (int)rank, (int)table_stride,
+                               query, (int)query_stride, last_score, last_row);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_als_topk_finish, dim3(fg), dim3(ET_THREADS), 0, st, (const int*)last_row, n_out, (int)K, (int)(n_rows < K ? n_rows : K), table, (int)rank,
+                       (int)table_stride, query, (int)query_stride, scores, rows);
+    HIP_TRY(hipGetLastError());
+    return SPRK_OK;
+}
+
+}  // extern "C"

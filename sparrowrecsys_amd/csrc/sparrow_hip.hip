@@ -36,6 +36,7 @@
 #include "api_forward.h"             // C ABI: sprk_din_pool, sprk_forward, sprk_forward_many, sprk_describe, sprk_check_ids, sprk_destroy, operators, emb ranker
 #include "api_ingest.h"              // C ABI: CSV ingest on the host (sprk_pack_csv[_mt]) and on the device (sprk_pack_csv_device), sprk_cross_hash
 #include "api_emb_topk.h"            // C ABI: sprk_emb_topk, sprk_emb_topk_workspace_bytes (exact top-K embedding recall, k_emb_topk.h)
+#include "api_als_topk.h"            // C ABI: sprk_als_topk, sprk_als_topk_workspace_bytes (ALS recommendations, k_als_topk.h)
 #include "api_pack_columns.h"       // C ABI: a dict of feature columns -> packed ids / dense on the host (sprk_pack_columns) and on the device (sprk_pack_columns_device)
 #include "api_feature_join.h"       // C ABI: sprk_join_features (pairs of ids -> packed sample rows from the feature store), sprk_rank_scores
 #include "api_comm.h"                // C ABI: the score all-gather over RCCL (sprk_comm_*) and as direct peer writes (sprk_peer_*)

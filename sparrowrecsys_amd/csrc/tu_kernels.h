@@ -35,6 +35,7 @@
 #include "k_mlp_rows.h"
 #include "k_emb_rank.h"
 #include "k_emb_topk.h"           // exact top-K recall over the whole table (reuses er_key)
+#include "k_als_topk.h"           // ALS recommendations: the same selection over the float32 dot of two factor rows
 #include "k_dien_seq.h"
 #include "k_dien_mfma.h"
 #include "k_dien_fused.h"
