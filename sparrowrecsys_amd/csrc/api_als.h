@@ -1,6 +1,6 @@
 // api_als.h -- C ABI: sprk_als_fit / sprk_als_workspace_bytes (ratings -> ALS factors on the device) and sprk_als_predict (factors ->
-// scores), k_als.h.  Part of sparrow_feature_eng.hip, after api_catalog.h; it uses api_feature_eng.h's sort capacity, grids and
-// long-segment sort.  Every argument is checked before any device call; the calls enqueue their kernels on the caller's stream and
+// scores), k_als.h.  From host_segments.h: the carver and the workspace check, the grids, and for each of the two sides the counts-only
+// seg_scan and seg_sort.  Every argument is checked before any device call; the calls enqueue their kernels on the caller's stream and
 // return: no synchronisation, no memory of their own.
 namespace {
 // The workspace, carved in this order; every part starts on a 16-byte boundary.  [zeroed] parts are cleared by one memset per call.
@@ -11,9 +11,7 @@ struct AlsWorkspace {
     unsigned* cur_movie;           // [n_items]                                                         [zeroed]
     unsigned* words;               // [4]            ALS_W_*: long segments of either side, next row, stop   [zeroed]
     size_t zeroed_bytes;
-    unsigned* kept_off;            // [max(n_users, n_items) + 1]  k_fe_scan_*'s second scan, unused here
-    unsigned* tops;                // [2 * n_tiles]  (the larger side's)
-    long long* n_kept;             // [2]            k_fe_scan_add's total, unused here
+    unsigned* tops;                // [n_tiles]      (the larger side's)
     int* long_user;                // [n / 64 + 1]
     int* long_movie;               // [n / 64 + 1]
     int* val_user;                 // [n]            the rating's bits, in the user's segment
@@ -30,48 +28,27 @@ inline bool als_sizes_ok(int64_t n, int32_t n_users, int32_t n_items, int32_t ra
 }
 AlsWorkspace als_carve(void* base, int64_t n, int32_t n_users, int32_t n_items) {
     AlsWorkspace w;
-    size_t o = 0;
-    auto take = [&](size_t count, size_t elem) { const size_t at = o; o += (count * elem + 15) / 16 * 16; return (unsigned char*)base + at; };
-    const size_t nu = (size_t)n_users, ni = (size_t)n_items, nr = (size_t)n, nmax = nu > ni ? nu : ni;
-    w.off_user = (unsigned*)take(nu + 1, 4);
-    w.off_movie = (unsigned*)take(ni + 1, 4);
-    w.cur_user = (unsigned*)take(nu, 4);
-    w.cur_movie = (unsigned*)take(ni, 4);
-    w.words = (unsigned*)take(4, 4);
-    w.zeroed_bytes = o;
-    w.tiles_user = (int)((nu + 1 + FE_SCAN_TILE - 1) / FE_SCAN_TILE);
-    w.tiles_movie = (int)((ni + 1 + FE_SCAN_TILE - 1) / FE_SCAN_TILE);
-    w.kept_off = (unsigned*)take(nmax + 1, 4);
-    w.tops = (unsigned*)take(2 * (size_t)(w.tiles_user > w.tiles_movie ? w.tiles_user : w.tiles_movie), 4);
-    w.n_kept = (long long*)take(2, 8);
-    w.long_user = (int*)take(nr / 64 + 1, 4);
-    w.long_movie = (int*)take(nr / 64 + 1, 4);
-    w.val_user = (int*)take(nr, 4);
-    w.val_movie = (int*)take(nr, 4);
-    w.tmp_val = (int*)take(nr, 4);
-    w.key_user = (long long*)take(nr, 8);
-    w.key_movie = (long long*)take(nr, 8);
-    w.tmp_key = (long long*)take(nr, 8);
-    w.bytes = o;
+    Carver c{base};
+    const size_t nu = (size_t)n_users, ni = (size_t)n_items, nr = (size_t)n;
+    w.off_user = c.take<unsigned>(nu + 1);
+    w.off_movie = c.take<unsigned>(ni + 1);
+    w.cur_user = c.take<unsigned>(nu);
+    w.cur_movie = c.take<unsigned>(ni);
+    w.words = c.take<unsigned>(4);
+    w.zeroed_bytes = c.at;
+    w.tiles_user = seg_scan_tiles(nu);
+    w.tiles_movie = seg_scan_tiles(ni);
+    w.tops = c.take<unsigned>((size_t)(w.tiles_user > w.tiles_movie ? w.tiles_user : w.tiles_movie));
+    w.long_user = c.take<int>(nr / 64 + 1);
+    w.long_movie = c.take<int>(nr / 64 + 1);
+    w.val_user = c.take<int>(nr);
+    w.val_movie = c.take<int>(nr);
+    w.tmp_val = c.take<int>(nr);
+    w.key_user = c.take<long long>(nr);
+    w.key_movie = c.take<long long>(nr);
+    w.tmp_key = c.take<long long>(nr);
+    w.bytes = c.at;
     return w;
-}
-
-// offsets of one side from its counts, in place
-int als_scan(unsigned* off, long long count, int n_tiles, const AlsWorkspace& w, hipStream_t st) {
-    hipLaunchKernelGGL(k_fe_scan_tiles, dim3((unsigned)n_tiles), dim3(FE_THREADS), 0, st, off, w.kept_off, count, w.tops, n_tiles);
-    hipLaunchKernelGGL(k_fe_scan_tops, dim3(1), dim3(FE_THREADS), 0, st, w.tops, n_tiles);
-    hipLaunchKernelGGL(k_fe_scan_add, dim3(fe_grid(count)), dim3(FE_THREADS), 0, st, off, w.kept_off, count, (const unsigned*)w.tops, n_tiles, w.n_kept);
-    HIP_TRY(hipGetLastError());
-    return SPRK_OK;
-}
-
-// every segment of one side by its key: in LDS up to `cap` keys, chunks and merge passes beyond
-int als_sort(int cap, long long n, int n_rows, const unsigned* off, long long* key, int* val, const AlsWorkspace& w, int* long_list, unsigned* n_long, hipStream_t st) {
-    if (n_rows == 0) return SPRK_OK;
-    const unsigned g = (unsigned)n_rows < 65536u * 16u ? (unsigned)n_rows : 65536u * 16u;
-    hipLaunchKernelGGL(k_fe_sort_short, dim3(g), dim3(FE_THREADS), (size_t)cap * 12, st, n_rows, cap, off, key, val, long_list, n_long);
-    HIP_TRY(hipGetLastError());
-    return fe_sort_long_segments(cap, n, off, key, val, w.tmp_key, w.tmp_val, long_list, n_long, st);
 }
 
 int als_half_sweep(int n_dst, int rank, double reg, const unsigned* off, const long long* key, const int* val, const float* src, int src_stride, float* dst,
@@ -124,9 +101,7 @@ int sprk_als_fit(const int32_t* user_id, const int32_t* movie_id, const float* r
         ((uintptr_t)item_factors & 3) || ((uintptr_t)user_count & 3) || ((uintptr_t)item_count & 3))
         return fail(SPRK_EINVAL, "als_fit: misaligned column");
     const AlsWorkspace w = als_carve(workspace, n_ratings, n_users, n_items);
-    if (!workspace || workspace_bytes < w.bytes)
-        return fail(SPRK_EINVAL, "als_fit: needs a workspace of %zu bytes (sprk_als_workspace_bytes), got %zu", w.bytes, workspace ? workspace_bytes : (size_t)0);
-    if ((uintptr_t)workspace & 15) return fail(SPRK_EINVAL, "als_fit: the workspace must start on a 16-byte boundary");
+    SPRK_TRY(check_workspace("als_fit", "sprk_als_workspace_bytes", workspace, workspace_bytes, w.bytes));
     const int cap = fe_sort_cap();
     hipStream_t st = (hipStream_t)stream;
     const long long n = n_ratings;
@@ -137,14 +112,14 @@ int sprk_als_fit(const int32_t* user_id, const int32_t* movie_id, const float* r
         hipLaunchKernelGGL(k_als_count, dim3(fe_grid_capped(n)), dim3(ALS_THREADS), 0, st, n, user_id, movie_id, rating, (int)n_users, (int)n_items, w.off_user, w.off_movie, err);
         HIP_TRY(hipGetLastError());
     }
-    SPRK_TRY(als_scan(w.off_user, (long long)n_users + 1, w.tiles_user, w, st));
-    SPRK_TRY(als_scan(w.off_movie, (long long)n_items + 1, w.tiles_movie, w, st));
+    SPRK_TRY(seg_scan(w.off_user, (long long)n_users + 1, w.tops, w.tiles_user, FeScanKept<false>{}, st));
+    SPRK_TRY(seg_scan(w.off_movie, (long long)n_items + 1, w.tops, w.tiles_movie, FeScanKept<false>{}, st));
     if (n > 0) {
         hipLaunchKernelGGL(k_als_scatter, dim3(fe_grid_capped(n)), dim3(ALS_THREADS), 0, st, n, user_id, movie_id, rating, (int)n_users, (int)n_items,
                            (const unsigned*)w.off_user, (const unsigned*)w.off_movie, w.cur_user, w.cur_movie, w.key_user, w.val_user, w.key_movie, w.val_movie);
         HIP_TRY(hipGetLastError());
-        SPRK_TRY(als_sort(cap, n, n_users, w.off_user, w.key_user, w.val_user, w, w.long_user, w.words + ALS_W_LONG_USER, st));
-        SPRK_TRY(als_sort(cap, n, n_items, w.off_movie, w.key_movie, w.val_movie, w, w.long_movie, w.words + ALS_W_LONG_MOVIE, st));
+        SPRK_TRY(seg_sort(cap, n, n_users, w.off_user, w.key_user, w.val_user, w.tmp_key, w.tmp_val, w.long_user, w.words + ALS_W_LONG_USER, nullptr, st));
+        SPRK_TRY(seg_sort(cap, n, n_items, w.off_movie, w.key_movie, w.val_movie, w.tmp_key, w.tmp_val, w.long_movie, w.words + ALS_W_LONG_MOVIE, nullptr, st));
     }
     if (n_users > 0 || n_items > 0) {
         hipLaunchKernelGGL(k_als_init, dim3(fe_grid_capped(n_users > n_items ? n_users : n_items)), dim3(ALS_THREADS), 0, st, (int)n_users, (int)n_items, (int)rank,

@@ -1,5 +1,5 @@
 // api_als_topk.h -- C ABI: sprk_als_topk / sprk_als_topk_workspace_bytes, the K best rows of a factor table for every query factor row
-// (k_als_topk.h).  Part of sparrow_hip.hip, after api_emb_topk.h, whose chunk length (SPRK_EMB_TOPK_CHUNK), merge plan and merge kernel it uses.
+// (k_als_topk.h).  Uses api_emb_topk.h's chunk length (SPRK_EMB_TOPK_CHUNK), merge plan, workspace split and merge tree driver (et_plan, et_split, et_merge_levels).
 namespace {
 inline bool at_sizes_ok(int32_t n_rows, int32_t n_queries, int32_t K) { return n_rows >= 0 && n_queries >= 0 && K >= 1 && K <= 1024; }
 // the workspace: the merge tree's runs (api_emb_topk.h's layout), then the last level's [n_queries][K] doubles and rows; 0 when the table is one chunk
@@ -44,13 +44,8 @@ int sprk_als_topk(const float* table, const uint8_t* table_has, int32_t n_rows, 
         HIP_TRY(hipGetLastError());
         return SPRK_OK;
     }
-    // workspace: keys of the even levels | keys of the odd levels | rows of the even levels | rows of the odd levels | last level: doubles | rows
-    unsigned long long* keys[2];
-    int* runs[2];
-    keys[0] = (unsigned long long*)workspace;
-    keys[1] = keys[0] + (size_t)n_queries * p.pairs[0];
-    runs[0] = (int*)(keys[1] + (size_t)n_queries * p.pairs[1]);
-    runs[1] = runs[0] + (size_t)n_queries * p.pairs[0];
+    // workspace: the tree's places (et_split) | last level: doubles | rows
+    const EtRuns r = et_split(workspace, p, n_queries);
     double* last_score = (double*)((unsigned char*)workspace + at_tree_bytes(p, n_queries));
     int* last_row = (int*)(last_score + (size_t)n_out);
     const bool one = p.n_levels == 1;
@@ -61,27 +56,12 @@ int sprk_als_topk(const float* table, const uint8_t* table_has, int32_t n_rows, 
         for (int u0 = 0; u0 < n_queries; u0 += 65535) {
             const int nq = n_queries - u0 < 65535 ? n_queries - u0 : 65535;
             hipLaunchKernelGGL(k_als_topk_chunk, dim3((unsigned)l0.n_runs, (unsigned)nq), dim3(ET_THREADS), lds, st, table, table_has, (int)n_rows, (int)rank, (int)table_stride,
-                               query, query_has, (int)query_stride, u0, CH, P, (int)K, one ? 0 : l0.slot, keys[0], runs[0], scores, rows);
+                               query, query_has, (int)query_stride, u0, CH, P, (int)K, one ? 0 : l0.slot, r.keys[0], r.rows[0], scores, rows);
         }
         HIP_TRY(hipGetLastError());
     }
     if (one) return SPRK_OK;
-    for (int l = 0; l + 1 < p.n_levels; ++l) {
-        const EtLevel& in = p.lv[l];
-        const EtLevel& out = p.lv[l + 1];
-        const bool last = l + 2 == p.n_levels;
-        const int F = ET_CH / in.slot;
-        const int P = et_pow2((long long)(in.n_runs < F ? in.n_runs : F) * in.slot);
-        const size_t lds = (size_t)P * 12;
-        for (int u0 = 0; u0 < n_queries; u0 += 65535) {
-            const int nq = n_queries - u0 < 65535 ? n_queries - u0 : 65535;
-            hipLaunchKernelGGL(k_emb_topk_merge, dim3((unsigned)out.n_runs, (unsigned)nq), dim3(ET_THREADS), lds, st, (const unsigned long long*)keys[l & 1],
-                               (const int*)runs[l & 1], in.n_runs, in.slot, in.span, F, P, (int)n_rows, (int)K, 1, u0, out.slot,
-                               last ? (unsigned long long*)nullptr : keys[(l + 1) & 1], last ? (int*)nullptr : runs[(l + 1) & 1], table, (int)rank, (int)table_stride,
-                               query, (int)query_stride, last_score, last_row);
-        }
-        HIP_TRY(hipGetLastError());
-    }
+    SPRK_TRY(et_merge_levels(p, r, n_queries, n_rows, K, 1, table, rank, table_stride, query, query_stride, last_score, last_row, st));
     hipLaunchKernelGGL(k_als_topk_finish, dim3(fg), dim3(ET_THREADS), 0, st, (const int*)last_row, n_out, (int)K, (int)(n_rows < K ? n_rows : K), table, (int)rank,
                        (int)table_stride, query, (int)query_stride, scores, rows);
     HIP_TRY(hipGetLastError());

@@ -1,6 +1,7 @@
 // api_catalog.h -- C ABI: sprk_catalog_build / sprk_catalog_build_workspace_bytes (ratings + the movie table -> average ratings and the
 // sorted lists) and sprk_catalog_similar (candidates and the default similarity ranker for Q queries), on the device (k_catalog.h).
-// Part of sparrow_feature_eng.hip, after api_user_emb.h: the sort capacity, the grids and the long-segment sort are api_feature_eng.h's.
+// From host_segments.h: the carver and the workspace check, the grids, the counts-only seg_scan, and seg_sort twice: the ratings per movie
+// behind the `ungrouped` word, then the 2 (G + 1) lists.
 // Every argument is checked before any device call; the calls enqueue their kernels on the caller's stream and return: no
 // synchronisation, no memory of their own.
 namespace {
@@ -17,9 +18,7 @@ struct CatWorkspace {
     int* inv_hash;                 // [n_movies]      hash position -> movie                                      [zeroed]
     size_t zeroed_bytes;
     unsigned* first;               // [n_movies]      the first row of the movie's (only) run
-    unsigned* kept_off;            // [n_movies + 1]  k_fe_scan_*'s second scan, unused here
-    unsigned* tops;                // [2 * n_tiles]
-    long long* n_kept;             // [2]             k_fe_scan_add's total, unused here
+    unsigned* tops;                // [n_tiles]
     int* long_list;                // [n / 64 + 1]
     int* seg_rating;               // [n]             float32 bits
     int* tmp_rating;               // [n]
@@ -39,36 +38,33 @@ inline bool cat_sizes_ok(int64_t n, int32_t n_movies, int64_t capacity) {
 }
 CatWorkspace cat_carve(void* base, int64_t n, int32_t n_movies, int64_t capacity) {
     CatWorkspace w;
-    size_t o = 0;
-    auto take = [&](size_t count, size_t elem) { const size_t at = o; o += (count * elem + 15) / 16 * 16; return (unsigned char*)base + at; };
+    Carver c{base};
     const size_t nm = (size_t)n_movies, nr = (size_t)n, nl = (size_t)capacity, L = 2 * (CAT_MAX_GENRES + 1);
-    w.seg_off = (unsigned*)take(nm + 1, 4);
-    w.runs = (unsigned*)take(nm, 4);
-    w.cursor = (unsigned*)take(nm, 4);
-    w.words = (unsigned*)take(4, 4);
-    w.lwords = (unsigned*)take(4, 4);
-    w.lcnt = (unsigned*)take(CAT_MAX_GENRES + 1, 4);
-    w.lcursor = (unsigned*)take(L, 4);
-    w.inv_file = (int*)take(nm, 4);
-    w.inv_hash = (int*)take(nm, 4);
-    w.zeroed_bytes = o;
-    w.n_tiles = (int)((nm + 1 + FE_SCAN_TILE - 1) / FE_SCAN_TILE);
-    w.first = (unsigned*)take(nm, 4);
-    w.kept_off = (unsigned*)take(nm + 1, 4);
-    w.tops = (unsigned*)take(2 * (size_t)w.n_tiles, 4);
-    w.n_kept = (long long*)take(2, 8);
-    w.long_list = (int*)take(nr / 64 + 1, 4);
-    w.seg_rating = (int*)take(nr, 4);
-    w.tmp_rating = (int*)take(nr, 4);
-    w.seg_key = (long long*)take(nr, 8);
-    w.tmp_key = (long long*)take(nr, 8);
-    w.lseg_off = (unsigned*)take(L + 1, 4);
-    w.llong_list = (int*)take(L, 4);
-    w.lrow = (int*)take(nl, 4);
-    w.ltmp_row = (int*)take(nl, 4);
-    w.lkey = (long long*)take(nl, 8);
-    w.ltmp_key = (long long*)take(nl, 8);
-    w.bytes = o;
+    w.seg_off = c.take<unsigned>(nm + 1);
+    w.runs = c.take<unsigned>(nm);
+    w.cursor = c.take<unsigned>(nm);
+    w.words = c.take<unsigned>(4);
+    w.lwords = c.take<unsigned>(4);
+    w.lcnt = c.take<unsigned>(CAT_MAX_GENRES + 1);
+    w.lcursor = c.take<unsigned>(L);
+    w.inv_file = c.take<int>(nm);
+    w.inv_hash = c.take<int>(nm);
+    w.zeroed_bytes = c.at;
+    w.n_tiles = seg_scan_tiles(nm);
+    w.first = c.take<unsigned>(nm);
+    w.tops = c.take<unsigned>((size_t)w.n_tiles);
+    w.long_list = c.take<int>(nr / 64 + 1);
+    w.seg_rating = c.take<int>(nr);
+    w.tmp_rating = c.take<int>(nr);
+    w.seg_key = c.take<long long>(nr);
+    w.tmp_key = c.take<long long>(nr);
+    w.lseg_off = c.take<unsigned>(L + 1);
+    w.llong_list = c.take<int>(L);
+    w.lrow = c.take<int>(nl);
+    w.ltmp_row = c.take<int>(nl);
+    w.lkey = c.take<long long>(nl);
+    w.ltmp_key = c.take<long long>(nl);
+    w.bytes = c.at;
     return w;
 }
 }  // namespace
@@ -100,14 +96,11 @@ int sprk_catalog_build(const int32_t* movie_id, const float* rating, int64_t n_r
         ((uintptr_t)movie_hash_pos & 3) || ((uintptr_t)avg_rating & 7) || ((uintptr_t)rating_count & 3) || ((uintptr_t)list_offsets & 3) || ((uintptr_t)list_movies & 3))
         return fail(SPRK_EINVAL, "catalog_build: misaligned column");
     const CatWorkspace w = cat_carve(workspace, n_ratings, n_movies, list_capacity);
-    if (!workspace || workspace_bytes < w.bytes)
-        return fail(SPRK_EINVAL, "catalog_build: needs a workspace of %zu bytes (sprk_catalog_build_workspace_bytes), got %zu", w.bytes, workspace ? workspace_bytes : (size_t)0);
-    if ((uintptr_t)workspace & 15) return fail(SPRK_EINVAL, "catalog_build: the workspace must start on a 16-byte boundary");
+    SPRK_TRY(check_workspace("catalog_build", "sprk_catalog_build_workspace_bytes", workspace, workspace_bytes, w.bytes));
     const int cap = fe_sort_cap();
     hipStream_t st = (hipStream_t)stream;
-    const long long n = n_ratings, count = (long long)n_movies + 1;
+    const long long n = n_ratings;
     const int G = n_genres, L = 2 * (G + 1);
-    const size_t sort_lds = (size_t)cap * 12;
 
     HIP_TRY(hipMemsetAsync(workspace, 0, w.zeroed_bytes, st));
     if (n > 0) {
@@ -116,18 +109,12 @@ int sprk_catalog_build(const int32_t* movie_id, const float* rating, int64_t n_r
         HIP_TRY(hipGetLastError());
     }
     if (n_movies > 0) {
-        hipLaunchKernelGGL(k_fe_scan_tiles, dim3((unsigned)w.n_tiles), dim3(FE_THREADS), 0, st, w.seg_off, w.kept_off, count, w.tops, w.n_tiles);
-        hipLaunchKernelGGL(k_fe_scan_tops, dim3(1), dim3(FE_THREADS), 0, st, w.tops, w.n_tiles);
-        hipLaunchKernelGGL(k_fe_scan_add, dim3(fe_grid(count)), dim3(FE_THREADS), 0, st, w.seg_off, w.kept_off, count, (const unsigned*)w.tops, w.n_tiles, w.n_kept);
-        HIP_TRY(hipGetLastError());
+        SPRK_TRY(seg_scan(w.seg_off, (long long)n_movies + 1, w.tops, w.n_tiles, FeScanKept<false>{}, st));
         if (n > 0) {                                                        // each of these does nothing unless k_cat_count raised `ungrouped`
             hipLaunchKernelGGL(k_cat_scatter, dim3(fe_grid_capped(n)), dim3(CAT_THREADS), 0, st, n, movie_id, rating, (int)n_movies, movie_has, (const unsigned*)w.seg_off, w.cursor,
                                w.seg_key, w.seg_rating, (const unsigned*)w.words);
             HIP_TRY(hipGetLastError());
-            const unsigned ug = (unsigned)n_movies < 65536u * 16u ? (unsigned)n_movies : 65536u * 16u;
-            hipLaunchKernelGGL(k_ue_sort_short, dim3(ug), dim3(FE_THREADS), sort_lds, st, (int)n_movies, cap, (const unsigned*)w.seg_off, w.seg_key, w.seg_rating, w.long_list, w.words);
-            HIP_TRY(hipGetLastError());
-            SPRK_TRY(fe_sort_long_segments(cap, n, w.seg_off, w.seg_key, w.seg_rating, w.tmp_key, w.tmp_rating, w.long_list, w.words + UE_W_LONG, st));
+            SPRK_TRY(seg_sort(cap, n, n_movies, w.seg_off, w.seg_key, w.seg_rating, w.tmp_key, w.tmp_rating, w.long_list, w.words + UE_W_LONG, w.words + UE_W_UNGROUPED, st));
         }
         const unsigned mg = fe_grid_capped(n_movies);
         hipLaunchKernelGGL(k_cat_avg_short, dim3(mg), dim3(CAT_THREADS), 0, st, (int)n_movies, (const unsigned*)w.seg_off, (const unsigned*)w.first, (const int*)w.seg_rating, rating,
@@ -143,9 +130,8 @@ int sprk_catalog_build(const int32_t* movie_id, const float* rating, int64_t n_r
     if (n_movies > 0 && list_capacity > 0) {
         hipLaunchKernelGGL(k_cat_list_scatter, dim3(fe_grid_capped(n_movies)), dim3(CAT_THREADS), 0, st, (int)n_movies, (const unsigned*)movie_genre_mask, movie_has, movie_year,
                            movie_file_pos, movie_hash_pos, (const double*)avg_rating, G, (const unsigned*)w.lseg_off, w.lcursor, w.lkey, w.lrow, w.inv_file, w.inv_hash);
-        hipLaunchKernelGGL(k_fe_sort_short, dim3((unsigned)L), dim3(FE_THREADS), sort_lds, st, L, cap, (const unsigned*)w.lseg_off, w.lkey, w.lrow, w.llong_list, w.lwords);
         HIP_TRY(hipGetLastError());
-        SPRK_TRY(fe_sort_long_segments(cap, (long long)list_capacity, w.lseg_off, w.lkey, w.lrow, w.ltmp_key, w.ltmp_row, w.llong_list, w.lwords, st));
+        SPRK_TRY(seg_sort(cap, (long long)list_capacity, L, w.lseg_off, w.lkey, w.lrow, w.ltmp_key, w.ltmp_row, w.llong_list, w.lwords, nullptr, st));
     }
     if (list_capacity > 0) {
         const unsigned wg = fe_grid_capped(list_capacity) < 256u ? fe_grid_capped(list_capacity) : 256u;

@@ -38,6 +38,40 @@ EtPlan et_plan(int n_items, int K, int CH) {
 }
 inline int et_pow2(long long n) { int p = 2; while (p < n) p <<= 1; return p; }
 inline bool et_sizes_ok(int32_t n_items, int32_t n_queries, int32_t K) { return n_queries >= 0 && K >= 1 && K <= 1024 && K <= n_items; }
+
+// the tree's places in a workspace: keys of the even levels | keys of the odd levels | rows of the even levels | rows of the odd levels
+struct EtRuns { unsigned long long* keys[2]; int* rows[2]; };
+EtRuns et_split(void* workspace, const EtPlan& p, int n_queries) {
+    EtRuns r;
+    r.keys[0] = (unsigned long long*)workspace;
+    r.keys[1] = r.keys[0] + (size_t)n_queries * p.pairs[0];
+    r.rows[0] = (int*)(r.keys[1] + (size_t)n_queries * p.pairs[1]);
+    r.rows[1] = r.rows[0] + (size_t)n_queries * p.pairs[0];
+    return r;
+}
+
+// levels 0 -> 1 -> ... -> last of every query's tree over level 0's runs in r; the last level scores its rows again (table, query) and
+// writes last_score / last_row.  Nothing for a tree of one level.
+int et_merge_levels(const EtPlan& p, const EtRuns& r, int n_queries, int n_rows, int K, int largest, const float* table, int D, int table_stride, const float* query,
+                    int query_stride, double* last_score, int* last_row, hipStream_t st) {
+    for (int l = 0; l + 1 < p.n_levels; ++l) {
+        const EtLevel& in = p.lv[l];
+        const EtLevel& out = p.lv[l + 1];
+        const bool last = l + 2 == p.n_levels;
+        const int F = ET_CH / in.slot;
+        const int P = et_pow2((long long)(in.n_runs < F ? in.n_runs : F) * in.slot);
+        const size_t lds = (size_t)P * 12;
+        for (int u0 = 0; u0 < n_queries; u0 += 65535) {
+            const int nq = n_queries - u0 < 65535 ? n_queries - u0 : 65535;
+            hipLaunchKernelGGL(k_emb_topk_merge, dim3((unsigned)out.n_runs, (unsigned)nq), dim3(ET_THREADS), lds, st, (const unsigned long long*)r.keys[l & 1],
+                               (const int*)r.rows[l & 1], in.n_runs, in.slot, in.span, F, P, n_rows, K, largest, u0, out.slot,
+                               last ? (unsigned long long*)nullptr : r.keys[(l + 1) & 1], last ? (int*)nullptr : r.rows[(l + 1) & 1], table, D, table_stride,
+                               query, query_stride, last_score, last_row);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return SPRK_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -66,13 +100,7 @@ int sprk_emb_topk(const float* item_emb, const uint8_t* item_has, int32_t n_item
     if (need && ((uintptr_t)workspace & 7)) return fail(SPRK_EINVAL, "emb_topk: the workspace must start on an 8-byte boundary");
     if (n_queries == 0) return SPRK_OK;
     hipStream_t st = (hipStream_t)stream;
-    // workspace: keys of the even levels | keys of the odd levels | rows of the even levels | rows of the odd levels
-    unsigned long long* keys[2];
-    int* rows[2];
-    keys[0] = (unsigned long long*)workspace;
-    keys[1] = keys[0] + (size_t)n_queries * p.pairs[0];
-    rows[0] = (int*)(keys[1] + (size_t)n_queries * p.pairs[1]);
-    rows[1] = rows[0] + (size_t)n_queries * p.pairs[0];
+    const EtRuns r = et_split(workspace, p, n_queries);
     const bool one = p.n_levels == 1;
     {
         const EtLevel& l0 = p.lv[0];
@@ -81,27 +109,11 @@ int sprk_emb_topk(const float* item_emb, const uint8_t* item_has, int32_t n_item
         for (int u0 = 0; u0 < n_queries; u0 += 65535) {
             const int nq = n_queries - u0 < 65535 ? n_queries - u0 : 65535;
             hipLaunchKernelGGL(k_emb_topk_chunk, dim3((unsigned)l0.n_runs, (unsigned)nq), dim3(ET_THREADS), lds, st, item_emb, item_has, n_items, D, item_stride,
-                               query_emb, query_has, query_stride, u0, CH, P, K, largest, one ? 0 : l0.slot, keys[0], rows[0], scores, items);
+                               query_emb, query_has, query_stride, u0, CH, P, K, largest, one ? 0 : l0.slot, r.keys[0], r.rows[0], scores, items);
         }
         HIP_TRY(hipGetLastError());
     }
-    for (int l = 0; l + 1 < p.n_levels; ++l) {
-        const EtLevel& in = p.lv[l];
-        const EtLevel& out = p.lv[l + 1];
-        const bool last = l + 2 == p.n_levels;
-        const int F = ET_CH / in.slot;
-        const int P = et_pow2((long long)(in.n_runs < F ? in.n_runs : F) * in.slot);
-        const size_t lds = (size_t)P * 12;
-        for (int u0 = 0; u0 < n_queries; u0 += 65535) {
-            const int nq = n_queries - u0 < 65535 ? n_queries - u0 : 65535;
-            hipLaunchKernelGGL(k_emb_topk_merge, dim3((unsigned)out.n_runs, (unsigned)nq), dim3(ET_THREADS), lds, st, (const unsigned long long*)keys[l & 1],
-                               (const int*)rows[l & 1], in.n_runs, in.slot, in.span, F, P, n_items, K, largest, u0, out.slot,
-                               last ? (unsigned long long*)nullptr : keys[(l + 1) & 1], last ? (int*)nullptr : rows[(l + 1) & 1], item_emb, D, item_stride,
-                               query_emb, query_stride, scores, items);
-        }
-        HIP_TRY(hipGetLastError());
-    }
-    return SPRK_OK;
+    return et_merge_levels(p, r, n_queries, n_items, K, largest, item_emb, D, item_stride, query_emb, query_stride, scores, items, st);
 }
 
 }  // extern "C"

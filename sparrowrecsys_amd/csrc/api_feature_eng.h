@@ -1,16 +1,8 @@
 // api_feature_eng.h -- C ABI: sprk_feature_eng / sprk_feature_eng_workspace_bytes, ratings -> samples and the feature store's rows on the
-// device (k_feature_eng.h).  Part of sparrow_feature_eng.hip.  Every argument is checked before any device call; the call enqueues its
-// kernels on the caller's stream and returns: no synchronisation, no memory of its own.
+// device (k_feature_eng.h).  From host_segments.h: the carver and the workspace check, the grids, seg_scan with its `kept` half, seg_sort.
+// Every argument is checked before any device call; the call enqueues its kernels on the caller's stream and returns: no
+// synchronisation, no memory of its own.
 namespace {
-// LDS sort capacity: FE_SORT_CAP, or SPRK_FE_SORT_CAP = a power of two in [64, FE_SORT_CAP], read at each call (tests: the long path at small sizes)
-int fe_sort_cap() {
-    if (const char* e = getenv("SPRK_FE_SORT_CAP")) {
-        const int v = atoi(e);
-        if (v >= 64 && v <= FE_SORT_CAP && (v & (v - 1)) == 0) return v;
-    }
-    return FE_SORT_CAP;
-}
-
 // The workspace, carved in this order; every part starts on a 16-byte boundary.  [zeroed] parts are cleared by one memset per call.
 struct FeWorkspace {
     unsigned* seg_off;             // [n_users + 1]  len, then its exclusive scan                       [zeroed]
@@ -36,58 +28,28 @@ struct FeWorkspace {
 inline bool fe_sizes_ok(int64_t n, int32_t n_users, int32_t n_movies) { return n >= 0 && n < 0x7fffffffll && n_users >= 0 && n_users < 0x7fffffff && n_movies >= 0; }
 FeWorkspace fe_carve(void* base, int64_t n, int32_t n_users, int32_t n_movies) {
     FeWorkspace w;
-    size_t o = 0;
-    auto take = [&](size_t count, size_t elem) { const size_t at = o; o += (count * elem + 15) / 16 * 16; return (unsigned char*)base + at; };
+    Carver c{base};
     const size_t nu = (size_t)n_users, nm = (size_t)n_movies, nr = (size_t)n;
-    w.seg_off = (unsigned*)take(nu + 1, 4);
-    w.cursor = (unsigned*)take(nu, 4);
-    w.mv_cnt = (unsigned*)take(nm, 4);
-    w.mv_flag = (unsigned*)take(nm, 4);
-    w.mv_S = (unsigned long long*)take(nm, 8);
-    w.mv_Q = (unsigned long long*)take(nm, 8);
-    w.n_long = (unsigned*)take(4, 4);
-    w.zeroed_bytes = o;
-    w.n_tiles = (int)((nu + 1 + FE_SCAN_TILE - 1) / FE_SCAN_TILE);
-    w.kept_off = (unsigned*)take(nu + 1, 4);
-    w.tops = (unsigned*)take(2 * (size_t)w.n_tiles, 4);
-    w.mv_dense = (float*)take(nm * 4, 4);
-    w.long_list = (int*)take(nr / 64 + 1, 4);
-    w.seg_row = (int*)take(nr, 4);
-    w.seg_user = (int*)take(nr, 4);
-    w.tmp_row = (int*)take(nr, 4);
-    w.seg_ts = (long long*)take(nr, 8);
-    w.tmp_ts = (long long*)take(nr, 8);
-    w.bytes = o;
+    w.seg_off = c.take<unsigned>(nu + 1);
+    w.cursor = c.take<unsigned>(nu);
+    w.mv_cnt = c.take<unsigned>(nm);
+    w.mv_flag = c.take<unsigned>(nm);
+    w.mv_S = c.take<unsigned long long>(nm);
+    w.mv_Q = c.take<unsigned long long>(nm);
+    w.n_long = c.take<unsigned>(4);
+    w.zeroed_bytes = c.at;
+    w.n_tiles = seg_scan_tiles(nu);
+    w.kept_off = c.take<unsigned>(nu + 1);
+    w.tops = c.take<unsigned>(2 * (size_t)w.n_tiles);
+    w.mv_dense = c.take<float>(nm * 4);
+    w.long_list = c.take<int>(nr / 64 + 1);
+    w.seg_row = c.take<int>(nr);
+    w.seg_user = c.take<int>(nr);
+    w.tmp_row = c.take<int>(nr);
+    w.seg_ts = c.take<long long>(nr);
+    w.tmp_ts = c.take<long long>(nr);
+    w.bytes = c.at;
     return w;
-}
-inline unsigned fe_grid(long long items) {
-    const long long g = (items + FE_THREADS - 1) / FE_THREADS;
-    return (unsigned)(g < 1 ? 1 : g);
-}
-inline unsigned fe_grid_capped(long long items) { const unsigned g = fe_grid(items); return g < (unsigned)FE_MAX_GRID ? g : (unsigned)FE_MAX_GRID; }
-
-// The segments k_fe_sort_short listed (longer than `cap`), sorted where they are: chunks of `cap` in LDS, then merge passes between
-// (seg_ts, seg_row) and (tmp_ts, tmp_row), and a copy back after an odd number of passes.  n = all keys: no segment is longer.
-int fe_sort_long_segments(int cap, long long n, const unsigned* seg_off, long long* seg_ts, int* seg_row, long long* tmp_ts, int* tmp_row, const int* long_list,
-                          const unsigned* n_long, hipStream_t st) {
-    if (n <= cap) return SPRK_OK;                                           // no segment can be longer than the LDS sort holds
-    const size_t sort_lds = (size_t)cap * 12;
-    const unsigned lg = fe_grid_capped(n);
-    const unsigned cg = (unsigned)((n + cap - 1) / cap) < (unsigned)FE_MAX_GRID ? (unsigned)((n + cap - 1) / cap) : (unsigned)FE_MAX_GRID;
-    hipLaunchKernelGGL(k_fe_sort_long_chunks, dim3(cg), dim3(FE_THREADS), sort_lds, st, cap, seg_off, seg_ts, seg_row, long_list, n_long);
-    HIP_TRY(hipGetLastError());
-    long long* ts[2] = {seg_ts, tmp_ts};
-    int* row[2] = {seg_row, tmp_row};
-    int at = 0;
-    for (long long width = cap; width < n; width *= 2, at ^= 1) {
-        hipLaunchKernelGGL(k_fe_merge_pass, dim3(lg), dim3(FE_THREADS), 0, st, width, seg_off, (const long long*)ts[at], (const int*)row[at], ts[at ^ 1], row[at ^ 1], long_list, n_long);
-        HIP_TRY(hipGetLastError());
-    }
-    if (at) {
-        hipLaunchKernelGGL(k_fe_long_copy, dim3(lg), dim3(FE_THREADS), 0, st, seg_off, (const long long*)tmp_ts, (const int*)tmp_row, seg_ts, seg_row, long_list, n_long);
-        HIP_TRY(hipGetLastError());
-    }
-    return SPRK_OK;
 }
 }  // namespace
 
@@ -127,13 +89,10 @@ int sprk_feature_eng(const int32_t* user_id, const int32_t* movie_id, const floa
         ((uintptr_t)movie_year & 3) || ((uintptr_t)movie_genre3 & 3) || ((uintptr_t)movie_genre_mask & 3) || ((uintptr_t)user_rows & 3) || ((uintptr_t)movie_rows & 3))
         return fail(SPRK_EINVAL, "feature_eng: misaligned column");
     const FeWorkspace w = fe_carve(workspace, n_ratings, n_users, n_movies);
-    if (!workspace || workspace_bytes < w.bytes)
-        return fail(SPRK_EINVAL, "feature_eng: needs a workspace of %zu bytes (sprk_feature_eng_workspace_bytes), got %zu", w.bytes, workspace ? workspace_bytes : (size_t)0);
-    if ((uintptr_t)workspace & 15) return fail(SPRK_EINVAL, "feature_eng: the workspace must start on a 16-byte boundary");
+    SPRK_TRY(check_workspace("feature_eng", "sprk_feature_eng_workspace_bytes", workspace, workspace_bytes, w.bytes));
     const int cap = fe_sort_cap();
     hipStream_t st = (hipStream_t)stream;
-    const long long n = n_ratings, count = (long long)n_users + 1;
-    const size_t sort_lds = (size_t)cap * 12;
+    const long long n = n_ratings;
 
     HIP_TRY(hipMemsetAsync(workspace, 0, w.zeroed_bytes, st));
     if (n > 0) {
@@ -141,18 +100,12 @@ int sprk_feature_eng(const int32_t* user_id, const int32_t* movie_id, const floa
                            (unsigned long long*)error_key);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_fe_scan_tiles, dim3((unsigned)w.n_tiles), dim3(FE_THREADS), 0, st, w.seg_off, w.kept_off, count, w.tops, w.n_tiles);
-    hipLaunchKernelGGL(k_fe_scan_tops, dim3(1), dim3(FE_THREADS), 0, st, w.tops, w.n_tiles);
-    hipLaunchKernelGGL(k_fe_scan_add, dim3(fe_grid(count)), dim3(FE_THREADS), 0, st, w.seg_off, w.kept_off, count, (const unsigned*)w.tops, w.n_tiles, (long long*)n_kept);
-    HIP_TRY(hipGetLastError());
+    SPRK_TRY(seg_scan(w.seg_off, (long long)n_users + 1, w.tops, w.n_tiles, FeScanKept<true>{w.kept_off, (long long*)n_kept}, st));
     if (n > 0) {
         hipLaunchKernelGGL(k_fe_scatter, dim3(fe_grid_capped(n)), dim3(FE_THREADS), 0, st, n, user_id, movie_id, rating, (const long long*)timestamp, (int)n_users, (int)n_movies,
                            (const unsigned*)w.seg_off, w.cursor, w.seg_ts, w.seg_row, w.seg_user);
         HIP_TRY(hipGetLastError());
-        const unsigned ug = n_users < 1 ? 1u : (unsigned)n_users < 65536u * 16u ? (unsigned)n_users : 65536u * 16u;
-        hipLaunchKernelGGL(k_fe_sort_short, dim3(ug), dim3(FE_THREADS), sort_lds, st, (int)n_users, cap, (const unsigned*)w.seg_off, w.seg_ts, w.seg_row, w.long_list, w.n_long);
-        HIP_TRY(hipGetLastError());
-        SPRK_TRY(fe_sort_long_segments(cap, n, w.seg_off, w.seg_ts, w.seg_row, w.tmp_ts, w.tmp_row, w.long_list, w.n_long, st));
+        SPRK_TRY(seg_sort(cap, n, n_users, w.seg_off, w.seg_ts, w.seg_row, w.tmp_ts, w.tmp_row, w.long_list, w.n_long, nullptr, st));
     }
     if (n_movies > 0) {
         hipLaunchKernelGGL(k_fe_movie_stats, dim3(fe_grid(n_movies)), dim3(FE_THREADS), 0, st, (int)n_movies, movie_year, (const unsigned*)w.mv_cnt, (const unsigned long long*)w.mv_S,

@@ -1,11 +1,11 @@
 // k_als.h -- ALS collaborative filtering on the device (the reference's offline/spark/model/CollaborativeFiltering.scala: Spark ALS,
 // explicit feedback, no non-negativity): factors from ratings, and scores from factors.  The definition these kernels equal bit for bit
-// is sparrowrecsys_amd/als.py als_host; DESIGN.md section 5.10 has the rules.  Part of sparrow_feature_eng.hip, after k_catalog.h; it
-// uses k_feature_eng.h's scan, LDS sort and merge.
+// is sparrowrecsys_amd/als.py als_host; DESIGN.md section 5.10 has the rules.  Uses k_segments.h: the counts-only scan and the
+// (ungated) segment sort, once per side.
 //
 // Stages, one stream, no host synchronisation (api_als.h launches them in this order):
 //   k_als_count       per rating: validate (error word), count the user's and the movie's ratings
-//   k_fe_scan_*       exclusive scans of the two sets of counts: segment offsets
+//   k_fe_scan_*<false>  exclusive scans of the two sets of counts: segment offsets
 //   k_als_scatter     per rating: into its MOVIE's segment as (user << 32 | input row, rating bits) and into its USER's segment as
 //                     (movie << 32 | input row, rating bits), at atomic cursors, any order
 //   k_fe_sort_short + k_fe_sort_long_chunks + k_fe_merge_pass (+ k_fe_long_copy)  each segment by its key, once for all sweeps
@@ -17,6 +17,7 @@
 // No float or double atomics and nothing split along a row's ratings: the result is a function of the input alone.
 
 static constexpr int ALS_THREADS = 256;
+static_assert(ALS_THREADS == FE_THREADS, "api_als.h sizes the grids of ALS_THREADS kernels with fe_grid_capped");
 static constexpr int ALS_G = 16;                   // lanes per destination row: four rows a wave
 static constexpr int ALS_CHUNK = 16;               // ratings per lane group and pipeline stage
 static constexpr int ALS_MAX_RANK = 16;

@@ -1,17 +1,17 @@
 // k_catalog.h -- the reference's DataManager on the device: per-movie average rating as Java computes it (Movie.addRating, Movie.java:93-98),
 // the rating-sorted and year-sorted lists of the whole catalogue and of every genre (getMovies / getMoviesByGenre, DataManager.java:253-283),
 // candidate generation and the default similarity ranker (SimilarMovieProcess.java:39-83, :145-159).  The definition these kernels equal
-// bit for bit is sparrowrecsys_amd/catalog.py catalog_host / similar_host; DESIGN.md section 5.9 has the rules.  Part of
-// sparrow_feature_eng.hip, after k_user_emb.h: the scan, the LDS sort and the merge are k_feature_eng.h's, the sort behind the
-// `ungrouped` word is k_user_emb.h's.
+// bit for bit is sparrowrecsys_amd/catalog.py catalog_host / similar_host; DESIGN.md section 5.9 has the rules.  Uses
+// k_segments.h: the counts-only scan, the segment sort (behind the `ungrouped` word for the ratings, ungated for the lists) and
+// fe_block_scan in k_cat_similar; and k_user_emb.h's UE_W_* control words.
 //
 // sprk_catalog_build, one stream, no host synchronisation (api_catalog.h launches them in this order):
 //   k_cat_count       per rating: a non-finite rating raises the error word; a rating on a movie the table holds is counted, and a
 //                     movie's second run of rows in the input raises `ungrouped` (as k_ue_count does for users)
-//   k_fe_scan_*       exclusive scan over movies of the counts: segment offsets
+//   k_fe_scan_*<false>  exclusive scan over movies of the counts: segment offsets
 //   -- only when `ungrouped` is raised --
 //   k_cat_scatter     per rating: (input row, rating) into its movie's segment at an atomic cursor, any order
-//   k_ue_sort_short, k_fe_sort_long_chunks + k_fe_merge_pass (+ k_fe_long_copy): every segment by input row
+//   k_fe_sort_short (gate = the word), k_fe_sort_long_chunks + k_fe_merge_pass (+ k_fe_long_copy): every segment by input row
 //   -- always --
 //   k_cat_avg_short   one lane per movie of fewer than CAT_WAVE_MIN ratings: the recurrence, ratings loaded a chunk ahead
 //   k_cat_avg_wave    one wave per longer movie: 64 ratings per coalesced load, a chunk ahead; every lane runs the one chain on values
@@ -23,7 +23,8 @@
 // sprk_catalog_similar: k_cat_similar, one workgroup per query.
 // Integer atomics only count; nothing depends on the order of arrival.
 
-static constexpr int CAT_THREADS = 256;            // = FE_THREADS: fe_block_scan and fe_sort_lds are used as they are
+static constexpr int CAT_THREADS = 256;
+static_assert(CAT_THREADS == FE_THREADS, "k_cat_similar calls fe_block_scan; api_catalog.h sizes the grids of CAT_THREADS kernels with fe_grid_capped");
 static constexpr int CAT_WAVE_MIN = 128;           // a movie of this many ratings or more gets a wave of its own
 static constexpr int CAT_CHUNK = 8;                // ratings per lane and pipeline stage of k_cat_avg_short
 static constexpr int CAT_MAX_CAND = 4096;          // gathered list entries of one query: 12 bytes x 4096 of LDS at the most

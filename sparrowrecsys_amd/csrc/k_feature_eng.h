@@ -1,24 +1,19 @@
 // k_feature_eng.h -- ratings -> training samples and the feature store's rows, on the device (FeatureEngForRecModel.scala:21-130: label,
 // movie aggregates, the previous-100-ratings window of every user).  The definition these kernels equal bit for bit is
-// sparrowrecsys_amd/featureeng.py samples_host; DESIGN.md section 5.7 has the rules.  Part of sparrow_feature_eng.hip.
+// sparrowrecsys_amd/featureeng.py samples_host; DESIGN.md section 5.7 has the rules.  Uses k_segments.h: FE_THREADS, the scan with
+// its `kept` half (the only user of it) and the segment sort.
 //
 // Stages, one stream, no host synchronisation (api_feature_eng.h launches them in this order):
 //   k_fe_hist       per rating: validate (error word), count the user's ratings, add the movie's n / S / Q      (integer atomics)
-//   k_fe_scan_*     exclusive scans over users of len and of kept = max(0, len - 2): segment and sample offsets
+//   k_fe_scan_*<true>  (k_segments.h) exclusive scans over users of len and of kept = max(0, len - 2): segment and sample offsets
 //   k_fe_scatter    per rating: (timestamp, input row) into its user's segment, any order (the sort key is total)
-//   k_fe_sort_short one workgroup per user: segments of up to `cap` ratings sorted in LDS; longer ones are listed
-//   k_fe_sort_long_chunks + k_fe_merge_pass x ceil(log2(n / cap)) (+ k_fe_long_copy): the listed segments, sorted in chunks of `cap`
-//                   and merged in global memory by rank (keys are distinct: rank in the partner run = one binary search)
+//   k_fe_sort_short, k_fe_sort_long_chunks + k_fe_merge_pass (+ k_fe_long_copy)  (k_segments.h) every user's segment by (timestamp, input row)
 //   k_fe_movie_stats per movie: the four float32 of the store's movie row
 //   k_fe_window     per sorted position: the window's count / S / Q, last positives, 32 genre counters, top five; writes the sample
 //   k_fe_store      per user and per movie: the store's rows and `has` bytes
 // All sums are integer sums: the result is a function of the input alone.
 
-static constexpr int FE_THREADS = 256;
-static constexpr int FE_SORT_CAP = 4096;          // ratings of one user sorted in LDS: 4096 x 12 bytes = 48 KB, three workgroups per CU
 static constexpr int FE_WINDOW = 100;             // rowsBetween(-100, -1)
-static constexpr int FE_SCAN_TILE = 4 * FE_THREADS;
-static constexpr int FE_MAX_GRID = 2048;
 static constexpr int FE_POSITIVE_R2 = 7;          // label = rating >= 3.5
 static constexpr unsigned long long FE_ERR_USER = 1, FE_ERR_MOVIE = 2, FE_ERR_RATING = 3;
 
@@ -54,25 +49,6 @@ template <class W> __host__ __device__ inline unsigned fe_sd_h(unsigned long lon
 
 __device__ inline float fe_hundredths(unsigned h) { return (float)((double)h / 100.0); }
 
-__device__ inline bool fe_key_less(long long ta, int ra, long long tb, int rb) { return ta < tb || (ta == tb && ra < rb); }
-
-// exclusive scan of one value per thread over the workgroup (FE_THREADS); sh holds FE_THREADS words
-__device__ inline unsigned fe_block_scan(unsigned v, unsigned* sh, unsigned* total) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int d = 1; d < FE_THREADS; d <<= 1) {
-        const unsigned a = t >= d ? sh[t - d] : 0u;
-        __syncthreads();
-        sh[t] += a;
-        __syncthreads();
-    }
-    const unsigned incl = sh[t];
-    *total = sh[FE_THREADS - 1];
-    __syncthreads();
-    return incl - v;
-}
-
 __global__ __launch_bounds__(FE_THREADS) void k_fe_hist(long long n, const int* __restrict__ user, const int* __restrict__ movie, const float* __restrict__ rating,
                                                         int n_users, int n_movies, unsigned* __restrict__ len, unsigned* __restrict__ mv_cnt,
                                                         unsigned long long* __restrict__ mv_S, unsigned long long* __restrict__ mv_Q,
@@ -88,55 +64,6 @@ __global__ __launch_bounds__(FE_THREADS) void k_fe_hist(long long n, const int* 
     }
 }
 
-// seg[i] = len_i, kept[i] = (unwritten) for i in [0, count): both become tile-local exclusive scans, the tiles' totals go to tops
-__global__ __launch_bounds__(FE_THREADS) void k_fe_scan_tiles(unsigned* __restrict__ seg, unsigned* __restrict__ kept, long long count, unsigned* __restrict__ tops, int n_tiles) {
-    __shared__ unsigned sh[FE_THREADS];
-    const long long base = (long long)blockIdx.x * FE_SCAN_TILE + (long long)threadIdx.x * 4;
-    unsigned a[4], b[4], sa = 0, sb = 0;
-    for (int k = 0; k < 4; ++k) {
-        a[k] = base + k < count ? seg[base + k] : 0u;
-        b[k] = a[k] > 2 ? a[k] - 2 : 0u;
-        sa += a[k]; sb += b[k];
-    }
-    unsigned ta, tb;
-    unsigned ea = fe_block_scan(sa, sh, &ta);
-    unsigned eb = fe_block_scan(sb, sh, &tb);
-    for (int k = 0; k < 4; ++k) {
-        if (base + k < count) { seg[base + k] = ea; kept[base + k] = eb; }
-        ea += a[k]; eb += b[k];
-    }
-    if (threadIdx.x == 0) { tops[blockIdx.x] = ta; tops[n_tiles + blockIdx.x] = tb; }
-}
-
-// one workgroup: tops[0..n_tiles) and tops[n_tiles..2 n_tiles) become exclusive scans
-__global__ __launch_bounds__(FE_THREADS) void k_fe_scan_tops(unsigned* __restrict__ tops, int n_tiles) {
-    __shared__ unsigned sh[FE_THREADS];
-    for (int w = 0; w < 2; ++w) {
-        unsigned* t = tops + (size_t)w * n_tiles;
-        unsigned carry = 0;
-        for (int b0 = 0; b0 < n_tiles; b0 += FE_THREADS) {
-            const int i = b0 + threadIdx.x;
-            const unsigned v = i < n_tiles ? t[i] : 0u;
-            unsigned total;
-            const unsigned e = fe_block_scan(v, sh, &total);
-            if (i < n_tiles) t[i] = carry + e;
-            carry += total;
-        }
-    }
-}
-
-// adds the tiles' offsets; element count - 1 (the one past the last user) then holds the totals: the number of kept samples goes to n_kept
-__global__ __launch_bounds__(FE_THREADS) void k_fe_scan_add(unsigned* __restrict__ seg, unsigned* __restrict__ kept, long long count, const unsigned* __restrict__ tops, int n_tiles,
-                                                            long long* __restrict__ n_kept) {
-    const long long i = (long long)blockIdx.x * FE_THREADS + threadIdx.x;
-    if (i >= count) return;
-    const int tile = (int)(i / FE_SCAN_TILE);
-    seg[i] += tops[tile];
-    const unsigned k = kept[i] + tops[n_tiles + tile];
-    kept[i] = k;
-    if (i == count - 1) *n_kept = (long long)k;
-}
-
 __global__ __launch_bounds__(FE_THREADS) void k_fe_scatter(long long n, const int* __restrict__ user, const int* __restrict__ movie, const float* __restrict__ rating,
                                                            const long long* __restrict__ ts, int n_users, int n_movies, const unsigned* __restrict__ seg_off,
                                                            unsigned* __restrict__ cursor, long long* __restrict__ seg_ts, int* __restrict__ seg_row, int* __restrict__ seg_user) {
@@ -147,106 +74,6 @@ __global__ __launch_bounds__(FE_THREADS) void k_fe_scatter(long long n, const in
         seg_ts[pos] = ts[i];
         seg_row[pos] = (int)i;
         seg_user[pos] = u;
-    }
-}
-
-// sorts count <= cap keys at (gts, grow) by (timestamp, input row) in LDS: bitonic over P = the next power of two, padded with keys greater
-// than any real one (input rows are < 2^31 - 1)
-__device__ inline void fe_sort_lds(long long* __restrict__ gts, int* __restrict__ grow, int count, long long* sts, int* srow) {
-    int P = 2;
-    while (P < count) P <<= 1;
-    for (int i = threadIdx.x; i < P; i += FE_THREADS) {
-        sts[i] = i < count ? gts[i] : 0x7fffffffffffffffll;
-        srow[i] = i < count ? grow[i] : 0x7fffffff;
-    }
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = threadIdx.x; i < P; i += FE_THREADS) {
-                const int x = i ^ j;
-                if (x > i) {
-                    const long long ta = sts[i], tb = sts[x];
-                    const int ra = srow[i], rb = srow[x];
-                    const bool up = (i & k) == 0;
-                    if (fe_key_less(tb, rb, ta, ra) == up) { sts[i] = tb; sts[x] = ta; srow[i] = rb; srow[x] = ra; }
-                }
-            }
-            __syncthreads();
-        }
-    for (int i = threadIdx.x; i < count; i += FE_THREADS) { gts[i] = sts[i]; grow[i] = srow[i]; }
-    __syncthreads();
-}
-
-// dynamic LDS: cap x 8 bytes of timestamps, then cap x 4 bytes of rows
-__global__ __launch_bounds__(FE_THREADS) void k_fe_sort_short(int n_users, int cap, const unsigned* __restrict__ seg_off, long long* __restrict__ seg_ts, int* __restrict__ seg_row,
-                                                              int* __restrict__ long_list, unsigned* __restrict__ n_long) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char fe_lds[];
-    long long* sts = (long long*)fe_lds;
-    int* srow = (int*)(fe_lds + (size_t)cap * 8);
-    for (int u = blockIdx.x; u < n_users; u += gridDim.x) {
-        const unsigned base = seg_off[u], len = seg_off[u + 1] - base;
-        if (len < 2) continue;
-        if (len <= (unsigned)cap) fe_sort_lds(seg_ts + base, seg_row + base, (int)len, sts, srow);
-        else if (threadIdx.x == 0) long_list[atomicAdd(n_long, 1u)] = u;        // at most n / (cap + 1) users: the list holds n / 64 + 1
-    }
-}
-
-__global__ __launch_bounds__(FE_THREADS) void k_fe_sort_long_chunks(int cap, const unsigned* __restrict__ seg_off, long long* __restrict__ seg_ts, int* __restrict__ seg_row,
-                                                                    const int* __restrict__ long_list, const unsigned* __restrict__ n_long) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char fe_lds[];
-    long long* sts = (long long*)fe_lds;
-    int* srow = (int*)(fe_lds + (size_t)cap * 8);
-    const unsigned nl = *n_long;
-    for (unsigned s = 0; s < nl; ++s) {
-        const int u = long_list[s];
-        const unsigned base = seg_off[u], len = seg_off[u + 1] - base;
-        const unsigned chunks = (len + cap - 1) / cap;
-        for (unsigned c = blockIdx.x; c < chunks; c += gridDim.x) {
-            const unsigned o = c * (unsigned)cap, cnt = len - o < (unsigned)cap ? len - o : (unsigned)cap;
-            fe_sort_lds(seg_ts + base + o, seg_row + base + o, (int)cnt, sts, srow);
-        }
-    }
-}
-
-// one merge level of every listed segment: sorted runs of `width` keys pair up; a key's place in the merged pair is its index in its own
-// run plus its rank in the partner run.  A run without a partner (and a segment of one run) is copied, so all segments move src -> dst together.
-__global__ __launch_bounds__(FE_THREADS) void k_fe_merge_pass(long long width, const unsigned* __restrict__ seg_off, const long long* __restrict__ src_ts, const int* __restrict__ src_row,
-                                                              long long* __restrict__ dst_ts, int* __restrict__ dst_row, const int* __restrict__ long_list,
-                                                              const unsigned* __restrict__ n_long) {
-    const unsigned nl = *n_long;
-    for (unsigned s = 0; s < nl; ++s) {
-        const int u = long_list[s];
-        const long long base = seg_off[u], len = (long long)seg_off[u + 1] - base;
-        for (long long p = (long long)blockIdx.x * FE_THREADS + threadIdx.x; p < len; p += (long long)gridDim.x * FE_THREADS) {
-            const long long run = p / width, rs = run * width, ps = (run ^ 1) * width;
-            const long long t = src_ts[base + p];
-            const int r = src_row[base + p];
-            long long out = p;
-            if (ps < len) {
-                long long lo = ps, hi = ps + width < len ? ps + width : len;            // the partner's keys less than this one: [ps, lo)
-                while (lo < hi) {
-                    const long long mid = (lo + hi) >> 1;
-                    if (fe_key_less(src_ts[base + mid], src_row[base + mid], t, r)) lo = mid + 1; else hi = mid;
-                }
-                out = (rs < ps ? rs : ps) + (p - rs) + (lo - ps);                         // < the pair's end <= len
-            }
-            dst_ts[base + out] = t;
-            dst_row[base + out] = r;
-        }
-    }
-}
-
-__global__ __launch_bounds__(FE_THREADS) void k_fe_long_copy(const unsigned* __restrict__ seg_off, const long long* __restrict__ src_ts, const int* __restrict__ src_row,
-                                                             long long* __restrict__ dst_ts, int* __restrict__ dst_row, const int* __restrict__ long_list,
-                                                             const unsigned* __restrict__ n_long) {
-    const unsigned nl = *n_long;
-    for (unsigned s = 0; s < nl; ++s) {
-        const int u = long_list[s];
-        const long long base = seg_off[u], len = (long long)seg_off[u + 1] - base;
-        for (long long p = (long long)blockIdx.x * FE_THREADS + threadIdx.x; p < len; p += (long long)gridDim.x * FE_THREADS) {
-            dst_ts[base + p] = src_ts[base + p];
-            dst_row[base + p] = src_row[base + p];
-        }
     }
 }
 

@@ -1,15 +1,15 @@
 // k_user_emb.h -- user embeddings from ratings and item embeddings, on the device (Embedding.scala:53-101 generateUserEmb: per user, the
 // float32 sum of the embeddings of the movies the user rated, folded from the user's LAST row in file order to the first, divided by the
 // number of the user's rows).  The definition these kernels equal bit for bit is sparrowrecsys_amd/userembedding.py user_emb_host;
-// DESIGN.md section 5.8 has the rules.  Part of sparrow_feature_eng.hip, after k_feature_eng.h, whose scan, LDS sort and merge it uses.
+// DESIGN.md section 5.8 has the rules.  Uses k_segments.h: the counts-only scan, and the segment sort behind the `ungrouped` word.
 //
 // Stages, one stream, no host synchronisation (api_user_emb.h launches them in this order):
 //   k_ue_count      per rating: validate (error word), count the user's ratings; a rating whose predecessor in the input belongs to
 //                   another user starts a run: the run's first row is kept, and a user's second run raises the `ungrouped` word
-//   k_fe_scan_*     exclusive scan over users of the counts: segment offsets
+//   k_fe_scan_*<false>  (k_segments.h) exclusive scan over users of the counts: segment offsets
 //   -- only when `ungrouped` is raised (the kernels read the word and return; the long-path kernels find an empty list) --
 //   k_ue_scatter    per rating: (input row, item row) into its user's segment at an atomic cursor, any order
-//   k_ue_sort_short one workgroup per user: fe_sort_lds by input row; longer segments are listed
+//   k_fe_sort_short (k_segments.h; its gate is the `ungrouped` word) one workgroup per user: fe_sort_lds by input row; longer segments are listed
 //   k_fe_sort_long_chunks + k_fe_merge_pass (+ k_fe_long_copy): the listed segments
 //   -- always --
 //   k_ue_sum        per (user, dimension): the ordered sum and the division
@@ -19,6 +19,7 @@
 // No float atomics and nothing split along a segment: the result is a function of the input alone.
 
 static constexpr int UE_THREADS = 256;
+static_assert(UE_THREADS == FE_THREADS, "api_user_emb.h sizes k_ue_count's and k_ue_scatter's grids with fe_grid_capped");
 static constexpr int UE_CHUNK = 16;                // item rows per lane and pipeline stage
 static constexpr int UE_MAX_D = 1024;
 static constexpr unsigned long long UE_ERR_USER = 1;
@@ -47,21 +48,6 @@ __global__ __launch_bounds__(UE_THREADS) void k_ue_scatter(long long n, const in
         const size_t pos = (size_t)seg_off[u] + atomicAdd(&cursor[u], 1u);     // < seg_off[u + 1]: the same rows were counted
         seg_key[pos] = i;
         seg_item[pos] = item_row[i];
-    }
-}
-
-// k_fe_sort_short behind the `ungrouped` word.  Dynamic LDS: cap x 8 bytes of keys, then cap x 4 bytes of item rows
-__global__ __launch_bounds__(FE_THREADS) void k_ue_sort_short(int n_users, int cap, const unsigned* __restrict__ seg_off, long long* __restrict__ seg_key, int* __restrict__ seg_item,
-                                                              int* __restrict__ long_list, unsigned* __restrict__ words) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char fe_lds[];
-    if (!words[UE_W_UNGROUPED]) return;
-    long long* skey = (long long*)fe_lds;
-    int* sitem = (int*)(fe_lds + (size_t)cap * 8);
-    for (int u = blockIdx.x; u < n_users; u += gridDim.x) {
-        const unsigned base = seg_off[u], len = seg_off[u + 1] - base;
-        if (len < 2) continue;
-        if (len <= (unsigned)cap) fe_sort_lds(seg_key + base, seg_item + base, (int)len, skey, sitem);
-        else if (threadIdx.x == 0) long_list[atomicAdd(&words[UE_W_LONG], 1u)] = u;      // at most n / (cap + 1) users: the list holds n / 64 + 1
     }
 }
 

@@ -1,8 +1,10 @@
-// sparrow_feature_eng.hip -- ratings -> training samples and the feature store's rows on the device: the kernels (k_feature_eng.h) and
-// their C ABI (api_feature_eng.h: sprk_feature_eng_workspace_bytes / sprk_feature_eng); and ratings + item embeddings -> user embeddings
-// (k_user_emb.h, api_user_emb.h: sprk_user_emb_workspace_bytes / sprk_user_emb), which shares the per-user scan, sort and merge; and the movie catalogue
-// (k_catalog.h, api_catalog.h: sprk_catalog_build_workspace_bytes / sprk_catalog_build / sprk_catalog_similar), which shares them per movie and per list; and ALS
-// collaborative filtering (k_als.h, api_als.h: sprk_als_workspace_bytes / sprk_als_fit / sprk_als_predict), which shares them per user and per movie.  A translation unit of its own, like
+// sparrow_feature_eng.hip -- the four pipelines that start from a ratings file, each as kernels (k_*.h) and a C ABI (api_*.h):
+//   ratings -> training samples and the feature store's rows   k_feature_eng.h, api_feature_eng.h: sprk_feature_eng_workspace_bytes / sprk_feature_eng
+//   ratings + item embeddings -> user embeddings               k_user_emb.h, api_user_emb.h: sprk_user_emb_workspace_bytes / sprk_user_emb
+//   the movie catalogue                                        k_catalog.h, api_catalog.h: sprk_catalog_build_workspace_bytes / sprk_catalog_build / sprk_catalog_similar
+//   ALS collaborative filtering                                k_als.h, api_als.h: sprk_als_workspace_bytes / sprk_als_fit / sprk_als_predict
+// All four count per id, scan, scatter into per-id segments and sort every segment: k_segments.h has that device code and host_segments.h
+// its launches, the workspace carver and the workspace check.  A translation unit of its own, like
 // sparrow_metrics.hip: nothing here is used by the forward engine and nothing of the engine is used here.  Shares with the other units
 // only host_common.h (the thread's error string behind sprk_last_error, HIP_TRY, the roctx ranges), which opens the kernels' namespace
 // this file closes.
@@ -20,6 +22,7 @@
 #include "sparrow_hip.h"
 
 #include "host_common.h"
+#include "k_segments.h"
 #include "k_feature_eng.h"
 #include "k_user_emb.h"
 #include "k_catalog.h"
@@ -29,6 +32,7 @@
 #pragma GCC visibility pop
 using namespace sprk_dev;
 
+#include "host_segments.h"
 #include "api_feature_eng.h"
 #include "api_user_emb.h"
 #include "api_catalog.h"

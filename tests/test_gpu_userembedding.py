@@ -9,6 +9,7 @@ import pytest
 from sparrowrecsys_amd import _lib as L
 from sparrowrecsys_amd import ranker as R
 from sparrowrecsys_amd import userembedding as UE
+from tests import featureeng_cases as fe_cases
 from tests import userembedding_cases as cases
 
 pytestmark = pytest.mark.gpu
@@ -116,6 +117,35 @@ def test_segments_at_the_sort_capacity_and_one_past(lib, monkeypatch, cap):
     case = dict(base, user=user, row=rng.randint(0, cases.N_ITEMS, len(user)), n_users=3)
     assert np.bincount(user).tolist() == [cap, cap + 1, 1]
     _check(case, "mean", D=10)
+
+
+SPARSE_ITEMS = 200
+SPARSE_EMPTY_IDS = [1026, 2046, 2049, 262_141, 262_147]      # no ratings, next to the edges below
+
+
+def sparse_users_case():
+    """featureeng_cases.sparse_users_ratings with every movieId mapped to a row of a random table of SPARSE_ITEMS rows, D = 10, a tenth of
+    them without an embedding."""
+    ratings = fe_cases.sparse_users_ratings()
+    rng = np.random.RandomState(17)
+    return {"user": ratings["userId"], "row": 3 * ratings["movieId"] % SPARSE_ITEMS, "emb": rng.standard_normal((SPARSE_ITEMS, 10)).astype(np.float32),
+            "has": (rng.rand(SPARSE_ITEMS) >= 0.1).astype(np.uint8), "n_users": 300_000}
+
+
+def test_users_on_both_sides_of_a_scan_tile_and_of_a_round_of_tile_totals(lib):
+    """300 000 user ids, 55 of them with ratings: users 1022 - 1025 and 2047 / 2048 sit on both sides of k_fe_scan_tiles<false>'s tile
+    of 1024 ids, users 262 142 - 262 145 on both sides of the 256 tiles k_fe_scan_tops<false> takes per round (293 tiles: two rounds),
+    and the last id has ratings, so the total past it is added to.  The set is shuffled: scatter, k_fe_sort_short behind its gate.
+    An offset wrong by one tile's or one round's total moves every later user's segment: the outputs are compared byte for byte, and
+    the ids without ratings next to each edge have neither an embedding nor a count."""
+    case = sparse_users_case()
+    lens = np.bincount(case["user"], minlength=case["n_users"])
+    assert lens[-1] > 0 and not lens[SPARSE_EMPTY_IDS].any() and not case["has"].all()
+    assert (np.bincount(case["user"][np.flatnonzero(np.diff(case["user"], prepend=-1))], minlength=case["n_users"]) > 1).any()      # a user with two runs: not grouped
+    for mode in ("mean", "sum"):
+        emb, has, count = _check(case, mode)
+        assert not has[SPARSE_EMPTY_IDS].any() and not count[SPARSE_EMPTY_IDS].any()
+        assert has.sum() >= 50 and (count > 0).sum() == (has > 0).sum()
 
 
 def test_error_word_names_the_lowest_bad_row_and_other_users_are_untouched(synthetic):
