@@ -675,6 +675,50 @@ int sprk_als_topk(const float* table, const uint8_t* table_has, int32_t n_rows, 
                   const float* query, const uint8_t* query_has, int32_t n_queries, int32_t query_stride,
                   int32_t K, float* scores, int32_t* rows, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- item2vec on the device: ratings -> per-user item sequences -> skip-gram item vectors ----
+ * The reference's offline/spark/embedding/Embedding.scala (processItemSequence, then Spark Word2Vec: skip-gram with hierarchical
+ * softmax) without Spark.  The definitions are sparrowrecsys_amd/item2vec.py sequences_host and skipgram_host (numpy); both calls equal
+ * them bit for bit.  DESIGN.md section 5.11 has the rules and the deviations from Spark.  The calls are asynchronous on `stream`, own
+ * no memory, check every argument before any device call (SPRK_EINVAL) and report bad input through *error_key, which the caller sets
+ * to ~0 first: the least (kind << 32 | row) by atomicMin, kind 1 = user id, 2 = item id out of range, 3 = rating not finite, 4 = the
+ * corpus does not hold n_words words (the low word is the number found).
+ *
+ * sprk_item_sequences: the rows with rating >= 3.5f, per user in ascending (timestamp, input row): seq_offsets [n_users + 1],
+ * seq_items (room for n_ratings, seq_offsets[n_users] written) and item_count [n_items] (an item's occurrences among the kept rows).
+ *
+ * sprk_item_walks: the graph route (generateTransitionMatrix + randomWalk).  The adjacent pairs (prev, next) of every sequence are
+ * grouped per prev and sorted by next; sample_count walks of at most sample_length items are drawn in integers from a counter-based
+ * generator (item2vec.py walks_host): the start is the item whose pairs hold pair number mulhi64(word, total), a step takes entry
+ * mulhi64(word, row_total) of the current item's sorted pairs, an item without successors ends the walk.  walk_offsets
+ * [sample_count + 1], walk_items (room for sample_count * sample_length).
+ *
+ * sprk_skipgram_fit: seq_offsets [n_seq + 1] / seq_items [n_seq_items] as above (or random walks of the same shape); item_vocab
+ * [n_items] = an item's vocabulary index or -1; code_len [V], codes [V][40], points [V][40] = the Huffman tables
+ * (item2vec.py vocabulary_host); n_words = the corpus' size after the items outside the vocabulary are dropped; init [V][init_stride],
+ * exp_table [1000] float32 and loss_table [2][1000] float64 as item2vec.py computes them -- the device calls no transcendental.
+ * Sequences are cut into sentences of max_sentence words.  An iteration walks the corpus in rounds of `round` consecutive positions
+ * that all read the model as the round found it; a row's updates of one round are added in ascending (centre, context or depth) and
+ * scaled by row_cap / n when n > row_cap of them meet.  Outputs: vectors [V][stride] (floats past D untouched), syn1 [V][D], *loss
+ * (the mean table loss of every term at the full window under the final model).  D in [1, 64], window in [1, 16].
+ * The workspace holds one 12-byte record (twice, for the sort) per (position, context) and (position, depth) pair:
+ * sprk_skipgram_workspace_bytes, 16-byte aligned (0 for sizes the call rejects). */
+size_t sprk_item_sequences_workspace_bytes(int64_t n_ratings, int32_t n_users, int32_t n_items);
+int sprk_item_sequences(const int32_t* user_id, const int32_t* movie_id, const float* rating, const int64_t* timestamp, int64_t n_ratings,
+                        int32_t n_users, int32_t n_items, int32_t* seq_offsets, int32_t* seq_items, int32_t* item_count,
+                        uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+size_t sprk_item_walks_workspace_bytes(int64_t n_seq_items, int32_t n_seq, int32_t n_items, int64_t sample_count, int32_t sample_length);
+int sprk_item_walks(const int32_t* seq_offsets, const int32_t* seq_items, int64_t n_seq_items, int32_t n_seq, int32_t n_items,
+                    int64_t sample_count, int32_t sample_length, uint64_t seed, int32_t* walk_offsets, int32_t* walk_items,
+                    uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+size_t sprk_skipgram_workspace_bytes(int64_t n_seq_items, int32_t n_seq, int32_t vocab_size, int64_t n_words, int32_t D, int32_t window, int32_t round);
+int sprk_skipgram_fit(const int32_t* seq_offsets, const int32_t* seq_items, int64_t n_seq_items, int32_t n_seq,
+                      const int32_t* item_vocab, int32_t n_items, int32_t vocab_size, int64_t n_words,
+                      const int32_t* code_len, const uint8_t* codes, const int32_t* points,
+                      const float* init, int32_t init_stride, const float* exp_table, const double* loss_table,
+                      int32_t D, int32_t window, int32_t iters, double lr, int32_t round, int32_t row_cap, uint64_t seed, int32_t max_sentence,
+                      float* vectors, int32_t stride, float* syn1, double* loss,
+                      uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- multi-GPU: the path's one collective (the reference has no distributed path) ----
  * Batch rows are sharded over one process per GPU, tables and weights replicated; every rank ends with all scores through ONE
  * all-gather of the per-rank score slices over RCCL / xGMI, enqueued on the caller's HIP stream (no host synchronisation).

@@ -40,6 +40,8 @@ EXPORTED_SYMBOLS = [
     "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_user_emb_workspace_bytes", "sprk_user_emb",
     "sprk_catalog_build_workspace_bytes", "sprk_catalog_build", "sprk_catalog_similar",
     "sprk_als_workspace_bytes", "sprk_als_fit", "sprk_als_predict", "sprk_als_topk_workspace_bytes", "sprk_als_topk",
+    "sprk_item_sequences_workspace_bytes", "sprk_item_sequences", "sprk_item_walks_workspace_bytes", "sprk_item_walks",
+    "sprk_skipgram_workspace_bytes", "sprk_skipgram_fit",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -292,8 +294,19 @@ def load_library():
         lib.sprk_als_topk_workspace_bytes.argtypes = [i32, i32, i32]
         lib.sprk_als_topk_workspace_bytes.restype = sz
         lib.sprk_als_topk.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, sz, vp]
+        lib.sprk_item_sequences_workspace_bytes.argtypes = [C.c_int64, i32, i32]
+        lib.sprk_item_sequences_workspace_bytes.restype = sz
+        lib.sprk_item_sequences.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, vp, vp, sz, vp]
+        lib.sprk_item_walks_workspace_bytes.argtypes = [C.c_int64, i32, i32, C.c_int64, i32]
+        lib.sprk_item_walks_workspace_bytes.restype = sz
+        lib.sprk_item_walks.argtypes = [vp, vp, C.c_int64, i32, i32, C.c_int64, i32, C.c_uint64, vp, vp, vp, vp, sz, vp]
+        lib.sprk_skipgram_workspace_bytes.argtypes = [C.c_int64, i32, i32, C.c_int64, i32, i32, i32]
+        lib.sprk_skipgram_workspace_bytes.restype = sz
+        lib.sprk_skipgram_fit.argtypes = [vp, vp, C.c_int64, i32, vp, i32, i32, C.c_int64, vp, vp, vp,          # sequences, the vocabulary's tables
+                                          vp, i32, vp, vp, i32, i32, i32, C.c_double, i32, i32, C.c_uint64, i32,  # init, the two tables, D .. max_sentence
+                                          vp, i32, vp, vp, vp, vp, sz, vp]                                       # vectors, syn1, loss, error word, workspace, stream
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

@@ -1,9 +1,11 @@
 // k_segments.h -- counts per id -> segment offsets, and every segment sorted by a 64-bit key with a 32-bit payload: the device code
-// that the four ratings pipelines of sparrow_feature_eng.hip share.  host_segments.h launches it (seg_scan, seg_sort).
+// that the five ratings pipelines of sparrow_feature_eng.hip share.  host_segments.h launches it (seg_scan, seg_sort).
 //   feature engineering (k_feature_eng.h)  segments per user, key (timestamp, input row); the scan with its `kept` half
 //   user embeddings (k_user_emb.h)         segments per user, key (input row, item row), the sort behind the `ungrouped` word
 //   the catalogue (k_catalog.h)            segments per movie, behind the word likewise, and the 2 (G + 1) lists; fe_block_scan in k_cat_similar
 //   ALS (k_als.h)                          segments per user and per movie
+//   item2vec (k_item2vec.h)                segments per user, key (timestamp, input row); per `prev` item, key (next, place); per row of
+//                                          syn0 / syn1, key (centre, context or depth)
 // The kernels keep the names they got in feature engineering, where they were written first: k_fe_* are the names in rocprof traces,
 // in the timing tables of docs/*_results.md, in DESIGN.md sections 5.7-5.10 and in the GPU tests' docstrings.
 //   k_fe_scan_*     exclusive scan over ids of len (and, KEPT, of kept = max(0, len - 2)): three launches
