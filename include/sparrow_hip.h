@@ -775,6 +775,32 @@ void sprk_vtable_destroy(sprk_vtable v);
  * duplicate (embedding_column's variable, DeepFM.py:55,60). */
 int sprk_upload_external(sprk_handle h, int32_t slot, const void* dev_ptr, size_t bytes);
 
+/* model.fit for the graphs "embedding rows + numerics -> Dense/ReLU stack -> one sigmoid" (NeuralCF arch 1, EmbeddingMLP), with Adam as
+ * TensorFlow's ApplyAdam computes it; sparrowrecsys_amd/trainer.py's train_host is the definition of every bit.
+ * sprk_train_model: the id columns (vocab; genre != 0: ids may be -1 = no row), the width of every table row, per input row k of the first
+ * Dense kernel the id column it comes from (xcol, -1 = a numeric) and its place in the table row or among the numerics (xsub), the hidden
+ * widths.  params / m / v: one float vector each -- the tables in column order ([vocab][emb_dim]), then per hidden layer its kernel
+ * ([in][out]) and bias, then the head's -- trained in place.  ids [n][n_cols] int32, dense [n][n_dense], labels [n]; order: NULL or a
+ * permutation of 0 .. n - 1 (step b takes positions [b batch, (b + 1) batch) of it); alphas [epochs x ceil(n / batch)]: Adam's lr_t per
+ * step, a device array like every other pointer; p [epochs][n]: every epoch's training probabilities by position.  Before the first step:
+ * an id outside its vocabulary (kind 1), a numeric (2) or a label (3) that is not finite gives *error_key = kind << 32 | row, the least
+ * such key (the caller presets ~0), and no parameter changes.  The whole fit is enqueued on `stream`: no synchronisation.
+ * n x n_cols must stay below 2^31 - 1 (the schedule's unsigned offsets); tile x (n_x + the widths + 2 x the widest) floats must fit 160 KB. */
+#define SPRK_TRAIN_MAX_COLS 16
+#define SPRK_TRAIN_MAX_LAYERS 8
+#define SPRK_TRAIN_MAX_X 256
+#define SPRK_TRAIN_MAX_WIDTH 256
+typedef struct {
+    int32_t n_cols, n_dense, emb_dim, n_x, n_layers;
+    int32_t vocab[SPRK_TRAIN_MAX_COLS], genre[SPRK_TRAIN_MAX_COLS];
+    int32_t width[SPRK_TRAIN_MAX_LAYERS];
+    int32_t xcol[SPRK_TRAIN_MAX_X], xsub[SPRK_TRAIN_MAX_X];
+} sprk_train_model;
+size_t sprk_train_workspace_bytes(const sprk_train_model* model, int64_t n, int32_t batch, int32_t tile);
+int sprk_train_fit(const sprk_train_model* model, const int32_t* ids, const float* dense, const float* labels, const int32_t* order, int64_t n,
+                   int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
+                   float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 const char* sprk_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "sprk_als_workspace_bytes", "sprk_als_fit", "sprk_als_predict", "sprk_als_topk_workspace_bytes", "sprk_als_topk",
     "sprk_item_sequences_workspace_bytes", "sprk_item_sequences", "sprk_item_walks_workspace_bytes", "sprk_item_walks",
     "sprk_skipgram_workspace_bytes", "sprk_skipgram_fit",
+    "sprk_train_workspace_bytes", "sprk_train_fit",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -71,6 +72,16 @@ METRICS_MAX_THRESHOLDS = 1024
 
 class JoinCol(C.Structure):
     _fields_ = [("source", C.c_int32), ("offset", C.c_int32), ("rule", C.c_int32), ("vocab", C.c_int32)]
+
+
+TRAIN_MAX_COLS, TRAIN_MAX_LAYERS, TRAIN_MAX_X, TRAIN_MAX_WIDTH = 16, 8, 256, 256
+
+
+class TrainModel(C.Structure):
+    """sprk_train_model (include/sparrow_hip.h): what trainer.family_of gives, as the library takes it."""
+    _fields_ = [("n_cols", C.c_int32), ("n_dense", C.c_int32), ("emb_dim", C.c_int32), ("n_x", C.c_int32), ("n_layers", C.c_int32),
+                ("vocab", C.c_int32 * TRAIN_MAX_COLS), ("genre", C.c_int32 * TRAIN_MAX_COLS), ("width", C.c_int32 * TRAIN_MAX_LAYERS),
+                ("xcol", C.c_int32 * TRAIN_MAX_X), ("xsub", C.c_int32 * TRAIN_MAX_X)]
 
 
 class Seg(C.Structure):
@@ -114,7 +125,7 @@ _lib = None
 
 
 def build_library(force: bool = False, verbose: bool = False) -> str:
-    """Compile csrc/sparrow_hip.hip + csrc/tu_*.hip + csrc/sparrow_metrics.hip + csrc/sparrow_feature_eng.hip for gfx950 into the in-tree libsparrow_hip.so
+    """Compile csrc/sparrow_hip.hip + csrc/tu_*.hip + csrc/sparrow_metrics.hip + csrc/sparrow_feature_eng.hip + csrc/sparrow_train.hip for gfx950 into the in-tree libsparrow_hip.so
     (hipcc cross-compiles without a GPU)."""
     csrc = os.path.dirname(SRC_PATH)
     deps = [os.path.join(csrc, f) for f in os.listdir(csrc)] + [os.path.join(INCLUDE_DIR, "sparrow_hip.h")]
@@ -155,6 +166,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
                 units = [SRC_PATH]
             units.append(os.path.join(csrc, "sparrow_metrics.hip"))   # the evaluation metrics: a unit of their own, no part of the engine's
             units.append(os.path.join(csrc, "sparrow_feature_eng.hip"))   # ratings -> samples and store rows (featureeng.py): likewise
+            units.append(os.path.join(csrc, "sparrow_train.hip"))         # model.fit (trainer.py): likewise
             flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-pthread", "-fvisibility=hidden", "-fvisibility-inlines-hidden",
                      "-I", INCLUDE_DIR, "-I", csrc]               # [r6] hidden by default: include/sparrow_hip.h's declarations are the only exports
             if defines:                                           # experiment builds
@@ -305,8 +317,12 @@ def load_library():
         lib.sprk_skipgram_fit.argtypes = [vp, vp, C.c_int64, i32, vp, i32, i32, C.c_int64, vp, vp, vp,          # sequences, the vocabulary's tables
                                           vp, i32, vp, vp, i32, i32, i32, C.c_double, i32, i32, C.c_uint64, i32,  # init, the two tables, D .. max_sentence
                                           vp, i32, vp, vp, vp, vp, sz, vp]                                       # vectors, syn1, loss, error word, workspace, stream
+        lib.sprk_train_workspace_bytes.argtypes = [C.POINTER(TrainModel), C.c_int64, i32, i32]
+        lib.sprk_train_workspace_bytes.restype = sz
+        lib.sprk_train_fit.argtypes = [C.POINTER(TrainModel), vp, vp, vp, vp, C.c_int64, i32, i32, i32, vp, C.c_float, C.c_float, C.c_float,   # model .. epsilon
+                                       vp, vp, vp, vp, vp, vp, sz, vp]                              # params, m, v, p, error word, workspace, stream
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

@@ -1,0 +1,30 @@
+// sparrow_train.hip -- model.fit on the device: k_train.h (the kernels) and api_train.h (sprk_train_workspace_bytes / sprk_train_fit).
+// A translation unit of its own, like sparrow_metrics.hip and sparrow_feature_eng.hip: nothing here is used by the forward engine and
+// nothing of the engine is used here.  The schedule is built with the segment code of the ratings pipelines (k_segments.h,
+// host_segments.h); its kernels are not templates, so this unit's copies live in a namespace of their own and the linker sees two names.
+#include <hip/hip_runtime.h>
+#include <dlfcn.h>
+#include <unistd.h>
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+
+#include "sparrow_hip.h"
+
+#include "host_common.h"
+namespace train_unit {
+#include "k_segments.h"
+#include "k_train.h"
+}  // namespace train_unit
+
+}  // namespace sprk_dev
+#pragma GCC visibility pop
+using namespace sprk_dev;
+using namespace sprk_dev::train_unit;
+
+#include "host_segments.h"
+#include "api_train.h"

@@ -414,6 +414,7 @@ class CTRModel:
             w[name] = a if hasattr(a, "data_ptr") else np.ascontiguousarray(a, dtype=np.float32)
         self.weights = w
         self._engine = None
+        self._fit_state = None                                     # Adam's moments belong to the weights fit() left
 
     # ---- plan / engine ------------------------------------------------------------------
     def build_plan(self):
@@ -560,6 +561,45 @@ class CTRModel:
             raise ValueError("evaluate: an iterable of (features, labels) batches, or a feature dict with labels, is required")
         labels = np.concatenate([np.asarray(b[1]).astype(np.float64).reshape(-1) for b in batches])
         return evaluate_scores(labels, self.predict(batches, batch_size)[:, 0])
+
+    def fit(self, x, y=None, batch_size: int = 4096, epochs: int = 5, learning_rate: float = 0.001, order=None, tile: Optional[int] = None):
+        """Like ``tf.keras.Model.fit`` under the reference's ``compile(optimizer='adam', loss='binary_crossentropy')``: Adam (Keras
+        defaults) on the device, from the model's CURRENT weights (``init_weights(seed, trained_like=False)`` gives the reference
+        initialisers), for ``NeuralCF(arch=1)`` and ``EmbeddingMLP``; ``trainer.train_host`` defines every bit.
+        ``x`` is what ``evaluate`` takes: a dict of columns with ``"label"`` (or ``y``) -- ``featureeng.DeviceSamples.columns`` straight
+        from HBM --, or an iterable of ``(features, labels)`` batches, which are concatenated.  Deviations from the reference's script:
+        ``batch_size`` defaults to 4096, not 12 (12 works: it is a sequential chain of 1.6 M steps per epoch), and rows are taken in
+        input order, or in ``order`` (a permutation of the rows, the same in every epoch), not through a shuffle buffer.  -> per epoch
+        ``[loss, accuracy, roc_auc, pr_auc]`` of the training forward's own probabilities.  The trained weights are set
+        (``predict`` / ``evaluate_device`` / ``predict_pairs`` / ``recommend`` serve them); Adam's moments and step count are kept,
+        so a second ``fit`` continues."""
+        from . import trainer
+        fam = trainer.family_of(self)
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("fit needs a HIP device: no HIP device is visible (trainer.train_host is the host definition)")
+        if isinstance(x, Mapping):
+            batches = [(x, x["label"] if y is None else y)]
+        else:
+            batches = list(x)
+            if not batches or not all(isinstance(b, (tuple, list)) and len(b) == 2 and isinstance(b[0], Mapping) for b in batches):
+                raise ValueError("fit: an iterable of (features, labels) batches, or a feature dict with labels, is required")
+        packed = [self.pack_device(f) for f, _ in batches]
+        dev = packed[0][0].device
+        labels = [(l.detach().to(dev) if isinstance(l, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(l), dtype=np.float32)).to(dev))
+                  .to(torch.float32).reshape(-1) for _, l in batches]
+        ids = packed[0][0] if len(packed) == 1 else torch.cat([b[0] for b in packed])
+        dense = packed[0][1] if len(packed) == 1 else torch.cat([b[1] for b in packed])
+        labels = labels[0] if len(labels) == 1 else torch.cat(labels)
+        if int(labels.numel()) != int(ids.shape[0]):
+            raise ValueError("fit: %d rows with %d labels" % (int(ids.shape[0]), int(labels.numel())))
+        state = getattr(self, "_fit_state", None)
+        got = trainer.train_device(fam, self.weights, ids, dense, labels, batch_size, epochs, learning_rate, order, tile, state, device=dev)
+        weights = dict(self.weights)
+        weights.update({k: v.cpu().numpy() for k, v in got.weights.items()})
+        self.set_weights(weights)
+        self._fit_state = (got.m, got.v, got.step)
+        return got.history
 
     def evaluate_device(self, x, y=None, batch_size: Optional[int] = None, num_thresholds: int = 200):
         """``evaluate`` with the metrics accumulated ON THE DEVICE (``metrics.DeviceMetrics`` over ``sprk_metrics_update``): takes what
