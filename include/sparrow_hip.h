@@ -801,6 +801,31 @@ int sprk_train_fit(const sprk_train_model* model, const int32_t* ids, const floa
                    int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
                    float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
 
+/* model.fit for DeepFM_v2: first order + sum-of-squares FM cross over per-field Dense projections + a deep stack, one sigmoid; the rules of the
+ * trainer above, sparrowrecsys_amd/trainer_fm.py's train_host is the definition of every bit.
+ * sprk_train_fm_model: the fields (vocab; genre != 0: ids may be -1 = no row; fo_off: the field's first row in fo_cat/kernel -- the blocks tile its
+ * rows), order[g] = the field of group g < n_order (distinct; the numerics are the last group), emb_dim, proj_dim, the hidden widths.
+ * params / m / v: one float vector each -- the emb/ tables in field order ([vocab][emb_dim]), fo_cat/kernel, fo_cat/bias, fo_num/kernel,
+ * fo_num/bias, per group proj kernel ([in][proj_dim]) and bias (the numerics' last), per hidden layer kernel ([in][out]) and bias, the head's
+ * kernel ([1 + proj_dim + last width]) and bias -- trained in place.  Every other argument, the error word and the enqueue-only contract are
+ * those of the fit above.  n x n_fields must stay below 2^31 - 1; one workgroup's LDS (trainer_fm.lds_bytes) must fit 160 KB.
+ * A NaN that reaches p, a parameter, m or v is stored as 0x7fc00000. */
+#define SPRK_TRAIN_FM_MAX_FIELDS 8
+#define SPRK_TRAIN_FM_MAX_LAYERS 8
+#define SPRK_TRAIN_FM_MAX_PROJ 128
+#define SPRK_TRAIN_FM_MAX_FLAT 1024
+#define SPRK_TRAIN_FM_MAX_WIDTH 256
+#define SPRK_TRAIN_FM_MAX_IN 256
+typedef struct {
+    int32_t n_fields, n_dense, emb_dim, proj_dim, n_order, n_layers;
+    int32_t vocab[SPRK_TRAIN_FM_MAX_FIELDS], genre[SPRK_TRAIN_FM_MAX_FIELDS], fo_off[SPRK_TRAIN_FM_MAX_FIELDS], order[SPRK_TRAIN_FM_MAX_FIELDS];
+    int32_t width[SPRK_TRAIN_FM_MAX_LAYERS];
+} sprk_train_fm_model;
+size_t sprk_train_fm_workspace_bytes(const sprk_train_fm_model* model, int64_t n, int32_t batch, int32_t tile);
+int sprk_train_fm_fit(const sprk_train_fm_model* model, const int32_t* ids, const float* dense, const float* labels, const int32_t* order, int64_t n,
+                      int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
+                      float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 const char* sprk_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)

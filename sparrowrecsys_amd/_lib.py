@@ -42,7 +42,7 @@ EXPORTED_SYMBOLS = [
     "sprk_als_workspace_bytes", "sprk_als_fit", "sprk_als_predict", "sprk_als_topk_workspace_bytes", "sprk_als_topk",
     "sprk_item_sequences_workspace_bytes", "sprk_item_sequences", "sprk_item_walks_workspace_bytes", "sprk_item_walks",
     "sprk_skipgram_workspace_bytes", "sprk_skipgram_fit",
-    "sprk_train_workspace_bytes", "sprk_train_fit",
+    "sprk_train_workspace_bytes", "sprk_train_fit", "sprk_train_fm_workspace_bytes", "sprk_train_fm_fit",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -82,6 +82,16 @@ class TrainModel(C.Structure):
     _fields_ = [("n_cols", C.c_int32), ("n_dense", C.c_int32), ("emb_dim", C.c_int32), ("n_x", C.c_int32), ("n_layers", C.c_int32),
                 ("vocab", C.c_int32 * TRAIN_MAX_COLS), ("genre", C.c_int32 * TRAIN_MAX_COLS), ("width", C.c_int32 * TRAIN_MAX_LAYERS),
                 ("xcol", C.c_int32 * TRAIN_MAX_X), ("xsub", C.c_int32 * TRAIN_MAX_X)]
+
+
+TRAIN_FM_MAX_FIELDS, TRAIN_FM_MAX_LAYERS, TRAIN_FM_MAX_PROJ, TRAIN_FM_MAX_FLAT, TRAIN_FM_MAX_WIDTH, TRAIN_FM_MAX_IN = 8, 8, 128, 1024, 256, 256
+
+
+class TrainFmModel(C.Structure):
+    """sprk_train_fm_model (include/sparrow_hip.h): what trainer_fm.family_of gives, as the library takes it."""
+    _fields_ = [("n_fields", C.c_int32), ("n_dense", C.c_int32), ("emb_dim", C.c_int32), ("proj_dim", C.c_int32), ("n_order", C.c_int32), ("n_layers", C.c_int32),
+                ("vocab", C.c_int32 * TRAIN_FM_MAX_FIELDS), ("genre", C.c_int32 * TRAIN_FM_MAX_FIELDS), ("fo_off", C.c_int32 * TRAIN_FM_MAX_FIELDS),
+                ("order", C.c_int32 * TRAIN_FM_MAX_FIELDS), ("width", C.c_int32 * TRAIN_FM_MAX_LAYERS)]
 
 
 class Seg(C.Structure):
@@ -321,8 +331,11 @@ def load_library():
         lib.sprk_train_workspace_bytes.restype = sz
         lib.sprk_train_fit.argtypes = [C.POINTER(TrainModel), vp, vp, vp, vp, C.c_int64, i32, i32, i32, vp, C.c_float, C.c_float, C.c_float,   # model .. epsilon
                                        vp, vp, vp, vp, vp, vp, sz, vp]                              # params, m, v, p, error word, workspace, stream
+        lib.sprk_train_fm_workspace_bytes.argtypes = [C.POINTER(TrainFmModel), C.c_int64, i32, i32]
+        lib.sprk_train_fm_workspace_bytes.restype = sz
+        lib.sprk_train_fm_fit.argtypes = [C.POINTER(TrainFmModel)] + lib.sprk_train_fit.argtypes[1:]             # sprk_train_fit's argument list
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_train_fm_workspace_bytes", "sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

@@ -565,7 +565,8 @@ class CTRModel:
     def fit(self, x, y=None, batch_size: int = 4096, epochs: int = 5, learning_rate: float = 0.001, order=None, tile: Optional[int] = None):
         """Like ``tf.keras.Model.fit`` under the reference's ``compile(optimizer='adam', loss='binary_crossentropy')``: Adam (Keras
         defaults) on the device, from the model's CURRENT weights (``init_weights(seed, trained_like=False)`` gives the reference
-        initialisers), for ``NeuralCF(arch=1)`` and ``EmbeddingMLP``; ``trainer.train_host`` defines every bit.
+        initialisers), for ``NeuralCF(arch=1)`` and ``EmbeddingMLP``; ``trainer.train_host`` defines every bit (DESIGN.md section 5.12);
+        and for ``DeepFMv2``, through ``trainer_fm`` with a ``train_host`` of its own under the same rules (section 5.13).
         ``x`` is what ``evaluate`` takes: a dict of columns with ``"label"`` (or ``y``) -- ``featureeng.DeviceSamples.columns`` straight
         from HBM --, or an iterable of ``(features, labels)`` batches, which are concatenated.  Deviations from the reference's script:
         ``batch_size`` defaults to 4096, not 12 (12 works: it is a sequential chain of 1.6 M steps per epoch), and rows are taken in
@@ -574,10 +575,12 @@ class CTRModel:
         (``predict`` / ``evaluate_device`` / ``predict_pairs`` / ``recommend`` serve them); Adam's moments and step count are kept,
         so a second ``fit`` continues."""
         from . import trainer
+        if type(self) is DeepFMv2:                                 # the FM graph has a trainer of its own (DESIGN.md section 5.13)
+            from . import trainer_fm as trainer
         fam = trainer.family_of(self)
         import torch
         if not torch.cuda.is_available():
-            raise RuntimeError("fit needs a HIP device: no HIP device is visible (trainer.train_host is the host definition)")
+            raise RuntimeError("fit needs a HIP device: no HIP device is visible (%s.train_host is the host definition)" % trainer.__name__.rsplit(".", 1)[-1])
         if isinstance(x, Mapping):
             batches = [(x, x["label"] if y is None else y)]
         else:

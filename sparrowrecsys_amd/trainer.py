@@ -71,7 +71,7 @@ def family_of(model) -> Family:
         for j, k in enumerate(model.numeric_keys):
             xcol[rows[k]], xsub[rows[k]] = -1, j
     else:
-        raise NotImplementedError("fit is implemented for NeuralCF(arch=1) and EmbeddingMLP, not for %s%s" %
+        raise NotImplementedError("fit is implemented for NeuralCF(arch=1) and EmbeddingMLP, and DeepFMv2 through trainer_fm, not for %s%s" %
                                   (type(model).__name__, "(arch=%r)" % model.arch if hasattr(model, "arch") else ""))
     cols = [(c.key, c.kind, int(c.vocab)) for c in model.id_columns]
     fam = Family(cols, ["emb/" + c[0] for c in cols], int(D), xcol, xsub, len(model.numeric_keys), [int(h) for h in model.hidden],
