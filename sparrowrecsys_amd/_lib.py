@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = [
     "sprk_pack_columns", "sprk_pack_columns_device", "sprk_pack_last_route", "sprk_set_many_streams", "sprk_set_many_batches", "sprk_emb_rank",
     "sprk_emb_topk", "sprk_emb_topk_workspace_bytes", "sprk_join_features", "sprk_rank_scores",
     "sprk_metrics_state_bytes", "sprk_metrics_reset", "sprk_metrics_update",
-    "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_user_emb_workspace_bytes", "sprk_user_emb",
+    "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_segments_grid", "sprk_user_emb_workspace_bytes", "sprk_user_emb",
     "sprk_catalog_build_workspace_bytes", "sprk_catalog_build", "sprk_catalog_similar",
     "sprk_als_workspace_bytes", "sprk_als_fit", "sprk_als_predict", "sprk_als_topk_workspace_bytes", "sprk_als_topk",
     "sprk_item_sequences_workspace_bytes", "sprk_item_sequences", "sprk_item_walks_workspace_bytes", "sprk_item_walks",
@@ -297,6 +297,8 @@ def load_library():
                                          vp, vp, vp, vp, vp, vp, vp, vp, vp,                             # the sample columns
                                          vp, vp, i32, vp, vp,                                            # the store's tables (or NULL)
                                          vp, vp, vp, sz, vp]                                             # error word, sample count, workspace, stream
+        lib.sprk_segments_grid.argtypes = [C.c_int64]
+        lib.sprk_segments_grid.restype = C.c_int64
         lib.sprk_user_emb_workspace_bytes.argtypes = [C.c_int64, i32]
         lib.sprk_user_emb_workspace_bytes.restype = sz
         lib.sprk_user_emb.argtypes = [vp, vp, C.c_int64, i32, vp, vp, i32, i32, i32,                     # ratings, sizes, item table, D, item_stride
@@ -335,7 +337,7 @@ def load_library():
         lib.sprk_train_fm_workspace_bytes.restype = sz
         lib.sprk_train_fm_fit.argtypes = [C.POINTER(TrainFmModel)] + lib.sprk_train_fit.argtypes[1:]             # sprk_train_fit's argument list
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_train_fm_workspace_bytes", "sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_segments_grid", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

@@ -57,7 +57,7 @@ int als_half_sweep(int n_dst, int rank, double reg, const unsigned* off, const l
     hipLaunchKernelGGL(k_als_begin, dim3(1), dim3(1), 0, st, words, (const unsigned long long*)err);
     constexpr int ROWS_PER_GROUP = ALS_THREADS / ALS_G;                     // rows a workgroup draws at once
     const long long groups = ((long long)n_dst + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP;
-    const unsigned g = groups < FE_MAX_GRID ? (unsigned)groups : (unsigned)FE_MAX_GRID;
+    const unsigned g = groups < (long long)fe_max_grid() ? (unsigned)groups : fe_max_grid();
     const int acc = rank * (rank + 1) / 2 + rank;                            // chains per lane = ceil(acc / 16): 2 up to rank 6, 5 up to rank 10, 10 beyond
     if (acc <= 2 * ALS_G)
         hipLaunchKernelGGL(k_als_half_sweep<2>, dim3(g), dim3(ALS_THREADS), 0, st, n_dst, rank, reg, off, key, val, src, src_stride, dst, dst_stride, fail_kind, words, err);

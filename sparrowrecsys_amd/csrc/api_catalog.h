@@ -120,7 +120,7 @@ int sprk_catalog_build(const int32_t* movie_id, const float* rating, int64_t n_r
         hipLaunchKernelGGL(k_cat_avg_short, dim3(mg), dim3(CAT_THREADS), 0, st, (int)n_movies, (const unsigned*)w.seg_off, (const unsigned*)w.first, (const int*)w.seg_rating, rating,
                            (const unsigned*)w.words, avg_rating, rating_count);
         const long long waves = ((long long)n_movies + CAT_THREADS / 64 - 1) / (CAT_THREADS / 64);          // workgroups that give every movie its own wave
-        hipLaunchKernelGGL(k_cat_avg_wave, dim3((unsigned)(waves < 65536 * 4 ? waves : 65536 * 4)), dim3(CAT_THREADS), 0, st, (int)n_movies, (const unsigned*)w.seg_off,
+        hipLaunchKernelGGL(k_cat_avg_wave, dim3(fe_grid_own_cap((unsigned)(waves < 65536 * 4 ? waves : 65536 * 4))), dim3(CAT_THREADS), 0, st, (int)n_movies, (const unsigned*)w.seg_off,
                            (const unsigned*)w.first, (const int*)w.seg_rating, rating, (const unsigned*)w.words, avg_rating);
         hipLaunchKernelGGL(k_cat_list_count, dim3(mg), dim3(CAT_THREADS), 0, st, (int)n_movies, (const unsigned*)movie_genre_mask, movie_has, G, w.lcnt);
         HIP_TRY(hipGetLastError());
@@ -134,7 +134,7 @@ int sprk_catalog_build(const int32_t* movie_id, const float* rating, int64_t n_r
         SPRK_TRY(seg_sort(cap, (long long)list_capacity, L, w.lseg_off, w.lkey, w.lrow, w.ltmp_key, w.ltmp_row, w.llong_list, w.lwords, nullptr, st));
     }
     if (list_capacity > 0) {
-        const unsigned wg = fe_grid_capped(list_capacity) < 256u ? fe_grid_capped(list_capacity) : 256u;
+        const unsigned wg = fe_grid_own_cap(fe_grid_capped(list_capacity) < 256u ? fe_grid_capped(list_capacity) : 256u);
         hipLaunchKernelGGL(k_cat_list_write, dim3(wg, (unsigned)L), dim3(CAT_THREADS), 0, st, G, (int)n_movies, (const unsigned*)w.lseg_off, (const int*)w.lrow, (const int*)w.inv_file,
                            (const int*)w.inv_hash, list_movies, (long long)list_capacity);
         HIP_TRY(hipGetLastError());

@@ -55,6 +55,8 @@ FeWorkspace fe_carve(void* base, int64_t n, int32_t n_users, int32_t n_movies) {
 
 extern "C" {
 
+int64_t sprk_segments_grid(int64_t items) { return (int64_t)fe_grid_capped(items); }
+
 size_t sprk_feature_eng_workspace_bytes(int64_t n_ratings, int32_t n_users, int32_t n_movies) {
     if (!fe_sizes_ok(n_ratings, n_users, n_movies)) return 0;
     return fe_carve(nullptr, n_ratings, n_users, n_movies).bytes;

@@ -89,7 +89,7 @@ int sprk_user_emb(const int32_t* user_id, const int32_t* item_row, int64_t n_rat
     }
     const bool narrow = D <= 16;                                            // 16 lanes a user, four users a wave; else a wave a user
     const long long groups = ((long long)n_users + (narrow ? 15 : 3)) / (narrow ? 16 : 4);       // workgroups that give every user its own lanes
-    const unsigned sg = groups < FE_MAX_GRID ? (unsigned)groups : (unsigned)FE_MAX_GRID;
+    const unsigned sg = groups < (long long)fe_max_grid() ? (unsigned)groups : fe_max_grid();
     if (narrow)
         hipLaunchKernelGGL(k_ue_sum<16>, dim3(sg), dim3(UE_THREADS), 0, st, (int)n_users, (const unsigned*)w.seg_off, (const unsigned*)w.first, (const int*)w.seg_item, item_row, item_emb,
                            item_has, (int)n_items, (int)D, (int)item_stride, (int)mode, user_emb, (int)user_stride, user_has, user_count, w.words);

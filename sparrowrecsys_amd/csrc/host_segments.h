@@ -14,7 +14,21 @@ inline unsigned fe_grid(long long items) {
     const long long g = (items + FE_THREADS - 1) / FE_THREADS;
     return (unsigned)(g < 1 ? 1 : g);
 }
-inline unsigned fe_grid_capped(long long items) { const unsigned g = fe_grid(items); return g < (unsigned)FE_MAX_GRID ? g : (unsigned)FE_MAX_GRID; }
+// Grid cap: FE_MAX_GRID, or SPRK_FE_MAX_GRID = an integer in [1, FE_MAX_GRID], read at each call (tests: a grid-stride loop's second round and a
+// work queue's second draw at small sizes; results do not depend on the grid).  fe_max_grid_env() = that value, 0 where the variable is unset
+// or anything else: the launches with a cap of their own (k_fe_sort_short, k_cat_avg_wave, k_cat_list_write) keep it then.
+inline unsigned fe_max_grid_env() {
+    if (const char* e = getenv("SPRK_FE_MAX_GRID")) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end != e && *end == 0 && v >= 1 && v <= FE_MAX_GRID) return (unsigned)v;
+    }
+    return 0;
+}
+inline unsigned fe_max_grid() { const unsigned v = fe_max_grid_env(); return v ? v : (unsigned)FE_MAX_GRID; }
+inline unsigned fe_grid_capped(long long items) { const unsigned g = fe_grid(items), cap = fe_max_grid(); return g < cap ? g : cap; }
+// a launch with a cap of its own: `g` workgroups as the launch sizes them, under SPRK_FE_MAX_GRID where that is set
+inline unsigned fe_grid_own_cap(unsigned g) { const unsigned v = fe_max_grid_env(); return v && v < g ? v : g; }
 
 // A workspace handed out part by part, in order; every part starts on a 16-byte boundary.  at = the bytes taken so far.
 struct Carver {
@@ -55,7 +69,7 @@ int fe_sort_long_segments(int cap, long long n, const unsigned* seg_off, long lo
     if (n <= cap) return SPRK_OK;                                           // no segment can be longer than the LDS sort holds
     const size_t sort_lds = (size_t)cap * 12;
     const unsigned lg = fe_grid_capped(n);
-    const unsigned cg = (unsigned)((n + cap - 1) / cap) < (unsigned)FE_MAX_GRID ? (unsigned)((n + cap - 1) / cap) : (unsigned)FE_MAX_GRID;
+    const unsigned cg = (unsigned)((n + cap - 1) / cap) < fe_max_grid() ? (unsigned)((n + cap - 1) / cap) : fe_max_grid();
     hipLaunchKernelGGL(k_fe_sort_long_chunks, dim3(cg), dim3(FE_THREADS), sort_lds, st, cap, seg_off, seg_ts, seg_row, long_list, n_long);
     HIP_TRY(hipGetLastError());
     long long* ts[2] = {seg_ts, tmp_ts};
@@ -78,7 +92,7 @@ int fe_sort_long_segments(int cap, long long n, const unsigned* seg_off, long lo
 int seg_sort(int cap, long long n, int n_segs, const unsigned* off, long long* key, int* val, long long* tmp_key, int* tmp_val, int* long_list, unsigned* n_long,
              const unsigned* gate, hipStream_t st) {
     if (n_segs == 0) return SPRK_OK;
-    const unsigned g = (unsigned)n_segs < 65536u * 16u ? (unsigned)n_segs : 65536u * 16u;
+    const unsigned g = fe_grid_own_cap((unsigned)n_segs < 65536u * 16u ? (unsigned)n_segs : 65536u * 16u);
     hipLaunchKernelGGL(k_fe_sort_short, dim3(g), dim3(FE_THREADS), (size_t)cap * 12, st, n_segs, cap, off, key, val, long_list, n_long, gate);
     HIP_TRY(hipGetLastError());
     return fe_sort_long_segments(cap, n, off, key, val, tmp_key, tmp_val, long_list, n_long, st);

@@ -121,6 +121,22 @@ def synthetic(grouped=False, seed=7, rated=True):
     return {"movieId": movie.astype(np.int64), "rating": rating}, movies, info
 
 
+# ---- many ratings on few movies: the ratings side past one round of its grid ----
+def many_ratings(n=530_000, n_movies=600, seed=19):
+    """-> (ratings, movies).  ``n`` shuffled half-star ratings on ``n_movies`` movies of one to three of 20 genres, ids 0 .. n_movies - 1 in a
+    shuffled file order; a thousandth of the ratings fall on ids outside the table.  530 000 > 2048 x 256: k_cat_count and k_cat_scatter
+    stride, and the per-movie sort takes every segment (about 880 ratings each) in LDS."""
+    rng = np.random.RandomState(seed)
+    ids = rng.permutation(n_movies)
+    genres = ["|".join(GENRES_20[g] for g in np.sort(rng.permutation(20)[:rng.randint(1, 4)])) for _ in range(n_movies)]
+    movies = {"movieId": ids.tolist(), "title": _titles(rng, n_movies), "genres": genres}
+    movie = rng.randint(0, n_movies, n)
+    odd = rng.permutation(n)[:n // 1000]
+    movie[odd] = np.where(rng.rand(len(odd)) < 0.5, -1 - rng.randint(0, 1000, len(odd)), n_movies + rng.randint(0, 10 ** 6, len(odd)))
+    rating = (rng.randint(1, 11, n) * 0.5).astype(np.float32)
+    return {"movieId": movie.astype(np.int64), "rating": rating}, movies
+
+
 # ---- a table for candidate counts: disjoint one-genre movies and eight query movies ----
 COUNT_GENRES = {10: 24, 11: 25, 12: 1, 13: 2, 14: 63, 15: 64, 16: 65, 17: 0}   # genre -> its members next to the query
 COUNT_QUERIES = {1024: 10, 1025: 11, 1: 12, 2: 13, 63: 14, 64: 15, 65: 16, 0: 17}   # the mode-0 candidate count -> the query's own genre

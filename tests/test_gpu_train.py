@@ -1,6 +1,7 @@
 """``trainer.train_device`` (``sprk_train_fit``, csrc/k_train.h) against its definition ``trainer.train_host``: every weight, every
 ``m``, every ``v``, every ``p`` of the last epoch, accuracy and both AUCs of every epoch byte for byte, the loss within
-``DeviceMetrics``' bound (tests/metrics_cases.py loss_bound) (``-m gpu``).  Tiny vocabularies, tens to a few hundred rows."""
+``DeviceMetrics``' bound (tests/metrics_cases.py loss_bound) (``-m gpu``).  Tiny vocabularies and tens to a few hundred rows, then the
+step shape ``model.fit`` ships with: batch 4096 at the default tile, the stated maxima, tables and schedules beyond one round of a grid."""
 import ctypes as C
 
 import numpy as np
@@ -327,3 +328,125 @@ def test_ratings_to_recommendations(torch):
     cont = T.train_host(T.family_of(other), want.weights, ids, dense, np.asarray(cols["label"], dtype=F), batch_size=64, epochs=1, learning_rate=0.01,
                         state=(want.m, want.v, want.step))
     assert all(TC.same_bits(model.weights[k], cont.weights[k]) for k in cont.weights) and again[0][1:] == cont.history[0][1:]
+
+
+# ---------------------------------------------------------------- the step shape model.fit ships with
+
+def _mlp_128(n, seed):
+    """``EmbeddingMLP(hidden=(128, 128))`` over small buckets: n_x = 107, the default tile 8."""
+    model = M.EmbeddingMLP(seed=5, movie_buckets=30, user_buckets=40, hidden=(128, 128))
+    fam = T.family_of(model)
+    return (fam, model.weights) + TC.data(fam, n, seed)
+
+
+@pytest.mark.parametrize("which", ["neuralcf", "embedding_mlp"])
+def test_batch_4096_at_the_default_tile(torch, which):
+    """N = 4096 + 77, one epoch: one full batch of ``DEFAULT_BATCH`` rows and a short one.  NeuralCF over tables of 1 001 and 30 001 rows
+    (tile 16: 256 tiles, then 5); EmbeddingMLP (128, 128) (tile 8: 512 tiles, then 10 -- 64 rounds of the unrolled partial sum)."""
+    n = T.DEFAULT_BATCH + 77
+    if which == "neuralcf":
+        model = M.NeuralCF(seed=3, movie_buckets=1001, user_buckets=30001)
+        fam = T.family_of(model)
+        fam, w, ids, dense, y = (fam, model.weights) + TC.data(fam, n, 21)
+        assert fam.widths == [10, 10] and len(fam.xcol) == 20 and T.default_tile(fam) == 16
+    else:
+        fam, w, ids, dense, y = _mlp_128(n, 22)
+        assert T.default_tile(fam) == 8
+    want = both(fam, w, ids, dense, y, epochs=1)
+    assert want.step == 2
+
+
+@pytest.mark.parametrize("batch", [56, 64, 72, 120, 128, 136])
+def test_tile_counts_around_the_unrolled_partial_sum(torch, batch):
+    """Tile 8: 7, 8, 9, 15, 16 and 17 tiles -- k_tr_dense_adam adds eight partials at a time, then the rest -- and a last batch of 5 rows."""
+    fam, w, ids, dense, y = small(batch + 5, seed=batch)
+    assert batch // 8 in (7, 8, 9, 15, 16, 17)
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=8)
+
+
+def test_steps_of_more_than_48_kb_of_lds(torch):
+    """EmbeddingMLP (128, 128): 619 floats of LDS per sample.  The tiles come from ``lds_bytes``: ``mid`` = half the largest, above 48 KB (the
+    step kernel needs its attribute raised), run before and after a step of 20 KB in this one process; ``top`` = the largest that fits 160 KB;
+    ``top + 1`` is refused in words by the library and by ``train_device``."""
+    fam, w, ids, dense, y = _mlp_128(60, 23)
+    per = T.lds_bytes(fam, 1)
+    assert per == 619 * 4
+    top = T.LDS_BYTES // per
+    mid = top // 2
+    assert 48 * 1024 < T.lds_bytes(fam, mid) < T.lds_bytes(fam, top) <= T.LDS_BYTES < T.lds_bytes(fam, top + 1) and T.lds_bytes(fam, 8) < 48 * 1024
+    for tile, n in ((mid, 50), (8, 40), (mid, 60), (top, 60)):
+        both(fam, w, ids[:n], dense[:n], y[:n], batch_size=n, epochs=2, tile=tile)
+    lib = L.load_library()
+    ms = T._model_struct(fam)
+    assert lib.sprk_train_workspace_bytes(C.byref(ms), 60, 60, top) > 0 and lib.sprk_train_workspace_bytes(C.byref(ms), 60, 60, top + 1) == 0
+    rc = lib.sprk_train_fit(C.byref(ms), None, None, None, None, 60, 60, top + 1, 1, None, 0.1, 0.001, 1e-7, None, None, None, None, None, None, 0, None)
+    assert rc == L.EINVAL and b"tile = %d needs %d bytes of LDS" % (top + 1, T.lds_bytes(fam, top + 1)) in lib.sprk_last_error()
+    with pytest.raises(ValueError, match="tile = %d needs %d bytes of LDS" % (top + 1, T.lds_bytes(fam, top + 1))):
+        T.train_device(fam, w, ids, dense, y, batch_size=60, epochs=1, tile=top + 1)
+
+
+def test_a_tile_wider_than_the_workgroup(torch):
+    """Tile 300 > 256 threads: every per-sample loop of k_tr_step goes round; N = batch = 650 gives tiles of 300, 300 and 50."""
+    fam, w, ids, dense, y = small(650, seed=24)
+    assert T.lds_bytes(fam, 300) <= 48 * 1024
+    both(fam, w, ids, dense, y, batch_size=650, epochs=2, tile=300)
+
+
+@pytest.mark.parametrize("layers", [1, T.MAX_LAYERS])
+def test_the_stated_maxima(torch, layers):
+    """16 id columns x emb_dim 16 = 256 input rows, layers of 256 units, one and eight of them; 40 rows, tile 8."""
+    fam = TC.family([5] * T.MAX_COLS, ["id", "genre"] * (T.MAX_COLS // 2), 16, 0, [T.MAX_WIDTH] * layers)
+    assert len(fam.xcol) == T.MAX_X and len(fam.columns) == T.MAX_COLS
+    w = TC.weights(fam, 25)
+    ids, dense, y = TC.data(fam, 40, 25)
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+
+
+def test_a_table_beyond_one_round_of_the_grid(torch):
+    """Vocabularies (60 000, 5) x 10: 600 050 table floats, more than the 524 288 one round of k_tr_table_adam's grid covers.  Step 1 hits
+    rows 0, 52 428, 52 429 and 59 999: elements 524 280 .. 524 299 lie on both sides of the round's end.  Those rows move, rows never hit
+    keep their bits, and a row hit in step 1 only still moves in step 3."""
+    fam = TC.family([60000, 5], ["id", "id"], 10, 2, [6])
+    w = TC.weights(fam, 26)
+    ids, dense, y = TC.data(fam, 40, 26)
+    first = np.array([0, 52428, 52429, 59999])
+    ids[:16, 0] = first[np.arange(16) % 4]
+    later = np.random.default_rng(26).integers(100, 50000, 24)
+    ids[16:, 0] = later
+    assert (ids[16:, 0] != 52428).all() and 52428 * 10 < 2048 * 256 <= 52429 * 10
+    one = both(fam, w, ids[:16], dense[:16], y[:16], batch_size=16, epochs=1, tile=8)
+    two = both(fam, w, ids[:32], dense[:32], y[:32], batch_size=16, epochs=1, tile=8)
+    three = both(fam, w, ids, dense, y, batch_size=16, epochs=1, tile=8)
+    assert three.step == 3
+    for row in first:
+        assert not TC.same_bits(one.weights["emb/c0"][row], w["emb/c0"][row])
+        assert not TC.same_bits(three.weights["emb/c0"][row], two.weights["emb/c0"][row])             # hit in step 1 only: still moving
+    never = np.ones(60000, dtype=bool)
+    never[ids[:, 0]] = False
+    assert never.sum() > 59900 and TC.same_bits(three.weights["emb/c0"][never], w["emb/c0"][never])
+    assert TC.same_bits(one.weights["emb/c0"][np.setdiff1d(np.arange(60000), first)], w["emb/c0"][np.setdiff1d(np.arange(60000), first)])
+
+
+@pytest.mark.parametrize("batch,tile", [(4096, 32), (33000, 128)])
+def test_the_schedule_beyond_one_round_of_the_grid(torch, batch, tile):
+    """16 columns of vocabulary 7, emb_dim 2, N = 33 000: 528 000 entries, so k_tr_count and k_tr_scatter make a second trip; in batches
+    of 4 096 and as one batch of 33 000."""
+    fam = TC.family([7] * 16, ["id", "genre"] * 8, 2, 1, [4])
+    w = TC.weights(fam, 27)
+    ids, dense, y = TC.data(fam, 33000, 27)
+    assert ids.size > 2048 * 256
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=tile)
+
+
+def test_the_error_word_beyond_one_round_of_the_grid(torch):
+    """N = 524 288 + 600: bad labels at rows 524 300 and 524 500, both in k_tr_check's second trip.  Both routes name row 524 300 and no
+    parameter moves; the check precedes any training."""
+    fam, w, ids, dense, y = small(2048 * 256 + 600, seed=28)
+    y[524500], y[524300] = np.nan, np.inf
+    flat0 = np.concatenate([w[k].reshape(-1) for k in T.param_names(fam)])
+    rc, params, m, v, p, word, intact = raw_fit(torch, fam, w, ids, dense, y, 65536, 16, 1)
+    assert rc == 0 and intact and word == (T.ERR_LABEL << 32 | 524300), (word >> 32, word & 0xffffffff)
+    assert TC.same_bits(params, flat0) and not m.any() and not v.any()
+    for fit in (T.train_device, T.train_host):
+        with pytest.raises(ValueError, match="samples row 524300: the label"):
+            fit(fam, w, ids, dense, y, batch_size=65536, epochs=1, tile=16)

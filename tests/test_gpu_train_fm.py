@@ -1,6 +1,7 @@
 """``trainer_fm.train_device`` (``sprk_train_fm_fit``, csrc/k_train_fm.h) against its definition ``trainer_fm.train_host``: every weight,
 every ``m``, every ``v``, every ``p`` of the last epoch, accuracy and both AUCs of every epoch byte for byte, the loss within
-``max(N, 64) 2^-50`` relative (``-m gpu``).  Tiny vocabularies, tens to a few hundred rows."""
+``max(N, 64) 2^-50`` relative (``-m gpu``).  Tiny vocabularies and tens to a few hundred rows, then the step shape ``model.fit`` ships
+with: batch 4096 at the default tile, the stated maxima, tables and schedules beyond one round of a grid."""
 import ctypes as C
 
 import numpy as np
@@ -360,3 +361,107 @@ def test_neural_cf_fit_is_what_it_was(torch):
     history = model.fit({"movieId": ids[:, 0], "userId": ids[:, 1], "label": y}, batch_size=32, epochs=2)
     want = T.train_host(fam, start, ids, dense, y, batch_size=32, epochs=2)
     assert all(same(model.weights[k], want.weights[k]) for k in want.weights) and [h[1:] for h in history] == [h[1:] for h in want.history]
+
+
+# ---------------------------------------------------------------- the step shape model.fit ships with
+
+def test_batch_4096_at_the_default_tile(torch):
+    """The reference shape, N = 4096 + 77, one epoch: one full batch of ``DEFAULT_BATCH`` rows (512 tiles of 8: 64 rounds of the unrolled
+    partial sum) and a short one of 10 tiles."""
+    fam, w, ids, dense, y = TFC.small(TF.DEFAULT_BATCH + 77, seed=21, **TFC.REFERENCE_SHAPE)
+    assert TF.default_tile(fam) == 8
+    want = both(fam, w, ids, dense, y, epochs=1)
+    assert want.step == 2
+
+
+@pytest.mark.parametrize("batch", [56, 64, 72, 120, 128, 136])
+def test_tile_counts_around_the_unrolled_partial_sum(torch, batch):
+    """Tile 8: 7, 8, 9, 15, 16 and 17 tiles -- k_tf_dense_adam adds eight partials at a time, then the rest -- and a last batch of 5 rows."""
+    fam, w, ids, dense, y = TFC.small(batch + 5, seed=batch)
+    assert batch // 8 in (7, 8, 9, 15, 16, 17)
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=8)
+
+
+def test_steps_of_more_than_48_kb_of_lds(torch):
+    """The reference shape: 1 249 floats of LDS per sample.  The tiles come from ``lds_bytes``: ``mid`` = half the largest, above 48 KB (the
+    step kernel needs its attribute raised), run before and after a step of 39 KB in this one process; ``top`` = the largest that fits 160 KB;
+    ``top + 1`` is refused in words by the library and by ``train_device``."""
+    fam, w, ids, dense, y = TFC.small(60, seed=23, **TFC.REFERENCE_SHAPE)
+    per = TF.lds_bytes(fam, 1)
+    top = TF.LDS_BYTES // per
+    mid = top // 2
+    assert 48 * 1024 < TF.lds_bytes(fam, mid) < TF.lds_bytes(fam, top) <= TF.LDS_BYTES < TF.lds_bytes(fam, top + 1) and TF.lds_bytes(fam, 8) < 48 * 1024
+    for tile, n in ((mid, 50), (8, 40), (mid, 60), (top, 60)):
+        both(fam, w, ids[:n], dense[:n], y[:n], batch_size=n, epochs=2, tile=tile)
+    lib = L.load_library()
+    ms = TF._model_struct(fam)
+    assert lib.sprk_train_fm_workspace_bytes(C.byref(ms), 60, 60, top) > 0 and lib.sprk_train_fm_workspace_bytes(C.byref(ms), 60, 60, top + 1) == 0
+    rc = lib.sprk_train_fm_fit(C.byref(ms), None, None, None, None, 60, 60, top + 1, 1, None, 0.1, 0.001, 1e-7, None, None, None, None, None, None, 0, None)
+    assert rc == L.EINVAL and b"tile = %d needs %d bytes of LDS" % (top + 1, TF.lds_bytes(fam, top + 1)) in lib.sprk_last_error()
+    with pytest.raises(ValueError, match="tile = %d needs %d bytes of LDS" % (top + 1, TF.lds_bytes(fam, top + 1))):
+        TF.train_device(fam, w, ids, dense, y, batch_size=60, epochs=1, tile=top + 1)
+
+
+def test_a_tile_wider_than_the_workgroup(torch):
+    """Tile 300 > 256 threads: every per-sample loop of k_tf_step goes round; N = batch = 650 gives tiles of 300, 300 and 50."""
+    fam, w, ids, dense, y = TFC.small(650, seed=24)
+    assert TF.lds_bytes(fam, 300) <= TF.LDS_BYTES
+    both(fam, w, ids, dense, y, batch_size=650, epochs=2, tile=300)
+
+
+@pytest.mark.parametrize("kw", [dict(hidden=(TF.MAX_WIDTH,)), dict(hidden=(TF.MAX_WIDTH,) * TF.MAX_LAYERS),
+                                dict(vocabs=(6, 5), kinds=("id", "genre"), order=(0,), emb_dim=TF.MAX_IN)])
+def test_the_stated_maxima(torch, kw):
+    """Hidden layers of ``MAX_WIDTH`` units, one and ``MAX_LAYERS`` of them; table rows of ``MAX_IN`` floats; 40 rows, tile 8."""
+    fam, w, ids, dense, y = TFC.small(40, seed=25, **kw)
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+
+
+def test_a_table_beyond_one_round_of_the_grid(torch):
+    """Vocabularies (60 000, 5) x 10: 600 050 ``emb/`` floats and the 60 005 rows of ``fo_cat/kernel`` behind them, more than the 524 288 one
+    round of k_tf_table_adam's grid covers.  Step 1 hits rows 0, 52 428, 52 429 and 59 999 of field 0: elements 524 280 .. 524 299 lie on both
+    sides of the round's end, and every first-order row lies beyond it.  Those rows move, in ``emb/`` and in ``fo_cat/kernel``; rows never
+    hit keep their bits; a row hit in step 1 only still moves in step 3."""
+    fam, w, ids, dense, y = TFC.small(40, seed=26, vocabs=(60000, 5), kinds=("id", "id"), emb_dim=10)
+    key, fo0 = "emb/" + fam.fields[0][0], fam.fo_off[0]
+    assert fam.fields[0][2] == 60000 and TF.param_names(fam)[0] == key
+    first = np.array([0, 52428, 52429, 59999])
+    ids[:16, 0] = first[np.arange(16) % 4]
+    ids[16:, 0] = np.random.default_rng(26).integers(100, 50000, 24)
+    assert 52428 * 10 < 2048 * 256 <= 52429 * 10
+    one = both(fam, w, ids[:16], dense[:16], y[:16], batch_size=16, epochs=1, tile=8)
+    two = both(fam, w, ids[:32], dense[:32], y[:32], batch_size=16, epochs=1, tile=8)
+    three = both(fam, w, ids, dense, y, batch_size=16, epochs=1, tile=8)
+    assert three.step == 3
+    for row in first:
+        for name, r in ((key, row), ("fo_cat/kernel", fo0 + row)):
+            assert not same(one.weights[name][r], w[name][r])
+            assert not same(three.weights[name][r], two.weights[name][r])                             # hit in step 1 only: still moving
+    never = np.ones(60000, dtype=bool)
+    never[ids[:, 0]] = False
+    assert never.sum() > 59900 and same(three.weights[key][never], w[key][never])
+    assert same(three.weights["fo_cat/kernel"][fo0:fo0 + 60000][never], w["fo_cat/kernel"][fo0:fo0 + 60000][never])
+    rest = np.setdiff1d(np.arange(60000), first)
+    assert same(one.weights[key][rest], w[key][rest]) and same(one.weights["fo_cat/kernel"][fo0 + rest], w["fo_cat/kernel"][fo0 + rest])
+
+
+@pytest.mark.parametrize("batch,tile", [(4096, 32), (66000, 128)])
+def test_the_schedule_beyond_one_round_of_the_grid(torch, batch, tile):
+    """Eight fields, N = 66 000: 528 000 entries, so k_tr_count and k_tr_scatter make a second trip; in batches of 4 096 and as one batch."""
+    fam, w, ids, dense, y = TFC.small(66000, seed=27, **EIGHT)
+    assert ids.size > 2048 * 256
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=tile)
+
+
+def test_the_error_word_beyond_one_round_of_the_grid(torch):
+    """N = 524 288 + 600: bad labels at rows 524 300 and 524 500, both in k_tr_check's second trip.  Both routes name row 524 300 and no
+    parameter moves; the check precedes any training."""
+    fam, w, ids, dense, y = TFC.small(2048 * 256 + 600, seed=28)
+    y[524500], y[524300] = np.nan, np.inf
+    flat0 = np.concatenate([w[k].reshape(-1) for k in TF.param_names(fam)])
+    rc, params, m, v, p, word, intact = raw_fit(torch, fam, w, ids, dense, y, 65536, 16, 1)
+    assert rc == 0 and intact and word == (T.ERR_LABEL << 32 | 524300), (word >> 32, word & 0xffffffff)
+    assert same(params, flat0) and not m.any() and not v.any()
+    for fit in (TF.train_device, TF.train_host):
+        with pytest.raises(ValueError, match="samples row 524300: the label"):
+            fit(fam, w, ids, dense, y, batch_size=65536, epochs=1, tile=16)

@@ -277,6 +277,35 @@ def test_fit_without_a_device_points_to_the_host_definition(samples):
         T.train_device(fam, M.NeuralCF(seed=1).weights, np.zeros((1, 2), np.int32), np.zeros((1, 0), F), np.zeros(1, F))
 
 
+LIMIT_STRUCT = {"columns": ("n_cols", T.MAX_COLS + 1), "layers": ("n_layers", T.MAX_LAYERS + 1), "rows": ("n_x", T.MAX_X + 1), "width": ("width", T.MAX_WIDTH + 1)}
+
+
+@pytest.mark.parametrize("what,kw", [("columns", dict(vocabs=[5] * (T.MAX_COLS + 1), kinds=["id"] * (T.MAX_COLS + 1), emb_dim=2, n_dense=0, widths=[4])),
+                                     ("layers", dict(vocabs=[5], kinds=["id"], emb_dim=2, n_dense=0, widths=[2] * (T.MAX_LAYERS + 1))),
+                                     ("rows", dict(vocabs=[5] * T.MAX_COLS, kinds=["id"] * T.MAX_COLS, emb_dim=16, n_dense=1, widths=[4])),
+                                     ("width", dict(vocabs=[5], kinds=["id"], emb_dim=2, n_dense=0, widths=[T.MAX_WIDTH + 1]))])
+def test_one_more_than_each_maximum_is_refused_in_words(lib, what, kw):
+    """17 id columns, 9 hidden layers, 257 input rows, a layer of 257 units: ``_check_family`` names the limits, and the library, given the
+    largest family with that one field raised, reports no workspace and refuses the fit before any device call, naming them too."""
+    import ctypes as C
+    from sparrowrecsys_amd import _lib as L
+    with pytest.raises(ValueError, match="up to %d id columns, %d hidden layers of up to %d units and %d input rows" % (T.MAX_COLS, T.MAX_LAYERS, T.MAX_WIDTH, T.MAX_X)):
+        TC.family(**kw)
+    fam = TC.family([5] * T.MAX_COLS, ["id"] * T.MAX_COLS, 16, 0, [T.MAX_WIDTH] * T.MAX_LAYERS)
+    assert len(fam.xcol) == T.MAX_X
+    ms = T._model_struct(fam)
+    assert lib.sprk_train_workspace_bytes(C.byref(ms), 40, 16, 8) > 0
+    field, value = LIMIT_STRUCT[what]
+    if field == "width":
+        ms.width[3] = value
+    else:
+        setattr(ms, field, value)
+    assert lib.sprk_train_workspace_bytes(C.byref(ms), 40, 16, 8) == 0
+    rc = lib.sprk_train_fit(C.byref(ms), None, None, None, None, 40, 16, 8, 1, None, 0.1, 0.001, 1e-7, None, None, None, None, None, None, 0, None)
+    assert rc == L.EINVAL
+    assert b"bad model (need 1..%d id columns, 1..%d hidden layers of 1..%d units, 1..%d input rows" % (T.MAX_COLS, T.MAX_LAYERS, T.MAX_WIDTH, T.MAX_X) in lib.sprk_last_error()
+
+
 def test_families_of_the_two_models():
     ncf = T.family_of(M.NeuralCF(seed=1))
     assert ncf.xcol == [0] * 10 + [1] * 10 and ncf.xsub == list(range(10)) * 2 and ncf.n_dense == 0 and ncf.widths == [10, 10]

@@ -187,6 +187,29 @@ def test_limits_raise(kw):
         TFC.family(**kw)
 
 
+@pytest.mark.parametrize("field,value", [("n_fields", TF.MAX_FIELDS + 1), ("n_layers", TF.MAX_LAYERS + 1), ("width", TF.MAX_WIDTH + 1), ("proj_dim", TF.MAX_PROJ + 1),
+                                         ("emb_dim", TF.MAX_IN + 1), ("n_dense", TF.MAX_IN + 1)])
+def test_one_more_than_each_maximum_is_refused_by_the_library_in_words(lib, field, value):
+    """The other route of ``test_limits_raise``: a valid model with one field raised past its maximum has no workspace, and the fit is
+    refused before any device call in a message that names the limits."""
+    ms = TF._model_struct(TFC.family(hidden=(TF.MAX_WIDTH,) * TF.MAX_LAYERS))
+    assert lib.sprk_train_fm_workspace_bytes(C.byref(ms), 40, 16, 8) > 0
+    if field == "width":
+        ms.width[3] = value
+    else:
+        setattr(ms, field, value)
+    assert lib.sprk_train_fm_workspace_bytes(C.byref(ms), 40, 16, 8) == 0
+    rc = lib.sprk_train_fm_fit(C.byref(ms), None, None, None, None, 40, 16, 8, 1, None, 0.1, 0.001, 1e-7, None, None, None, None, None, None, 0, None)
+    assert rc == L.EINVAL
+    assert b"1..%d fields" % TF.MAX_FIELDS in lib.sprk_last_error() and b"1..%d hidden layers of 1..%d units, emb_dim 1..%d, 0..%d numerics" % (
+        TF.MAX_LAYERS, TF.MAX_WIDTH, TF.MAX_IN, TF.MAX_IN) in lib.sprk_last_error()
+    base = TFC.family()
+    more = {"n_fields": dict(fields=base.fields + [("x%d" % i, "id", 3) for i in range(value - len(base.fields))]), "n_layers": dict(hidden=[2] * value),
+            "width": dict(hidden=[value]), "proj_dim": dict(proj_dim=value), "emb_dim": dict(emb_dim=value), "n_dense": dict(n_dense=value)}[field]
+    with pytest.raises(ValueError, match="trainer_fm takes up to %d fields" % TF.MAX_FIELDS):
+        TF._check_family(base._replace(**more))
+
+
 def test_the_stated_maxima_are_inside_the_limits():
     for kw in (dict(proj_dim=TF.MAX_PROJ), dict(vocabs=(3,) * 8, kinds=("id",) * 8, proj_dim=TF.MAX_FLAT // 9), dict(hidden=(TF.MAX_WIDTH,) * TF.MAX_LAYERS)):
         fam = TFC.family(**kw)
