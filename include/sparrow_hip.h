@@ -533,6 +533,36 @@ int sprk_feature_eng(const int32_t* user_id, const int32_t* movie_id, const floa
                      int32_t* user_rows, uint8_t* user_has, int32_t user_pitch, int32_t* movie_rows, uint8_t* movie_has,
                      uint64_t* error_key, int64_t* n_kept, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- new ratings applied to a feature store on the device, equal to a rebuild ----
+ * Let R be the concatenation, in call order, of every ratings batch applied to one store and its state (the state of no ratings:
+ * user_count, ring_movie, ring_r2, movie_count, movie_sum, movie_sumsq, movie_flag all zero, user_last_ts INT64_MIN in every element;
+ * the tables of no ratings: user_has / movie_has 0 and every row the NA defaults, which is what sprk_feature_eng writes for
+ * n_ratings = 0).  After each call the first n_users / n_movies rows of user_rows, user_has, movie_rows, movie_has are byte for byte
+ * what sprk_feature_eng writes from R with the same movie table, n_vocab, hist_len and table sizes -- PROVIDED every new rating's
+ * timestamp is >= the latest timestamp of its user applied by an EARLIER call (rows of one call may come in any order).  The
+ * definition is sparrowrecsys_amd/featureeng.py update_host; DESIGN.md section 5.14 has the argument.
+ * State, device memory, owned by the caller and changed by this call alone: user_count [n_users] (ratings applied), user_last_ts
+ * [n_users], ring_movie / ring_r2 [n_users][100] (the user's last 100 ratings as movie id and 2 * rating, the rating at position p of
+ * the user's (timestamp, row in R) order in slot p % 100), movie_count / movie_sum / movie_sumsq [n_movies] (n, the sum of 2 * rating
+ * and of its square over all ratings), movie_flag [n_movies] (a rating of the movie sits at a user position >= 2: a kept sample names it).
+ * The rating columns, the movie table, n_vocab, hist_len, the tables and user_pitch are sprk_feature_eng's.  The caller keeps the sum of
+ * n_new over all calls below 2^31 - 1.
+ * `error_key` is ONE caller-provided device word, set to ~0 before the call: the first kernel atomicMins (kind << 32 | row of this
+ * batch) into it, kinds 1 - 3 as for sprk_feature_eng and 4 = timestamp older than the user's latest; it writes nothing else, and every
+ * later kernel returns at once when the word is set: then NO byte of the state or of the tables has changed.
+ * The workspace is sprk_store_update_workspace_bytes(n_new, n_users, n_movies) bytes, 16-byte aligned (0 for sizes the call rejects).
+ * 0 <= n_new < 2^31 - 1, 0 <= n_users < 2^31 - 1, n_movies >= 0, 1 <= hist_len <= 100, 0 <= n_vocab <= 32, user_pitch >= hist_len + 8, no
+ * NULL or misaligned pointer, a sufficient workspace: anything else returns SPRK_EINVAL BEFORE any device call.  Asynchronous on
+ * `stream`: no synchronisation, no memory owned by the library; integer sums only, so the result is a function of the input alone. */
+size_t sprk_store_update_workspace_bytes(int64_t n_new, int32_t n_users, int32_t n_movies);
+int sprk_store_update(const int32_t* user_id, const int32_t* movie_id, const float* rating, const int64_t* timestamp, int64_t n_new,
+                      int32_t n_users, int32_t n_movies, const int32_t* movie_year, const int32_t* movie_genre3, const uint32_t* movie_genre_mask,
+                      int32_t n_vocab, int32_t hist_len,
+                      uint32_t* user_count, int64_t* user_last_ts, int32_t* ring_movie, uint8_t* ring_r2,
+                      uint32_t* movie_count, uint64_t* movie_sum, uint64_t* movie_sumsq, uint8_t* movie_flag,
+                      int32_t* user_rows, uint8_t* user_has, int32_t user_pitch, int32_t* movie_rows, uint8_t* movie_has,
+                      uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The workgroups (of 256 threads) that the ratings pipelines and the trainers launch for a loop over `items` elements:
  * max(1, ceil(items / 256)), at most 2048; every such loop strides by the grid, and the work queues (sprk_als_fit's half sweeps,
  * sprk_user_emb's sums) are capped likewise.  SPRK_FE_MAX_GRID = an integer in [1, 2048], read at each call, lowers the cap (anything

@@ -37,7 +37,8 @@ EXPORTED_SYMBOLS = [
     "sprk_pack_columns", "sprk_pack_columns_device", "sprk_pack_last_route", "sprk_set_many_streams", "sprk_set_many_batches", "sprk_emb_rank",
     "sprk_emb_topk", "sprk_emb_topk_workspace_bytes", "sprk_join_features", "sprk_rank_scores",
     "sprk_metrics_state_bytes", "sprk_metrics_reset", "sprk_metrics_update",
-    "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_segments_grid", "sprk_user_emb_workspace_bytes", "sprk_user_emb",
+    "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_store_update_workspace_bytes", "sprk_store_update", "sprk_segments_grid",
+    "sprk_user_emb_workspace_bytes", "sprk_user_emb",
     "sprk_catalog_build_workspace_bytes", "sprk_catalog_build", "sprk_catalog_similar",
     "sprk_als_workspace_bytes", "sprk_als_fit", "sprk_als_predict", "sprk_als_topk_workspace_bytes", "sprk_als_topk",
     "sprk_item_sequences_workspace_bytes", "sprk_item_sequences", "sprk_item_walks_workspace_bytes", "sprk_item_walks",
@@ -297,6 +298,12 @@ def load_library():
                                          vp, vp, vp, vp, vp, vp, vp, vp, vp,                             # the sample columns
                                          vp, vp, i32, vp, vp,                                            # the store's tables (or NULL)
                                          vp, vp, vp, sz, vp]                                             # error word, sample count, workspace, stream
+        lib.sprk_store_update_workspace_bytes.argtypes = [C.c_int64, i32, i32]
+        lib.sprk_store_update_workspace_bytes.restype = sz
+        lib.sprk_store_update.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, i32, i32,     # ratings, sizes, movie table, n_vocab, hist_len
+                                          vp, vp, vp, vp, vp, vp, vp, vp,                                # the state: four arrays per user, four per movie
+                                          vp, vp, i32, vp, vp,                                           # the store's tables
+                                          vp, vp, sz, vp]                                                # error word, workspace, stream
         lib.sprk_segments_grid.argtypes = [C.c_int64]
         lib.sprk_segments_grid.restype = C.c_int64
         lib.sprk_user_emb_workspace_bytes.argtypes = [C.c_int64, i32]

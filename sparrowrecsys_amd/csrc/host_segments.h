@@ -1,4 +1,4 @@
-// host_segments.h -- the host side of k_segments.h, shared by the five entry points of sparrow_feature_eng.hip (api_feature_eng.h,
+// host_segments.h -- the host side of k_segments.h, shared by the entry points of sparrow_feature_eng.hip (api_feature_eng.h, api_store_update.h,
 // api_user_emb.h, api_catalog.h, api_als.h, api_item2vec.h): the sort capacity and the grids, the workspace carver and the workspace check, seg_scan
 // (counts -> offsets) and seg_sort (every segment of one side by its key).  Everything is enqueued on the caller's stream.
 namespace {

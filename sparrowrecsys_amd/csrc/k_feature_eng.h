@@ -96,9 +96,62 @@ __device__ inline unsigned long long fe_spread8(unsigned b) {
     return ((x + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;
 }
 
-// One thread per sorted position.  The workgroup's FE_THREADS positions and the FE_WINDOW before them sit in LDS (movie, genre mask,
-// 2 * rating); a thread walks its window backwards: most recent first, which is the order of userRatedMovie1.. .  The 32 genre counters
+// What a window is read from: entry i of the walk gives 2 * rating, and for a positive rating its movie and the movie's genre mask.
+// Here the workgroup's LDS image (k_fe_window); k_store_update.h has the other one, a user's ring and its new ratings.
+struct FeLdsWindow {
+    const int* movie_;
+    const unsigned* mask_;
+    const unsigned char* r2_;
+    __device__ unsigned r2(long long i) const { return r2_[i]; }
+    __device__ int movie(long long i) const { return movie_[i]; }
+    __device__ unsigned mask(long long i) const { return mask_[i]; }
+};
+
+// One window, walked backwards over the entries last .. first of `w` (most recent first, which is the order of userRatedMovie1..):
+// S and Q of 2 * rating, the first H positive movies to hist[0 .. H) (0 where there are fewer), and top[0 .. 5) = the five greatest keys
+// count << 5 | (31 - dictionary id) among the genres with count > 0 (count desc, dictionary id asc; 0 = none).  The 32 genre counters
 // (<= 100 each) are bytes of four 64-bit registers.
+template <class Window>
+__device__ inline void fe_window_fold(const Window w, long long last, long long first, int H, int* __restrict__ hist, unsigned* S_out, unsigned* Q_out, unsigned* top) {
+    unsigned S = 0, Q = 0;
+    int n_pos = 0;
+    unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    for (long long i = last; i >= first; --i) {
+        const unsigned r2 = w.r2(i);
+        S += r2; Q += r2 * r2;
+        if (r2 >= FE_POSITIVE_R2) {
+            if (n_pos < H) hist[n_pos] = w.movie(i);
+            ++n_pos;
+            const unsigned g = w.mask(i);
+            c0 += fe_spread8(g & 255u); c1 += fe_spread8((g >> 8) & 255u); c2 += fe_spread8((g >> 16) & 255u); c3 += fe_spread8(g >> 24);
+        }
+    }
+    for (int k = n_pos; k < H; ++k) hist[k] = 0;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) top[k] = 0;
+#pragma unroll
+    for (int g = 0; g < 32; ++g) {
+        const unsigned long long cw = g < 8 ? c0 : g < 16 ? c1 : g < 24 ? c2 : c3;
+        const unsigned c = (unsigned)(cw >> ((g & 7) * 8)) & 255u;
+        unsigned key = c ? (c << 5 | (unsigned)(31 - g)) : 0u;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {                                          // kept sorted by insertion
+            const unsigned hi = top[k] > key ? top[k] : key;
+            key = top[k] > key ? key : top[k];
+            top[k] = hi;
+        }
+    }
+    *S_out = S; *Q_out = Q;
+}
+
+// userGenre of a key of fe_window_fold's top five: a genre outside the vocabulary holds its place as -1
+__device__ inline int fe_top_genre(unsigned key, int n_vocab) {
+    const int id = 31 - (int)(key & 31u);
+    return (key && id < n_vocab) ? id : -1;
+}
+
+// One thread per sorted position.  The workgroup's FE_THREADS positions and the FE_WINDOW before them sit in LDS (movie, genre mask,
+// 2 * rating); a thread folds its window with fe_window_fold.
 __global__ __launch_bounds__(FE_THREADS) void k_fe_window(const unsigned* __restrict__ seg_off, const unsigned* __restrict__ kept_off, int n_users,
                                                           const long long* __restrict__ seg_ts, const int* __restrict__ seg_row, const int* __restrict__ seg_user,
                                                           const int* __restrict__ movie, const float* __restrict__ rating,
@@ -133,34 +186,8 @@ __global__ __launch_bounds__(FE_THREADS) void k_fe_window(const unsigned* __rest
     const int me = (int)(pos - lo);
     const int first = (int)((pos - FE_WINDOW > start ? pos - FE_WINDOW : start) - lo);
     unsigned S = 0, Q = 0;
-    int n_pos = 0;
-    unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-    int* hist = out_hist + j * (size_t)H;
-    for (int i = me - 1; i >= first; --i) {
-        const unsigned r2 = s_r2[i];
-        S += r2; Q += r2 * r2;
-        if (r2 >= FE_POSITIVE_R2) {
-            if (n_pos < H) hist[n_pos] = s_movie[i];
-            ++n_pos;
-            const unsigned g = s_mask[i];
-            c0 += fe_spread8(g & 255u); c1 += fe_spread8((g >> 8) & 255u); c2 += fe_spread8((g >> 16) & 255u); c3 += fe_spread8(g >> 24);
-        }
-    }
-    for (int k = n_pos; k < H; ++k) hist[k] = 0;
-    // top five of (count desc, dictionary id asc) among count > 0: keys count << 5 | (31 - id), kept sorted by insertion
-    unsigned top[5] = {0, 0, 0, 0, 0};
-#pragma unroll
-    for (int g = 0; g < 32; ++g) {
-        const unsigned long long w = g < 8 ? c0 : g < 16 ? c1 : g < 24 ? c2 : c3;
-        const unsigned c = (unsigned)(w >> ((g & 7) * 8)) & 255u;
-        unsigned key = c ? (c << 5 | (unsigned)(31 - g)) : 0u;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const unsigned hi = top[k] > key ? top[k] : key;
-            key = top[k] > key ? key : top[k];
-            top[k] = hi;
-        }
-    }
+    unsigned top[5];
+    fe_window_fold(FeLdsWindow{s_movie, s_mask, s_r2}, (long long)me - 1, (long long)first, H, out_hist + j * (size_t)H, &S, &Q, top);
     const int row = seg_row[pos], m = s_movie[me];
     const unsigned r2 = s_r2[me];
     const int count = me - first;
@@ -174,8 +201,7 @@ __global__ __launch_bounds__(FE_THREADS) void k_fe_window(const unsigned* __rest
     for (int k = 0; k < 3; ++k) og[k] = mv_genre3[(size_t)m * 3 + k];
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        const int id = 31 - (int)(top[k] & 31u);
-        og[3 + k] = (top[k] && id < n_vocab) ? id : -1;                        // a genre outside the vocabulary holds its place as -1
+        og[3 + k] = fe_top_genre(top[k], n_vocab);
     }
     float* od = out_dense + j * 7;
     const float* md = mv_dense + (size_t)m * 4;

@@ -1,6 +1,7 @@
 // k_segments.h -- counts per id -> segment offsets, and every segment sorted by a 64-bit key with a 32-bit payload: the device code
-// that the five ratings pipelines of sparrow_feature_eng.hip share.  host_segments.h launches it (seg_scan, seg_sort).
+// that the ratings pipelines of sparrow_feature_eng.hip share.  host_segments.h launches it (seg_scan, seg_sort).
 //   feature engineering (k_feature_eng.h)  segments per user, key (timestamp, input row); the scan with its `kept` half
+//   store updates (k_store_update.h)       segments per user of the NEW ratings, key (timestamp, row in the batch)
 //   user embeddings (k_user_emb.h)         segments per user, key (input row, item row), the sort behind the `ungrouped` word
 //   the catalogue (k_catalog.h)            segments per movie, behind the word likewise, and the 2 (G + 1) lists; fe_block_scan in k_cat_similar
 //   ALS (k_als.h)                          segments per user and per movie

@@ -4,7 +4,9 @@
 //   the movie catalogue                                        k_catalog.h, api_catalog.h: sprk_catalog_build_workspace_bytes / sprk_catalog_build / sprk_catalog_similar
 //   ALS collaborative filtering                                k_als.h, api_als.h: sprk_als_workspace_bytes / sprk_als_fit / sprk_als_predict
 //   item2vec: rating sequences and the skip-gram trainer       k_item2vec.h, api_item2vec.h: sprk_item_sequences / sprk_item_walks / sprk_skipgram_fit and their *_workspace_bytes
-// All five count per id, scan, scatter into per-id segments and sort every segment: k_segments.h has that device code and host_segments.h
+// and the unit that keeps the first one's store current:
+//   new ratings -> the feature store's rows, in place          k_store_update.h, api_store_update.h: sprk_store_update_workspace_bytes / sprk_store_update
+// All of them count per id, scan, scatter into per-id segments and sort every segment: k_segments.h has that device code and host_segments.h
 // its launches, the workspace carver and the workspace check.  A translation unit of its own, like
 // sparrow_metrics.hip: nothing here is used by the forward engine and nothing of the engine is used here.  Shares with the other units
 // only host_common.h (the thread's error string behind sprk_last_error, HIP_TRY, the roctx ranges), which opens the kernels' namespace
@@ -25,6 +27,7 @@
 #include "host_common.h"
 #include "k_segments.h"
 #include "k_feature_eng.h"
+#include "k_store_update.h"
 #include "k_user_emb.h"
 #include "k_catalog.h"
 #include "k_als.h"
@@ -36,6 +39,7 @@ using namespace sprk_dev;
 
 #include "host_segments.h"
 #include "api_feature_eng.h"
+#include "api_store_update.h"
 #include "api_user_emb.h"
 #include "api_catalog.h"
 #include "api_als.h"

@@ -33,8 +33,11 @@ equals ``float32("%.2f" % (h / 100))``.  Counts and ``releaseYear`` are ``float3
 Parity with the reference: the movie side and the rounding are pinned by the reference's own data (tests/test_featureeng.py); the
 reference does not ship ``ratings.csv``, so the user windows are pinned by this definition and hand-worked examples.
 
-Out of scope: feeding the device-resident samples straight into ``evaluate_device`` (use ``.to_host()``), and updating an existing
-store incrementally from new ratings.
+New ratings are applied to an existing store by :func:`update_host` (the definition) and :func:`update_device` (``sprk_store_update``,
+csrc/k_store_update.h): the store's tables afterwards are byte for byte the tables built from all ratings applied so far, given
+that a user's new ratings are not older than the user's latest.  They keep a :class:`StoreState`.
+
+Out of scope: feeding the device-resident samples straight into ``evaluate_device`` (use ``.to_host()``).
 """
 from __future__ import annotations
 
@@ -55,6 +58,7 @@ _ID_LIMIT = (1 << 31) - 1
 _JAVA_BLANKS = "".join(chr(c) for c in range(33))          # String.trim strips every char <= U+0020
 DENSE_KEYS = ["releaseYear", "movieRatingCount", "movieAvgRating", "movieRatingStddev", "userRatingCount", "userAvgRating", "userRatingStddev"]
 ERR_USER, ERR_MOVIE, ERR_RATING = 1, 2, 3                   # the device error word's kinds, in the order the host checks them
+ERR_OLDER = 4                                               # (updates only: a rating older than its user's latest applied one)
 
 # year [n] int32, genre [n, 3] int32 (vocabulary index or -1), mask [n] uint32 (bit g = dictionary id g), has [n] uint8, dictionary [str];
 # row = movieId; a movie the table does not hold: 1990, -1, 0, 0
@@ -220,7 +224,7 @@ def _rating_columns(ratings):
 
 def _error_message(kind: int, row: int) -> str:
     what = {ERR_USER: "userId outside the user table", ERR_MOVIE: "movieId outside the movie table",
-            ERR_RATING: "rating off the half-star scale 0, 0.5 .. 10"}[kind]
+            ERR_RATING: "rating off the half-star scale 0, 0.5 .. 10", ERR_OLDER: "older than its user's latest rating"}[kind]
     return "ratings row %d: %s" % (row, what)
 
 
@@ -231,11 +235,19 @@ def _half_stars(r: np.ndarray) -> np.ndarray:
     return np.where(ok, np.where(ok, t, 0).astype(np.int64), -1)
 
 
-def _validate(u, m, r2, n_users, n_movies):
-    """Raises the ValueError the device's error word names: the lowest kind, then the first input row."""
-    for kind, bad in ((ERR_USER, (u < 0) | (u >= n_users)), (ERR_MOVIE, (m < 0) | (m >= n_movies)), (ERR_RATING, r2 < 0)):
+def _validate(u, m, r2, n_users, n_movies, older=None):
+    """Raises the ValueError the device's error word names: the lowest kind, then the first input row.  ``older``: an update's rows
+    that precede their user's latest rating."""
+    checks = [(ERR_USER, (u < 0) | (u >= n_users)), (ERR_MOVIE, (m < 0) | (m >= n_movies)), (ERR_RATING, r2 < 0)]
+    for kind, bad in checks if older is None else checks + [(ERR_OLDER, older)]:
         if bad.any():
             raise ValueError(_error_message(kind, int(np.flatnonzero(bad)[0])))
+
+
+def _greatest_id(col) -> int:
+    """The greatest id of a column (a numpy array or a tensor) that can index a table, -1 for none."""
+    ok = (col >= 0) & (col < _ID_LIMIT)
+    return int(col[ok].max()) if bool(ok.any()) else -1
 
 
 def _table_sizes(u, m, table: MovieTable, n_users, n_movies):
@@ -350,6 +362,33 @@ class DeviceSamples:
         return FeatureStore._from_device_tables(self._store_tensors, self.hist_len, self.device)
 
 
+def _device_rating_columns(ratings, dev):
+    """-> userId, movieId (int32), rating (float32), timestamp (int64) as contiguous tensors on ``dev``, their length, and the greatest
+    userId and movieId where the columns came from the host (-1 for none; None for device tensors, which are used where they are)."""
+    import torch
+    if isinstance(ratings, Mapping) and all(hasattr(ratings.get(k), "detach") for k in RATING_KEYS):
+        cols = [ratings[k].detach().to(dev) for k in RATING_KEYS]
+        if not all(c.ndim == 1 and c.numel() == cols[0].numel() for c in cols):
+            raise ValueError("the ratings columns differ in length")
+        if any(c.dtype.is_floating_point for c in (cols[0], cols[1], cols[3])):
+            raise TypeError("userId, movieId and timestamp must be integer tensors")
+        # (an id beyond int32 must not wrap into range: it becomes -1, which the kernel reports)
+        ids = [torch.where((c < 0) | (c >= _ID_LIMIT), torch.full_like(c, -1), c).to(torch.int32).contiguous() for c in cols[:2]]
+        u_d, m_d, r_d, t_d = ids[0], ids[1], cols[2].to(torch.float32).contiguous(), cols[3].to(torch.int64).contiguous()
+        n, greatest = u_d.numel(), None
+    else:
+        u, m, r, t = _rating_columns(ratings)
+        n = len(u)
+        clip = lambda a: np.where((a < 0) | (a >= _ID_LIMIT), -1, a).astype(np.int32)
+        u, m = clip(u), clip(m)
+        greatest = (int(u.max()), int(m.max())) if n else (-1, -1)
+        u_d, m_d = torch.from_numpy(u).to(dev), torch.from_numpy(m).to(dev)
+        r_d, t_d = torch.from_numpy(np.ascontiguousarray(r)).to(dev), torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+    if n >= _ID_LIMIT:
+        raise ValueError("at most 2^31 - 2 ratings")
+    return u_d, m_d, r_d, t_d, n, greatest
+
+
 def build(ratings, movies, hist_len: int = 5, device=None, n_users: Optional[int] = None, n_movies: Optional[int] = None) -> DeviceSamples:
     """Samples and store on the device.  ``ratings``: a CSV path or ``{userId, movieId, rating, timestamp}`` columns, numpy arrays or
     device tensors (tensors on ``device`` are used where they are); ``movies``: what :func:`movie_table` takes.  ``n_users`` /
@@ -368,27 +407,10 @@ def build(ratings, movies, hist_len: int = 5, device=None, n_users: Optional[int
         raise RuntimeError("featureeng.build needs a HIP device: no HIP device is visible (samples_host is the host definition)")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     table = movie_table(movies)
-    if isinstance(ratings, Mapping) and all(hasattr(ratings.get(k), "detach") for k in RATING_KEYS):
-        cols = [ratings[k].detach().to(dev) for k in RATING_KEYS]
-        if not all(c.ndim == 1 and c.numel() == cols[0].numel() for c in cols):
-            raise ValueError("the ratings columns differ in length")
-        if any(c.dtype.is_floating_point for c in (cols[0], cols[1], cols[3])):
-            raise TypeError("userId, movieId and timestamp must be integer tensors")
-        # (an id beyond int32 must not wrap into range: it becomes -1, which the kernel reports)
-        ids = [torch.where((c < 0) | (c >= _ID_LIMIT), torch.full_like(c, -1), c).to(torch.int32).contiguous() for c in cols[:2]]
-        u_d, m_d, r_d, t_d = ids[0], ids[1], cols[2].to(torch.float32).contiguous(), cols[3].to(torch.int64).contiguous()
-        n = u_d.numel()
-        um, mm = (int(u_d.max()), int(m_d.max())) if n and (n_users is None or n_movies is None) else (-1, -1)
-    else:
-        u, m, r, t = _rating_columns(ratings)
-        n = len(u)
-        clip = lambda a: np.where((a < 0) | (a >= _ID_LIMIT), -1, a).astype(np.int32)
-        u, m = clip(u), clip(m)
-        um, mm = (int(u.max()), int(m.max())) if n else (-1, -1)
-        u_d, m_d = torch.from_numpy(u).to(dev), torch.from_numpy(m).to(dev)
-        r_d, t_d = torch.from_numpy(np.ascontiguousarray(r)).to(dev), torch.from_numpy(np.ascontiguousarray(t)).to(dev)
-    if n >= _ID_LIMIT:
-        raise ValueError("at most 2^31 - 2 ratings")
+    u_d, m_d, r_d, t_d, n, greatest = _device_rating_columns(ratings, dev)
+    if greatest is None:
+        greatest = (int(u_d.max()), int(m_d.max())) if n and (n_users is None or n_movies is None) else (-1, -1)
+    um, mm = greatest
     n_users, n_movies = _table_sizes(np.array([um]), np.array([mm]), table, n_users, n_movies)
     table = _padded(table, n_movies)
     pitch = user_pitch(hist_len)
@@ -418,3 +440,190 @@ def build(ratings, movies, hist_len: int = 5, device=None, n_users: Optional[int
     cut = lambda x: x[:kept]
     columns = _columns_dict(hist_len, cut(o_user), cut(o_movie), cut(o_rating), cut(o_ts), cut(o_label), cut(o_src), cut(o_genres), cut(o_hist), cut(o_dense))
     return DeviceSamples(columns, kept, hist_len, (user_rows, user_has, movie_rows, movie_has), dev)
+
+
+# ---- new ratings applied to an existing store ----
+TS_MIN = int(np.iinfo(np.int64).min)
+# name, dtype, per-row shape; the first four have one row per user, the others one per movie
+STATE_ARRAYS = [("user_count", np.uint32, ()), ("user_last_ts", np.int64, ()), ("ring_movie", np.int32, (WINDOW,)), ("ring_r2", np.uint8, (WINDOW,)),
+                ("movie_count", np.uint32, ()), ("movie_sum", np.uint64, ()), ("movie_sumsq", np.uint64, ()), ("movie_flag", np.uint8, ())]
+TABLE_NAMES = ["user_rows", "user_has", "movie_rows", "movie_has"]
+
+
+class StoreState:
+    """What an updatable store keeps next to its four tables so that new ratings can be applied without the old ones.
+
+    Per user: ``user_count`` (ratings applied), ``user_last_ts`` (the latest timestamp applied, ``TS_MIN`` for none), ``ring_movie`` /
+    ``ring_r2`` ``[n_users, 100]``: the user's last 100 ratings as movie id and 2 * rating, the rating at position p of the user's
+    ``(timestamp, input row)`` order in slot ``p % 100``.  Per movie: ``movie_count`` / ``movie_sum`` / ``movie_sumsq`` (n, S, Q over all
+    ratings) and ``movie_flag`` (a rating of the movie sits at a user position >= 2: a kept sample names it).  ``table``: the movie table
+    padded to ``n_movies``.  ``tables``: the store's ``user_rows, user_has, movie_rows, movie_has``, changed in place.  ``n_ratings``: all
+    ratings applied.  On the host (``device`` None) everything is a numpy array of exactly ``n_users`` / ``n_movies`` rows; on a device
+    everything is a tensor with one spare row (an empty array still has an address), and ``movie_dev`` holds the movie table's columns."""
+
+    def __init__(self, table, n_users, n_movies, hist_len, arrays, tables, device=None, movie_dev=None):
+        self.table, self.n_users, self.n_movies, self.hist_len = table, int(n_users), int(n_movies), int(hist_len)
+        self.arrays, self.tables, self.device, self.movie_dev = dict(arrays), tuple(tables), device, movie_dev
+        self.n_ratings = 0
+
+    def __getattr__(self, name):                                               # state.user_count is state.arrays["user_count"]
+        arrays = self.__dict__.get("arrays", {})
+        if name in arrays:
+            return arrays[name]
+        raise AttributeError(name)
+
+    def to_host(self) -> dict:
+        """The state arrays and the tables as numpy arrays of ``n_users`` / ``n_movies`` rows (copies), by name."""
+        rows = [self.n_users] * 4 + [self.n_movies] * 4 + [self.n_users] * 2 + [self.n_movies] * 2
+        named = [(k, self.arrays[k], dt) for k, dt, _ in STATE_ARRAYS] + [(k, v, None) for k, v in zip(TABLE_NAMES, self.tables)]
+        out = {}
+        for (k, v, dt), n in zip(named, rows):
+            a = v.cpu().numpy() if hasattr(v, "detach") else v
+            out[k] = (a if dt is None else a.view(dt))[:n].copy()              # (a device array stores an unsigned word as the signed type of its width)
+        return out
+
+    def state_bytes(self) -> int:
+        """Bytes of the state arrays, the tables not counted."""
+        return sum((self.n_users if k < 4 else self.n_movies) * int(np.prod(shape, dtype=np.int64)) * np.dtype(dt).itemsize
+                   for k, (_, dt, shape) in enumerate(STATE_ARRAYS))
+
+
+def empty_state(movies, n_users: int, n_movies: int, hist_len: int = 5, device=None) -> StoreState:
+    """The state and the tables of no ratings: what ``sprk_feature_eng`` writes for an empty ``ratings.csv``.  ``device`` None or
+    ``"cpu"``: on the host."""
+    from .featurestore import MOVIE_PITCH, user_pitch
+    if not 1 <= hist_len <= WINDOW:
+        raise ValueError("hist_len = %d outside [1, %d]" % (hist_len, WINDOW))
+    table = movie_table(movies)
+    n_users, n_movies = _table_sizes(np.array([-1]), np.array([-1]), table, int(n_users), int(n_movies))
+    table = _padded(table, n_movies)
+    pitch = user_pitch(hist_len)
+    if device is None or str(device) == "cpu":
+        arrays = {k: np.zeros((n_users if i < 4 else n_movies,) + shape, dtype=dt) for i, (k, dt, shape) in enumerate(STATE_ARRAYS)}
+        arrays["user_last_ts"][:] = TS_MIN
+        user_rows, movie_rows = np.zeros((n_users, pitch), np.int32), np.zeros((n_movies, MOVIE_PITCH), np.int32)
+        user_rows[:, hist_len:hist_len + 5] = -1
+        movie_rows[:, :3] = -1
+        return StoreState(table, n_users, n_movies, hist_len, arrays, (user_rows, np.zeros(n_users, np.uint8), movie_rows, np.zeros(n_movies, np.uint8)))
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("an updatable store on a device needs a HIP device: none is visible (device=\"cpu\" runs the host definition)")
+    dev = torch.device(device)
+    storage = {np.uint32: torch.int32, np.uint64: torch.int64, np.int32: torch.int32, np.int64: torch.int64, np.uint8: torch.uint8}   # (the same bits)
+    arrays = {k: torch.zeros((n_users + 1 if i < 4 else n_movies + 1,) + shape, dtype=storage[dt], device=dev) for i, (k, dt, shape) in enumerate(STATE_ARRAYS)}
+    arrays["user_last_ts"][:n_users] = TS_MIN
+    user_rows, movie_rows = torch.zeros((n_users + 1, pitch), dtype=torch.int32, device=dev), torch.zeros((n_movies + 1, MOVIE_PITCH), dtype=torch.int32, device=dev)
+    user_rows[:n_users, hist_len:hist_len + 5] = -1
+    movie_rows[:n_movies, :3] = -1
+    tables = (user_rows, torch.zeros(n_users + 1, dtype=torch.uint8, device=dev), movie_rows, torch.zeros(n_movies + 1, dtype=torch.uint8, device=dev))
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    return StoreState(table, n_users, n_movies, hist_len, arrays, tables, dev, (up(table.year), up(table.genre), up(table.mask.view(np.int32))))
+
+
+def _user_row(movies, r2s, table: MovieTable, hist_len: int, pitch: int) -> np.ndarray:
+    """The store's user row of one window, ``movies`` / ``r2s`` in position order (oldest first): history | userGenre1..5 | count avg
+    stddev | zeros -- the columns of the sample whose window this is."""
+    n, s, q = len(r2s), int(r2s.sum()), int((r2s * r2s).sum())
+    liked = movies[r2s >= POSITIVE_R2][::-1]                                   # most recent first
+    counts = [0] * MAX_GENRES
+    for bits in table.mask[liked].tolist():
+        for g in range(MAX_GENRES):
+            counts[g] += (bits >> g) & 1
+    top = sorted((g for g in range(MAX_GENRES) if counts[g]), key=lambda g: (-counts[g], g))[:5]    # count desc, dictionary id asc
+    row = np.zeros(pitch, dtype=np.int32)
+    row[:min(hist_len, len(liked))] = liked[:hist_len]
+    row[hist_len:hist_len + 5] = [g if g < S.N_GENRES else -1 for g in top] + [-1] * (5 - len(top))
+    row[hist_len + 5:hist_len + 8] = np.array([np.float32(n), hundredths(avg_h(n, s)), hundredths(sd_h(n, s, q))], dtype=np.float32).view(np.int32)
+    return row
+
+
+def update_host(state: StoreState, ratings) -> int:
+    """The definition of an update: ``ratings`` (what :func:`build` takes) applied to ``state`` and its tables in place, in numpy and
+    integers; returns their number.  Afterwards the tables are the tables of ``samples_host`` over ALL ratings applied, in call order,
+    provided no new rating is older than the latest rating of its user applied by an earlier call -- then the new ratings sort after
+    the old ones of their user (a timestamp tie goes by input row), so no old position moves: the user row is the window before the new
+    last position, read from the ring and the sorted new ratings; a movie row is a function of the movie's n / S / Q and of its flag.
+    Errors are ``ValueError`` as for :func:`samples_host`, and "older than its user's latest rating"; an error leaves every byte as it was."""
+    from .featurestore import user_pitch
+    if state.device is not None:
+        raise TypeError("update_host takes a host state (update_device applies ratings to a state on a device)")
+    u, m, r, t = _rating_columns(ratings)
+    n = len(u)
+    if state.n_ratings + n >= _ID_LIMIT:
+        raise ValueError("at most 2^31 - 2 ratings")
+    r2 = _half_stars(r)
+    known = (u >= 0) & (u < state.n_users)
+    older = np.zeros(n, dtype=bool)
+    older[known] = t[known] < state.user_last_ts[u[known]]
+    _validate(u, m, r2, state.n_users, state.n_movies, older)
+    if n == 0:
+        return 0
+    table, H, pitch = state.table, state.hist_len, user_pitch(state.hist_len)
+    user_rows, user_has, movie_rows, movie_has = state.tables
+    state.arrays["movie_count"] += np.bincount(m, minlength=state.n_movies).astype(np.uint32)
+    state.arrays["movie_sum"] += np.bincount(m, weights=r2, minlength=state.n_movies).astype(np.uint64)            # (exact in float64: below 2^53)
+    state.arrays["movie_sumsq"] += np.bincount(m, weights=r2 * r2, minlength=state.n_movies).astype(np.uint64)
+    order = np.lexsort((np.arange(n), t, u))
+    us = u[order]
+    starts = np.flatnonzero(np.concatenate([[True], us[1:] != us[:-1]]))
+    for lo, hi in zip(starts, np.concatenate([starts[1:], [n]])):
+        rows, user = order[lo:hi], int(us[lo])                                 # the user's new ratings by (timestamp, row in the batch)
+        k, old = int(hi - lo), int(state.user_count[user])
+        mv, rr = m[rows], r2[rows]
+        state.movie_flag[mv[max(0, 2 - old):]] = 1                             # new position j is the user's position old + j
+        last = old + k - 1
+        if last >= 2:                                                          # the last kept sample: the window before the last position
+            pos = np.arange(max(0, last - WINDOW), last)
+            new = np.clip(pos - old, 0, k - 1)
+            w_movie = np.where(pos < old, state.ring_movie[user, pos % WINDOW], mv[new])
+            w_r2 = np.where(pos < old, state.ring_r2[user, pos % WINDOW], rr[new]).astype(np.int64)
+            user_rows[user] = _user_row(w_movie, w_r2, table, H, pitch)
+            user_has[user] = 1
+        tail = np.arange(max(0, k - WINDOW), k)
+        state.ring_movie[user, (old + tail) % WINDOW] = mv[tail]
+        state.ring_r2[user, (old + tail) % WINDOW] = rr[tail]
+        state.user_count[user] = old + k
+        state.user_last_ts[user] = t[rows[-1]]
+    for movie in np.unique(m).tolist():
+        cnt, sm, sq = int(state.movie_count[movie]), int(state.movie_sum[movie]), int(state.movie_sumsq[movie])
+        if state.movie_flag[movie]:
+            movie_rows[movie, :3] = table.genre[movie]
+            movie_rows[movie, 3:7] = np.array([np.float32(table.year[movie]), np.float32(cnt), hundredths(avg_h(cnt, sm)), hundredths(sd_h(cnt, sm, sq))],
+                                              dtype=np.float32).view(np.int32)
+            movie_has[movie] = 1
+    state.n_ratings += n
+    return n
+
+
+def update_device(state: StoreState, ratings) -> int:
+    """:func:`update_host` on the device (``sprk_store_update``): the same bytes in the state and in the tables.  ``ratings`` as for
+    :func:`build`; tensors on the state's device are used where they are.  Everything is enqueued on the current stream; one host
+    synchronisation, for the error word."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib as L
+    if state.device is None:
+        raise TypeError("update_device takes a state on a device (update_host is the host definition)")
+    lib, dev = L.load_library(), state.device
+    u_d, m_d, r_d, t_d, n, _ = _device_rating_columns(ratings, dev)
+    if state.n_ratings + n >= _ID_LIMIT:
+        raise ValueError("at most 2^31 - 2 ratings")
+    if n == 0:
+        return 0
+    with torch.cuda.device(dev):
+        word = torch.tensor([-1], dtype=torch.int64, device=dev)               # the error word (~0)
+        ws_bytes = lib.sprk_store_update_workspace_bytes(n, state.n_users, state.n_movies)
+        ws = torch.empty(max(ws_bytes, 16) // 8 + 2, dtype=torch.int64, device=dev)   # (torch's allocations are 512-byte aligned)
+        p = lambda x: C.c_void_p(x.data_ptr())
+        user_rows, user_has, movie_rows, movie_has = state.tables
+        L.check(lib.sprk_store_update(p(u_d), p(m_d), p(r_d), p(t_d), n, state.n_users, state.n_movies, *(p(x) for x in state.movie_dev), S.N_GENRES, state.hist_len,
+                                      *(p(state.arrays[k]) for k, _, _ in STATE_ARRAYS),
+                                      p(user_rows), p(user_has), int(user_rows.shape[1]), p(movie_rows), p(movie_has),
+                                      p(word), p(ws), ws.numel() * 8, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        err = int(word.cpu().numpy()[0])                                       # the one synchronisation
+    if err != -1:
+        raise ValueError(_error_message((err >> 32) & 0xffffffff, err & 0xffffffff))
+    state.n_ratings += n
+    return n

@@ -206,6 +206,8 @@ class FeatureStore:
     ``n_users``, ``n_movies``, ``hist_len``, ``user_pitch``, ``movie_pitch`` (dwords) describe the tables; ``images`` is the host copy
     they were uploaded from (a :class:`RowImages`), ``user_layout`` / ``movie_layout`` map a column to its dword and role."""
 
+    _state = None                       # an updatable store's featureeng.StoreState (empty, from_ratings(updatable=True))
+
     def __init__(self, images: RowImages, device=None):
         self._images = images
         self.hist_len = int(images.hist_len)
@@ -252,12 +254,25 @@ class FeatureStore:
         return self
 
     @classmethod
-    def from_ratings(cls, ratings, movies, hist_len: int = 5, device=None, n_users: Optional[int] = None, n_movies: Optional[int] = None):
+    def from_ratings(cls, ratings, movies, hist_len: int = 5, device=None, n_users: Optional[int] = None, n_movies: Optional[int] = None,
+                     updatable: bool = False):
         """From ``ratings.csv`` and ``movies.csv`` (paths or columns, as ``featureeng.build`` takes them) without the reference's Spark
         job: the samples are computed on ``device`` and the tables written there (``sprk_feature_eng``).  ``device="cpu"`` builds the images
         from the host definition ``featureeng.samples_host``: no GPU involved, like the other constructors.  ``n_users`` / ``n_movies``
-        default to the greatest id of the RATINGS + 1 (the movie table's rows at least)."""
+        default to the greatest id of the RATINGS + 1 (the movie table's rows at least).  ``updatable=True``: the same tables, byte for
+        byte, as :meth:`empty` followed by :meth:`update`: the store keeps the state that later updates need, and its table sizes are
+        capacities."""
         from . import featureeng as FE
+        if updatable:
+            table = FE.movie_table(movies)
+            on_device = isinstance(ratings, Mapping) and all(hasattr(ratings.get(k), "detach") for k in FE.RATING_KEYS)
+            cols = ratings if on_device else dict(zip(FE.RATING_KEYS, FE._rating_columns(ratings)))
+            sized = n_users is not None and n_movies is not None
+            greatest = [np.array([-1 if sized else FE._greatest_id(cols[k])]) for k in ("userId", "movieId")]
+            n_users, n_movies = FE._table_sizes(greatest[0], greatest[1], table, n_users, n_movies)
+            store = cls.empty(table, n_users, n_movies, hist_len, device)
+            store.update(cols)
+            return store
         if device is not None and str(device) == "cpu":
             table = FE.movie_table(movies)
             u, m, _, _ = cols = FE._rating_columns(ratings)
@@ -276,6 +291,55 @@ class FeatureStore:
                           n_movies: Optional[int] = None):
         """``{id: {column: str-or-number}}`` maps, the shape of the ``uf:`` / ``mf:`` hashes (:func:`row_images_from_feature_maps`)."""
         return cls(row_images_from_feature_maps(user_maps, movie_maps, hist_len, n_users, n_movies), device)
+
+    @classmethod
+    def empty(cls, movies, n_users: int, n_movies: int, hist_len: int = 5, device=None):
+        """An updatable store with no ratings: no entry, every row the NA defaults.  ``movies``: what ``featureeng.movie_table`` takes;
+        ``n_users`` / ``n_movies`` are capacities that do not grow: an id beyond them in a later batch is :meth:`update`'s error.
+        ``device="cpu"``: the host images and the host definition of the update, no GPU involved."""
+        from . import featureeng as FE
+        if device is not None and str(device) == "cpu":
+            state = FE.empty_state(movies, n_users, n_movies, hist_len, "cpu")
+            self = cls(RowImages(*state.tables, int(hist_len)), "cpu")         # (the images ARE the state's tables: updated in place)
+        else:
+            import torch
+            if not torch.cuda.is_available():
+                raise RuntimeError("FeatureStore needs a HIP device (device=\"cpu\" keeps the host images only)")
+            dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+            state = FE.empty_state(movies, n_users, n_movies, hist_len, dev)
+            self = cls._from_device_tables(state.tables, hist_len, dev)
+        self._state = state
+        return self
+
+    @property
+    def updatable(self) -> bool:
+        """:meth:`update` applies new ratings to this store."""
+        return self._state is not None
+
+    @property
+    def n_ratings(self) -> int:
+        """The ratings an updatable store has been given so far, the ones it was built from included."""
+        if self._state is None:
+            raise RuntimeError("this FeatureStore does not count its ratings: it is not updatable")
+        return self._state.n_ratings
+
+    def update(self, ratings) -> int:
+        """Applies new ratings -- a CSV path or ``{userId, movieId, rating, timestamp}`` columns, numpy arrays or device tensors, which
+        are used where they are -- and returns their number.  Afterwards the four tables are byte for byte the tables of
+        ``from_ratings(R, ...)`` with the same table sizes, R = every batch this store has been given, in call order, PROVIDED no
+        rating is older than the latest rating of its user in an EARLIER batch (a nearline stream is in time order per user; the rows
+        of one batch may come in any order).  A rating that is older, an id beyond the tables or a rating off the half-star scale raises
+        ``ValueError`` naming the batch's row, and the store is as it was.  On a device: the kernels of ``sprk_store_update`` on the
+        current stream and one host synchronisation, for the error word; the tables are changed in place, so :meth:`tensors`, join plans
+        and engines made earlier stay valid, and the cached host image is dropped."""
+        from . import featureeng as FE
+        if self._state is None:
+            raise RuntimeError("this FeatureStore is not updatable: build it with FeatureStore.empty or from_ratings(..., updatable=True)")
+        if self._state.device is None:
+            return FE.update_host(self._state, ratings)
+        n = FE.update_device(self._state, ratings)
+        self._images = None
+        return n
 
     def tensors(self):
         """Device tensors ``(user_rows, user_has, movie_rows, movie_has)``."""
@@ -296,6 +360,8 @@ class FeatureStore:
         return self.n_users * (self.user_pitch * 4 + 1) + self.n_movies * (self.movie_pitch * 4 + 1)
 
     def close(self):
-        """Drops the device tables (the host images stay)."""
+        """Drops the device tables (the host images stay) and, with them, an updatable store's state on the device."""
+        if self._state is not None and self._state.device is not None:
+            self._state = None
         self._tensors = None
         self.device = None
