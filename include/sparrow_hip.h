@@ -497,6 +497,41 @@ int sprk_metrics_reset(void* state, size_t state_bytes, int32_t num_thresholds, 
 int sprk_metrics_update(void* state, size_t state_bytes, const float* scores, const void* labels, int32_t label_storage,
                         int64_t label_stride /* bytes */, int64_t n, void* stream);
 
+/* ---- the exact areas under the ROC and the PR curve, over every distinct score ----
+ * offline/spark/evaluate/Evaluator.scala of the reference reports BinaryClassificationMetrics' areaUnderROC and areaUnderPR: the areas
+ * over EVERY distinct score, not Keras' 200 thresholds.  sparrowrecsys_amd/metrics.py exact_auc_host defines every number (DESIGN.md
+ * section 5.15, with the rules read out of Spark 2.4 and the deviations); this call gives its bits from n float32 scores and their
+ * labels in device memory.  scores: any finite float32; the threshold of a score is its float32 value, -0.0 taken as +0.0.  labels as
+ * sprk_metrics_update takes them (label_storage, label_stride in bytes); a sample is positive iff label > 0.5.  Groups g = 1 .. G are
+ * the distinct thresholds in DESCENDING order, tp_g / fp_g the positives / negatives with a score >= the group's, P = tp_G, N = fp_G:
+ *   roc_numerator  = sum over g of neg_g (2 tp_{g-1} + pos_g), an integer (the rank statistic with ties at one half, times 2)
+ *   area_under_roc = (double)roc_numerator / (double)(2 P N); 1.0 when N = 0, else 0.0 when P = 0
+ *   pr_sum         = sum over g of (double)pos_g (prec_g + prec_{g-1}), prec_g = (double)tp_g / (double)(tp_g + fp_g), prec_0 := prec_1,
+ *                    added in runs of 1024 consecutive groups, each from +0.0 in group order, the run sums from +0.0 in run order
+ *   area_under_pr  = pr_sum / (double)(2 P); 0.0 when P = 0
+ * Every operation is rounded on its own; no floating-point atomic: the result is a function of the inputs alone, whatever the grid,
+ * the sort capacity, the bin width or the order of arrival.  The curve -- thresholds[g], tp[g], fp[g] (cumulative) for the G groups --
+ * goes to the three arrays, each of which may be NULL and otherwise holds n elements, of which the first n_groups are written.
+ * Errors are found before anything is computed: *error_key, which the caller sets to ~0 (= none), takes the LEAST of
+ * kind << 32 | row over the rows in error -- kind 1: the score is not finite; kind 2: a float label is not finite -- and every later
+ * kernel of the call returns at once, so result and the curve arrays keep what they held.  The caller reads the word.
+ * 1 <= n < 2^31 - 1.  The workspace is what the _workspace_bytes call reports for n (0 for an n outside the range), 16-byte
+ * aligned; rows go to bins by the leading _bin_bits(n) bits of their key (SPRK_EXACT_AUC_BIN_BITS = an integer in [1, 24], read at each call,
+ * overrides the rule), bins are sorted in LDS up to 4096 keys (SPRK_FE_SORT_CAP, below) and by chunks and merge passes beyond.
+ * NULL or misaligned pointers (result and error word 8 bytes), an n outside the range, an unknown storage, a bad stride, a short or
+ * misaligned workspace (the message names sprk_exact_auc_workspace_bytes) return SPRK_EINVAL BEFORE any device call.  Asynchronous on
+ * `stream`: no synchronisation, no memory owned by the library. */
+typedef struct {
+    int64_t n, n_pos, n_groups;
+    uint64_t roc_numerator;
+    double pr_sum, area_under_roc, area_under_pr;
+} sprk_exact_auc_result;
+size_t sprk_exact_auc_workspace_bytes(int64_t n);
+int32_t sprk_exact_auc_bin_bits(int64_t n);                 /* 0 for an n outside the range */
+int sprk_exact_auc(const float* scores, const void* labels, int32_t label_storage, int64_t label_stride /* bytes */, int64_t n,
+                   sprk_exact_auc_result* result, float* thresholds, uint32_t* tp, uint32_t* fp,
+                   uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- feature engineering on the device: ratings -> training samples and the feature store's rows ----
  * The arithmetic of the reference's Spark job (FeatureEngForRecModel.scala:21-130): label = rating >= 3.5; per movie over ALL ratings
  * count / average / sample stddev; per user, in (timestamp, input row) order, the window of the previous 100 ratings -- its size, average,

@@ -37,6 +37,7 @@ EXPORTED_SYMBOLS = [
     "sprk_pack_columns", "sprk_pack_columns_device", "sprk_pack_last_route", "sprk_set_many_streams", "sprk_set_many_batches", "sprk_emb_rank",
     "sprk_emb_topk", "sprk_emb_topk_workspace_bytes", "sprk_join_features", "sprk_rank_scores",
     "sprk_metrics_state_bytes", "sprk_metrics_reset", "sprk_metrics_update",
+    "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_exact_auc",
     "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_store_update_workspace_bytes", "sprk_store_update", "sprk_segments_grid",
     "sprk_user_emb_workspace_bytes", "sprk_user_emb",
     "sprk_catalog_build_workspace_bytes", "sprk_catalog_build", "sprk_catalog_similar",
@@ -73,6 +74,12 @@ METRICS_MAX_THRESHOLDS = 1024
 
 class JoinCol(C.Structure):
     _fields_ = [("source", C.c_int32), ("offset", C.c_int32), ("rule", C.c_int32), ("vocab", C.c_int32)]
+
+
+class ExactAucResult(C.Structure):
+    """sprk_exact_auc_result (include/sparrow_hip.h): seven 8-byte words."""
+    _fields_ = [("n", C.c_int64), ("n_pos", C.c_int64), ("n_groups", C.c_int64), ("roc_numerator", C.c_uint64),
+                ("pr_sum", C.c_double), ("area_under_roc", C.c_double), ("area_under_pr", C.c_double)]
 
 
 TRAIN_MAX_COLS, TRAIN_MAX_LAYERS, TRAIN_MAX_X, TRAIN_MAX_WIDTH = 16, 8, 256, 256
@@ -292,6 +299,11 @@ def load_library():
         lib.sprk_metrics_state_bytes.restype = sz
         lib.sprk_metrics_reset.argtypes = [vp, sz, i32, vp]
         lib.sprk_metrics_update.argtypes = [vp, sz, vp, vp, i32, C.c_int64, C.c_int64, vp]
+        lib.sprk_exact_auc_workspace_bytes.argtypes = [C.c_int64]
+        lib.sprk_exact_auc_workspace_bytes.restype = sz
+        lib.sprk_exact_auc_bin_bits.argtypes = [C.c_int64]
+        lib.sprk_exact_auc_bin_bits.restype = i32
+        lib.sprk_exact_auc.argtypes = [vp, vp, i32, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, sz, vp]   # scores, labels .. n, result, the curve, error word, workspace, stream
         lib.sprk_feature_eng_workspace_bytes.argtypes = [C.c_int64, i32, i32]
         lib.sprk_feature_eng_workspace_bytes.restype = sz
         lib.sprk_feature_eng.argtypes = [vp, vp, vp, vp, C.c_int64, i32, i32, vp, vp, vp, i32, i32,      # ratings, sizes, movie table, n_vocab, hist_len
@@ -344,7 +356,7 @@ def load_library():
         lib.sprk_train_fm_workspace_bytes.restype = sz
         lib.sprk_train_fm_fit.argtypes = [C.POINTER(TrainFmModel)] + lib.sprk_train_fit.argtypes[1:]             # sprk_train_fit's argument list
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_segments_grid", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_segments_grid", "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

@@ -10,12 +10,20 @@ way Keras computes them so that a reference user reads the same figures:
             These are approximations of the exact rank statistics by design (the exact ROC-AUC is ``exact_roc_auc``).
 Host-side numpy: these functions are the DEFINITION of every number.  ``DeviceMetrics`` keeps the same accumulators in device memory
 (``sprk_metrics_update``, csrc/k_metrics.h) and gives these functions' bits for everything that is a count -- accuracy and both AUCs --
-and the loss up to the order of a float64 sum; the exact rank statistic (``exact_roc_auc``) needs every score and stays on the host."""
+and the loss up to the order of a float64 sum.
+
+The exact areas over EVERY distinct score -- what the reference's Spark job reports (offline/spark/evaluate/Evaluator.scala:
+``BinaryClassificationMetrics.areaUnderROC()`` / ``areaUnderPR()``) -- are ``exact_auc_host``, the definition, and ``exact_auc_device``,
+which gives its bits from scores that lie in device memory (``sprk_exact_auc``, csrc/k_exact_auc.h).  Its ROC
+area is the rank statistic ``exact_roc_auc`` computes on the host, which stays as it is."""
 from __future__ import annotations
 
 import numpy as np
 
 EPS = 1e-7
+PR_RUN = 1024                                                     # groups of one run of the PR sum: part of exact_auc_host's definition
+EXACT_AUC_MAX_N = (1 << 31) - 2
+EXACT_ERR_SCORE, EXACT_ERR_LABEL = 1, 2
 
 
 def _confusion(labels: np.ndarray, preds: np.ndarray, num_thresholds: int = 200):
@@ -79,6 +87,224 @@ def exact_roc_auc(labels, preds) -> float:
     return float((ranks[labels].sum() - n_pos * (n_pos + 1) / 2.0) / (n_pos * n_neg))
 
 
+# ---- the exact areas over every distinct score: Spark's BinaryClassificationMetrics ----------------------------
+
+def exact_auc_error_message(kind: int, row: int) -> str:
+    what = {EXACT_ERR_SCORE: "score", EXACT_ERR_LABEL: "label"}.get(int(kind), "input")
+    return "exact AUC: the %s of row %d is not finite" % (what, int(row))
+
+
+class ExactAuc:
+    """What ``exact_auc_host`` and ``exact_auc_device`` return.  ``area_under_roc``, ``area_under_pr`` (float), ``n``, ``n_pos``,
+    ``n_thresholds`` (the number of distinct scores, G), ``roc_numerator`` (int), ``pr_sum`` (float); with the curve also ``thresholds
+    [G] float32`` in descending order and ``tp``, ``fp`` ``[G] uint32``, the positives / negatives with a score >= the threshold
+    (``None`` without)."""
+
+    def __init__(self, n, n_pos, n_thresholds, roc_numerator, pr_sum, area_under_roc, area_under_pr, thresholds=None, tp=None, fp=None):
+        self.n, self.n_pos, self.n_thresholds, self.roc_numerator = int(n), int(n_pos), int(n_thresholds), int(roc_numerator)
+        self.pr_sum, self.area_under_roc, self.area_under_pr = float(pr_sum), float(area_under_roc), float(area_under_pr)
+        self.thresholds, self.tp, self.fp = thresholds, tp, fp
+
+    def words(self):
+        """The seven words of ``sprk_exact_auc_result``, the doubles as their bits: equal tuples are equal results."""
+        bits = lambda v: int(np.float64(v).view(np.uint64))
+        return (self.n, self.n_pos, self.n_thresholds, self.roc_numerator, bits(self.pr_sum), bits(self.area_under_roc), bits(self.area_under_pr))
+
+    def _curve(self):
+        if self.thresholds is None:
+            raise ValueError("the curve was not asked for (return_curve=True)")
+        return self.tp.astype(np.float64), self.fp.astype(np.float64)
+
+    def roc_points(self) -> np.ndarray:
+        """Spark's ROC curve ``[G + 2, 2]``: (0, 0), (fp_g / N, tp_g / P) per threshold, (1, 1); a rate over an empty class is 0."""
+        tp, fp = self._curve()
+        P, N = float(self.n_pos), float(self.n - self.n_pos)
+        x = fp / N if N else np.zeros_like(fp)
+        y = tp / P if P else np.zeros_like(tp)
+        return np.concatenate([[[0.0, 0.0]], np.stack([x, y], axis=1), [[1.0, 1.0]]])
+
+    def pr_points(self) -> np.ndarray:
+        """Spark 2.4's PR curve ``[G + 1, 2]``: (0, prec_1), then (tp_g / P, prec_g) per threshold; recall over no positive is 0."""
+        tp, fp = self._curve()
+        P = float(self.n_pos)
+        prec = tp / (tp + fp)
+        rec = tp / P if P else np.zeros_like(tp)
+        return np.concatenate([[[0.0, prec[0]]], np.stack([rec, prec], axis=1)])
+
+    def __repr__(self):
+        return "ExactAuc(area_under_roc=%r, area_under_pr=%r, n=%d, n_pos=%d, n_thresholds=%d)" % (self.area_under_roc, self.area_under_pr, self.n, self.n_pos,
+                                                                                                   self.n_thresholds)
+
+
+def _exact_host_labels(labels) -> np.ndarray:
+    a = np.asarray(labels).reshape(-1)
+    if a.dtype.str[1:] not in ("f4", "i4", "i8", "u1", "b1") or a.dtype.byteorder == ">":      # what DeviceMetrics.update uploads as it is
+        with np.errstate(over="ignore", invalid="ignore"):
+            a = a.astype(np.float32)
+    return a
+
+
+def exact_score_keys(scores: np.ndarray) -> np.ndarray:
+    """The threshold key of finite float32 scores, ``uint32``: ascending keys are descending scores, ``-0.0`` has the key of ``+0.0``."""
+    u = np.ascontiguousarray(scores, dtype=np.float32).view(np.uint32)
+    key = np.where(u & np.uint32(0x80000000), u, u ^ np.uint32(0x7fffffff)).astype(np.uint32)
+    key[scores == 0] = 0x7fffffff
+    return key
+
+
+def exact_key_scores(keys: np.ndarray) -> np.ndarray:
+    k = np.asarray(keys, dtype=np.uint32)
+    return np.where(k & np.uint32(0x80000000), k, k ^ np.uint32(0x7fffffff)).astype(np.uint32).view(np.float32)
+
+
+def exact_auc_host(labels, scores, return_curve: bool = False) -> ExactAuc:
+    """The DEFINITION of the exact areas under the ROC and the PR curve (DESIGN.md section 5.15 has the rules and where they come from).
+
+    ``scores``: float32 (anything else is converted), any finite value; a score's threshold is its float32 value, ``-0.0`` taken as
+    ``+0.0``.  ``labels``: as ``DeviceMetrics.update`` takes them (float32 / int32 / int64 / uint8 / bool; other dtypes go through
+    float32); a sample is positive iff ``label > 0.5``.  Groups ``g = 1 .. G`` are the distinct thresholds in descending order with
+    counts ``pos_g``, ``neg_g`` and running sums ``tp_g``, ``fp_g``; ``P = tp_G``, ``N = fp_G``.
+
+    * ``roc_numerator = sum_g neg_g (2 tp_{g-1} + pos_g)``, an integer; ``area_under_roc = float64(roc_numerator) / float64(2 P N)``;
+      1.0 when ``N = 0``, else 0.0 when ``P = 0``.
+    * ``prec_g = float64(tp_g) / float64(tp_g + fp_g)``, ``prec_0 := prec_1``; ``term_g = float64(pos_g) * (prec_g + prec_{g-1})``, every
+      operation rounded on its own.  The terms of ``PR_RUN`` consecutive groups are added in group order from ``+0.0``, the run sums
+      in run order from ``+0.0``: that is ``pr_sum``.  ``area_under_pr = pr_sum / float64(2 P)``; 0.0 when ``P = 0``.
+
+    Errors come before anything is computed: the least of ``kind << 32 | row`` over the rows whose score (kind 1) or label (kind 2) is
+    not finite raises a ``ValueError`` naming the row; so do ``n = 0`` and ``n > 2^31 - 2``."""
+    s = np.asarray(scores)
+    if s.dtype != np.float32:
+        with np.errstate(over="ignore", invalid="ignore"):
+            s = s.astype(np.float32)
+    s = np.ascontiguousarray(s.reshape(-1))
+    lab = _exact_host_labels(labels)
+    n = int(s.shape[0])
+    if int(lab.shape[0]) != n:
+        raise ValueError("exact AUC: %d scores, %d labels" % (n, int(lab.shape[0])))
+    if n == 0:
+        raise ValueError("exact AUC: no sample")
+    if n > EXACT_AUC_MAX_N:
+        raise ValueError("exact AUC: at most 2^31 - 2 samples")
+    bad = ~np.isfinite(s)
+    if bad.any():
+        raise ValueError(exact_auc_error_message(EXACT_ERR_SCORE, int(np.flatnonzero(bad)[0])))
+    if lab.dtype.kind == "f":
+        bad = ~np.isfinite(lab)
+        if bad.any():
+            raise ValueError(exact_auc_error_message(EXACT_ERR_LABEL, int(np.flatnonzero(bad)[0])))
+    positive = lab > 0.5
+    keys, inv = np.unique(exact_score_keys(s), return_inverse=True)
+    inv = inv.reshape(-1)
+    G = len(keys)
+    cnt = np.bincount(inv, minlength=G).astype(np.int64)
+    pos = np.bincount(inv[positive], minlength=G).astype(np.int64)
+    neg = cnt - pos
+    tp, fp = np.cumsum(pos), np.cumsum(neg)
+    P, N = int(tp[-1]), int(fp[-1])
+    numerator = int(np.sum(neg * (2 * (tp - pos) + pos)))                  # <= 2 P N < 2^62: exact in int64
+    roc = 1.0 if N == 0 else (0.0 if P == 0 else float(numerator) / float(2 * P * N))
+    prec = tp.astype(np.float64) / (tp + fp).astype(np.float64)
+    prev = np.concatenate([prec[:1], prec[:-1]])
+    term = pos.astype(np.float64) * (prec + prev)
+    runs = (G + PR_RUN - 1) // PR_RUN
+    padded = np.zeros(runs * PR_RUN, dtype=np.float64)                     # (+0.0 added to a sum that is >= +0.0 changes no bit)
+    padded[:G] = term
+    run_sum = np.cumsum(padded.reshape(runs, PR_RUN), axis=1)[:, -1]       # cumsum adds one element after the other
+    pr_sum = float(np.cumsum(run_sum)[-1])
+    pr = 0.0 if P == 0 else pr_sum / float(2 * P)
+    out = ExactAuc(n, P, G, numerator, pr_sum, roc, pr)
+    if return_curve:
+        out.thresholds, out.tp, out.fp = exact_key_scores(keys), tp.astype(np.uint32), fp.astype(np.uint32)
+    return out
+
+
+class _ExactAucCall:
+    """An enqueued ``sprk_exact_auc``: ``result()`` is the one synchronisation and the one small copy (the curve, when asked for, is a
+    second copy of its ``G`` rows)."""
+
+    def __init__(self, out, curve, keep):
+        self._out, self._curve, self._keep = out, curve, keep
+
+    def result(self) -> ExactAuc:
+        w = self._out.cpu().numpy()                                        # seven words of result, the error word
+        self._keep = None
+        err = int(w[7])
+        if err != -1:
+            raise ValueError(exact_auc_error_message((err >> 32) & 0xffffffff, err & 0xffffffff))
+        f = w[4:7].view(np.float64)
+        res = ExactAuc(int(w[0]), int(w[1]), int(w[2]), int(w[3:4].view(np.uint64)[0]), float(f[0]), float(f[1]), float(f[2]))
+        if self._curve is not None:
+            G = res.n_thresholds
+            thr, tp, fp = (t[:G].cpu().numpy() for t in self._curve)
+            res.thresholds, res.tp, res.fp = thr, tp.view(np.uint32), fp.view(np.uint32)
+        return res
+
+
+def _exact_auc_enqueue(scores, labels, return_curve: bool = False) -> _ExactAucCall:
+    import ctypes as C
+
+    import torch
+
+    from . import _lib as L
+    who = "exact_auc_device"
+    if not torch.cuda.is_available():
+        raise RuntimeError("%s: no HIP device is visible (exact_auc_host is the host definition)" % who)
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda or scores.dtype != torch.float32:
+        raise ValueError("%s: scores must be a float32 device tensor" % who)
+    if scores.dim() == 2 and scores.shape[1] == 1:
+        scores = scores[:, 0]
+    if scores.dim() != 1:
+        raise ValueError("%s: scores must be [n] or [n, 1], not %s" % (who, tuple(scores.shape)))
+    n = int(scores.shape[0])
+    if n > 1 and scores.stride(0) != 1:
+        scores = scores.contiguous()
+    dev = scores.device
+    if not isinstance(labels, torch.Tensor):
+        labels = torch.from_numpy(np.ascontiguousarray(_exact_host_labels(labels))).to(dev, non_blocking=True)
+    elif not labels.is_cuda:
+        labels = labels.to(dev, non_blocking=True)
+    if labels.dim() == 2 and labels.shape[1] == 1:
+        labels = labels[:, 0]
+    if labels.dim() != 1 or int(labels.shape[0]) != n:
+        raise ValueError("%s: %d scores, labels of shape %s" % (who, n, tuple(labels.shape)))
+    if labels.device != dev:
+        raise ValueError("%s: labels are on %s, the scores on %s" % (who, labels.device, dev))
+    storage = DeviceMetrics._storage_of(labels.dtype)
+    if storage is None:
+        labels, storage = labels.to(torch.float32), L.COL_F32
+    if n == 0:
+        raise ValueError("exact AUC: no sample")
+    if n > EXACT_AUC_MAX_N:
+        raise ValueError("exact AUC: at most 2^31 - 2 samples")
+    stride = labels.stride(0) if n > 1 else 1
+    if stride <= 0:
+        labels, stride = labels.contiguous(), 1
+    lib = L.load_library()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    with torch.cuda.device(dev):
+        out = torch.zeros(8, dtype=torch.int64, device=dev)
+        out[7] = -1                                                        # the error word, ~0
+        curve = None
+        if return_curve:
+            curve = (torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+        ws_bytes = lib.sprk_exact_auc_workspace_bytes(n)
+        ws = torch.empty(ws_bytes // 8 + 2, dtype=torch.int64, device=dev)    # (torch's allocations are 512-byte aligned)
+        null = C.c_void_p(None)
+        L.check(lib.sprk_exact_auc(p(scores), p(labels), storage, stride * labels.element_size(), n, p(out),
+                                   p(curve[0]) if curve else null, p(curve[1]) if curve else null, p(curve[2]) if curve else null,
+                                   C.c_void_p(out.data_ptr() + 56), p(ws), ws.numel() * 8, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return _ExactAucCall(out, curve, (scores, labels, ws))
+
+
+def exact_auc_device(scores, labels, return_curve: bool = False) -> ExactAuc:
+    """``exact_auc_host``'s result, bit for bit, from scores in device memory (``sprk_exact_auc``): ``scores`` a float32 device tensor
+    ``[n]`` or ``[n, 1]``, ``labels`` what ``DeviceMetrics.update`` takes -- a device tensor, a strided column view included, or a host
+    array, which is uploaded.  Enqueued on the current stream; one synchronisation and one copy of 64 bytes (with ``return_curve`` a
+    second copy of the ``G`` curve rows).  Errors are ``exact_auc_host``'s ``ValueError``."""
+    return _exact_auc_enqueue(scores, labels, return_curve).result()
+
+
 def binary_crossentropy(labels, preds) -> float:
     y = np.asarray(labels, dtype=np.float64).reshape(-1)
     p = np.clip(np.asarray(preds, dtype=np.float64).reshape(-1), EPS, 1.0 - EPS)
@@ -103,7 +329,8 @@ class DeviceMetrics:
 
     Accuracy and the two AUCs are ``evaluate_scores``' bits (integer counts, then the same expressions); the loss agrees with
     ``binary_crossentropy`` up to the order of the float64 additions and the device's ``log``, and is the same bits on every run.
-    Not provided: the exact rank-statistic AUC (``exact_roc_auc``), which needs every score and stays on the host.
+    Not provided here: the exact areas over every distinct score, which need every score at once -- ``exact_auc_device`` computes them
+    from a flat score buffer in device memory.
 
     One object is not re-entrant: its updates must be ordered on one stream (the current stream of its device).  ``state_dict`` /
     ``merge`` let row-sharded ranks combine their few KB instead of gathering scores; an object that was only merged into needs no GPU."""

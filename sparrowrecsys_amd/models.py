@@ -688,6 +688,75 @@ class CTRModel:
         self.engine.check_ids()
         return dm.result()
 
+    def evaluate_exact(self, x, y=None, batch_size: Optional[int] = None, return_curve: bool = False):
+        """The reference's Spark evaluation (offline/spark/evaluate/Evaluator.scala: ``areaUnderROC`` / ``areaUnderPR`` over every distinct
+        score) of this model's scores, on the device: takes what ``evaluate_device`` takes, scores every batch into ONE flat buffer in
+        device memory and hands it to ``metrics.exact_auc_device`` -- one call, one synchronisation, one small copy -> a
+        ``metrics.ExactAuc``, bit for bit ``metrics.exact_auc_host(labels, self.predict(x))``."""
+        import torch
+
+        from .metrics import _exact_auc_enqueue
+        if isinstance(x, Mapping):
+            labels = x["label"] if y is None else y
+            B = batch_size_of(x)
+            if batch_size is None or batch_size >= B:
+                batches = [(x, labels)]
+            else:
+                batches = [({k: v[s:s + batch_size] for k, v in x.items()}, labels[s:s + batch_size]) for s in range(0, B, batch_size)]
+        else:
+            batches = list(x)
+            if not batches or not all(isinstance(b, (tuple, list)) and len(b) == 2 and isinstance(b[0], Mapping) for b in batches):
+                raise ValueError("evaluate: an iterable of (features, labels) batches, or a feature dict with labels, is required")
+        packed = []
+        for feats, labels in batches:
+            ids_t, dense_t = self.pack_device(feats)
+            B = int(ids_t.shape[0])
+            count = labels.numel() if isinstance(labels, torch.Tensor) else np.asarray(labels).size
+            if count != B:
+                raise ValueError("evaluate: a batch of %d rows with %d labels" % (B, count))
+            if B:
+                packed.append((ids_t, dense_t, labels))
+        if not packed:
+            raise ValueError("exact AUC: no sample")
+        flat = torch.empty(sum(int(b[0].shape[0]) for b in packed), dtype=torch.float32, device=packed[0][0].device)
+        lo, at = 0, 0
+        while at < len(packed):                                   # groups of equal-sized batches, as predict forms them
+            B, end = int(packed[at][0].shape[0]), at + 1
+            while end < len(packed) and end - at < self.MANY_GROUP and int(packed[end][0].shape[0]) == B:
+                end += 1
+            if end - at == 1:
+                self.predict_device(packed[at][0], packed[at][1], flat[lo:lo + B])
+            else:
+                self.predict_device_many([b[0] for b in packed[at:end]], [b[1] for b in packed[at:end]], [flat[lo + i * B:lo + (i + 1) * B] for i in range(end - at)])
+            lo, at = lo + B * (end - at), end
+        if len(packed) == 1:
+            labels = packed[0][2]
+        elif all(isinstance(b[2], torch.Tensor) and b[2].is_cuda for b in packed):
+            labels = torch.cat([b[2].reshape(-1) for b in packed])
+        else:
+            labels = np.concatenate([b[2].cpu().numpy().reshape(-1) if isinstance(b[2], torch.Tensor) else np.asarray(b[2]).reshape(-1) for b in packed])
+        call = _exact_auc_enqueue(flat, labels, return_curve)
+        self.engine.check_ids()
+        return call.result()
+
+    def evaluate_exact_csv(self, source, label: str = "label", batch_size: int = 65536, max_rows: Optional[int] = None, return_curve: bool = False):
+        """``evaluate_exact`` along ``evaluate_csv``'s route: raw text to the device, tokenized there with the ``label`` column as one more
+        dense column, the forward into one flat score buffer, and ONE ``sprk_exact_auc`` call that reads the labels where the tokenizer
+        wrote them -> the ``metrics.ExactAuc`` of ``evaluate_exact(read_samples_csv(path))``."""
+        from .ingest import pack_csv_device, read_csv_to_device
+        from .metrics import _exact_auc_enqueue
+        if isinstance(source, str):
+            buf, nbytes = read_csv_to_device(source)
+            source = buf[:nbytes]
+        nd = len(self.numeric_keys)
+        ids, wide = pack_csv_device(source, self.id_columns, list(self.numeric_keys) + [label], max_rows=max_rows)
+        if int(ids.shape[0]) == 0:
+            raise ValueError("exact AUC: no sample")
+        out = self._score_slices(ids, wide[:, :nd].contiguous(), batch_size)
+        call = _exact_auc_enqueue(out, wide[:, nd], return_curve)
+        self.engine.check_ids()
+        return call.result()
+
     def predict_csv(self, source, batch_size: int = 65536, max_rows: Optional[int] = None) -> np.ndarray:
         """``model.predict(get_dataset(path))`` of the reference (DeepFM.py:14-22,131-133) without the host in the data path:
         ``source`` = a CSV file path, its bytes, or a ``torch.uint8`` device tensor holding the text.  The raw text goes to
