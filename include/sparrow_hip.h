@@ -635,6 +635,48 @@ int sprk_user_emb(const int32_t* user_id, const int32_t* item_row, int64_t n_rat
                   int32_t mode, float* user_emb, int32_t user_stride, uint8_t* user_has, int32_t* user_count,
                   uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- embedding LSH on the device: random-projection buckets, a sorted index per hash table, approximate top-K ----
+ * The reference's Embedding.embeddingLSH (Embedding.scala:230-252): Spark's BucketedRandomProjectionLSH, its transform and its single-probe
+ * approxNearestNeighbors.  The definition, rule by rule, is sparrowrecsys_amd/lsh.py hash_host / approx_nearest_host (DESIGN.md section
+ * 5.16); these calls give the same bits.  All arithmetic is double, every operation rounded on its own (no fused multiply-add), in index
+ * order; no float or double atomics, so every output is a function of the input alone.
+ *
+ * sprk_lsh_hash (`transform`).  In, device memory: emb [n][stride] float32 of which D per row are read, has [n] (NULL: every row has an
+ * embedding), vectors [T][D] float64 (the caller's: random_unit_vectors in lsh.py, or any).  Out: buckets [n][T] int64, every word written.
+ * For row x and table t: dot = ((+0.0 + x_0 r_t0) + x_1 r_t1) + ..., bucket = floor(dot / bucket_length) clamped to [-2^62, 2^62]; a dot
+ * that is not finite, and every table of a row with has == 0, gives SPRK_LSH_NO_BUCKET: the row is in no bucket of that table.  A row
+ * with a non-finite coordinate has no bucket in any table.
+ *
+ * sprk_lsh_build.  In: buckets [n][T].  Out: idx_bucket [T][n] int64 and idx_row [T][n] int32 -- table t's n (bucket, row) pairs
+ * sorted by (bucket, row) ascending, one segment per table: in LDS up to 4096 rows (SPRK_FE_SORT_CAP, as for sprk_feature_eng), by
+ * chunked sort + merge passes beyond.  The workspace is sprk_lsh_build_workspace_bytes(n, T) bytes, 16-byte aligned (0 for sizes the
+ * call rejects).
+ *
+ * sprk_lsh_query (`approxNearestNeighbors`, one probe).  In: the table, has, vectors and bucket_length as given to sprk_lsh_hash, its
+ * buckets, sprk_lsh_build's index; queries [Q][query_stride] float32, query_has [Q] (NULL: every query counts).  The candidates of a
+ * query are the rows with has != 0 whose bucket equals the query's in at least one table (SPRK_LSH_NO_BUCKET equals nothing), each
+ * once; dist = sqrt(sum_i (x_i - y_i)^2) from +0.0 in index order with a correctly rounded square root; candidates are ordered by
+ * (dist, row) ascending.  Out, every word written: dist [Q][K] float64 and rows [Q][K] int32, the first K candidates; count [Q] int32,
+ * the number of candidates, which may exceed K.  Places past count, and every place of a query with query_has == 0 (count 0), hold NaN
+ * (0x7ff8000000000000) / -1.  One workgroup per query walks the bucket's range of every table and keeps the best K next to the new
+ * pairs in an LDS buffer of 4096 pairs, sorted and cut to K when full; SPRK_LSH_CHUNK = a power of two in [64, 4096], read at each
+ * call, shortens the buffer (for the tests).  No workspace.
+ *
+ * 0 <= n < 2^31 - 1, Q >= 0, 1 <= D <= 1024, 1 <= T <= 16, strides >= D, 1 <= K <= 1024 and K < the buffer's pairs, bucket_length finite
+ * and > 0, no NULL (but has / query_has) or misaligned pointer, a sufficient workspace (the message names the bytes needed): anything
+ * else returns SPRK_EINVAL BEFORE any device call.  Asynchronous on `stream`: no synchronisation, no memory owned by the library; all
+ * index arithmetic in 64 bits; the element-wise loops stride by sprk_segments_grid's grid. */
+#define SPRK_LSH_NO_BUCKET INT64_MIN
+int sprk_lsh_hash(const float* emb, const uint8_t* has, int64_t n, int32_t D, int32_t stride, const double* vectors, int32_t T,
+                  double bucket_length, int64_t* buckets, void* stream);
+size_t sprk_lsh_build_workspace_bytes(int64_t n, int32_t T);
+int sprk_lsh_build(const int64_t* buckets, int64_t n, int32_t T, int64_t* idx_bucket, int32_t* idx_row,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int sprk_lsh_query(const float* emb, const uint8_t* has, int64_t n, int32_t D, int32_t stride, const double* vectors, int32_t T,
+                   double bucket_length, const int64_t* buckets, const int64_t* idx_bucket, const int32_t* idx_row,
+                   const float* queries, const uint8_t* query_has, int32_t Q, int32_t query_stride, int32_t K,
+                   double* dist, int32_t* rows, int32_t* count, void* stream);
+
 /* ---- the movie catalogue on the device: average ratings, sorted lists, candidates and the default similarity ranker ----
  * The arithmetic of the reference's DataManager and SimilarMovieProcess (Movie.java:93-98, DataManager.java:253-283,
  * SimilarMovieProcess.java:39-83 and :145-159).  The definition, rule by rule, is sparrowrecsys_amd/catalog.py catalog_host / similar_host

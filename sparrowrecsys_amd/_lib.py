@@ -40,6 +40,7 @@ EXPORTED_SYMBOLS = [
     "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_exact_auc",
     "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_store_update_workspace_bytes", "sprk_store_update", "sprk_segments_grid",
     "sprk_user_emb_workspace_bytes", "sprk_user_emb",
+    "sprk_lsh_hash", "sprk_lsh_build_workspace_bytes", "sprk_lsh_build", "sprk_lsh_query",
     "sprk_catalog_build_workspace_bytes", "sprk_catalog_build", "sprk_catalog_similar",
     "sprk_als_workspace_bytes", "sprk_als_fit", "sprk_als_predict", "sprk_als_topk_workspace_bytes", "sprk_als_topk",
     "sprk_item_sequences_workspace_bytes", "sprk_item_sequences", "sprk_item_walks_workspace_bytes", "sprk_item_walks",
@@ -322,6 +323,12 @@ def load_library():
         lib.sprk_user_emb_workspace_bytes.restype = sz
         lib.sprk_user_emb.argtypes = [vp, vp, C.c_int64, i32, vp, vp, i32, i32, i32,                     # ratings, sizes, item table, D, item_stride
                                       i32, vp, i32, vp, vp, vp, vp, sz, vp]                              # mode, the three outputs, error word, workspace, stream
+        lib.sprk_lsh_hash.argtypes = [vp, vp, C.c_int64, i32, i32, vp, i32, C.c_double, vp, vp]          # table, has, n, D, stride, vectors, T, bucket_length, buckets, stream
+        lib.sprk_lsh_build_workspace_bytes.argtypes = [C.c_int64, i32]
+        lib.sprk_lsh_build_workspace_bytes.restype = sz
+        lib.sprk_lsh_build.argtypes = [vp, C.c_int64, i32, vp, vp, vp, sz, vp]                         # buckets, n, T, the index, workspace, stream
+        lib.sprk_lsh_query.argtypes = [vp, vp, C.c_int64, i32, i32, vp, i32, C.c_double, vp, vp, vp,     # sprk_lsh_hash's first eight, buckets, the index
+                                       vp, vp, i32, i32, i32, vp, vp, vp, vp]                           # queries, query_has, Q, query_stride, K, dist, rows, count, stream
         lib.sprk_catalog_build_workspace_bytes.argtypes = [C.c_int64, i32, C.c_int64]
         lib.sprk_catalog_build_workspace_bytes.restype = sz
         lib.sprk_catalog_build.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, vp, vp, i32,                  # ratings, sizes, movie table, n_genres
@@ -356,7 +363,7 @@ def load_library():
         lib.sprk_train_fm_workspace_bytes.restype = sz
         lib.sprk_train_fm_fit.argtypes = [C.POINTER(TrainFmModel)] + lib.sprk_train_fit.argtypes[1:]             # sprk_train_fit's argument list
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_segments_grid", "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_segments_grid", "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_lsh_build_workspace_bytes", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

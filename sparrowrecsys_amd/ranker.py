@@ -8,7 +8,8 @@ Host side only parses the reference's embedding files and moves arrays; the scor
 
 Recall -- the step in front of the ranker -- is `EmbRanker.topk` / `retrieve` / `similar_movies`: the K table rows closest to a
 query over the WHOLE table, exact (`sprk_emb_topk`; `SimilarMovieProcess.retrievalCandidatesByEmbedding`,
-SimilarMovieProcess.java:91-112).
+SimilarMovieProcess.java:91-112).  `EmbRanker.lsh_index` / `approx_similar_movies` are the approximate recall next to it: the rows that
+share an LSH bucket with the query (`lsh.py`, `sprk_lsh_query`; Embedding.embeddingLSH, Embedding.scala:230-252).
 """
 from __future__ import annotations
 
@@ -66,6 +67,7 @@ class EmbRanker:
         self.ids = np.array(ids, dtype=np.int64)                         # movie id of every table row
         self._topk_ws = None
         self._row_lut = None
+        self._lsh = {}
         self.table = torch.from_numpy(table).to(self.device)
         self.has = torch.from_numpy(has).to(self.device)
 
@@ -196,6 +198,28 @@ class EmbRanker:
         n = min(int(size) + 1, len(self.ids))
         _, rows = self.topk(self.table[row:row + 1], n, query_has=self.has[row:row + 1])
         out = [int(m) for m in self.ids[rows[0].cpu().numpy()].tolist() if m != int(movie_id)]
+        return out[:int(size)]
+
+    # ---- approximate recall: the rows that share an LSH bucket with the query (lsh.py, sprk_lsh_query) ----
+    def lsh_index(self, bucket_length: float = 0.1, num_hash_tables: int = 3, seed: int = 0):
+        """The :class:`~sparrowrecsys_amd.lsh.LSHIndex` over this table (Embedding.embeddingLSH's configuration by default), built on
+        first use and kept per argument triple."""
+        from . import lsh
+        key = (float(bucket_length), int(num_hash_tables), int(seed))
+        if key not in self._lsh:
+            self._lsh[key] = lsh.LSHIndex.build(self.table, self.has, bucket_length=key[0], num_hash_tables=key[1], seed=key[2])
+        return self._lsh[key]
+
+    def approx_similar_movies(self, movie_id: int, size: int, **index_args) -> list:
+        """`similar_movies` through the LSH index (`index_args`: `lsh_index`'s): the movies that share a bucket with `movie_id` in at
+        least one hash table, closest first by Euclidean distance, the movie itself left out (asked for as size + 1 rows and dropped on
+        the host); [] for a movie the table does not know, and however many candidates the buckets give when that is fewer than
+        `size`.  The exact search reads every row of the table for a query; this one reads the rows of the query's buckets."""
+        row = self.row_of.get(int(movie_id))
+        if row is None or int(size) <= 0:
+            return []
+        _, rows, _ = self.lsh_index(**index_args).approx_nearest(self.table[row:row + 1], int(size) + 1, query_has=self.has[row:row + 1])
+        out = [int(self.ids[r]) for r in rows[0].cpu().tolist() if r >= 0 and r != row]
         return out[:int(size)]
 
 
