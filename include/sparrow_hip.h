@@ -677,6 +677,51 @@ int sprk_lsh_query(const float* emb, const uint8_t* has, int64_t n, int32_t D, i
                    const float* queries, const uint8_t* query_has, int32_t Q, int32_t query_stride, int32_t K,
                    double* dist, int32_t* rows, int32_t* count, void* stream);
 
+/* ---- the held-out split on the device: a sample of the rows, cut at random or at a quantile of the timestamps ----
+ * The reference's splitAndSaveTrainingTestSamples and ...ByTimeStamp (FeatureEngForRecModel.scala:176-205): a 10 % sample cut 80 / 20.
+ * The definition, rule by rule, is sparrowrecsys_amd/featureeng.py split_host; these calls give the same bytes.
+ *
+ * sprk_split_plan.  In, device memory: key [n] -- int32 (key_kind 1) or int64 (key_kind 2) -- or nothing (key_kind 0: a row's key is its
+ * position); timestamp [n] int64 (mode 1 only; unread in mode 0).  For key k and stream s (0 = sample, 1 = split), modulo 2^64:
+ *   x = seed + 0x9E3779B97F4A7C15 (2 k + s + 1);  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;
+ *   x ^= x >> 31;  u = x >> 11
+ * A row is sampled where its stream-0 u < t_sample.  mode 0 (random): a sampled row is training where its stream-1 u < t_train, else
+ * test.  mode 1 (time): with r = ceil(train * (double)n_sampled), the call's only float arithmetic, split_timestamp = the sampled rows'
+ * timestamp at ascending position max(r, 1) - 1, found exactly by a radix select (sign bit flipped, eight passes of eight bits, most
+ * significant first: a 256-bin histogram per pass and a one-workgroup pick between passes); sampled rows with timestamp <=
+ * split_timestamp are training, the others test.  t_sample and t_train are the caller's floor(fraction * 2^53) (2^53 for a fraction of 1).
+ * Out: index_train [n] and index_test [n] int32, of which the first n_train / n_test are written: the parts' source positions,
+ * ascending -- a row's place is decided by per-tile counts, a scan and ballots, by no atomic, so the lists are the same on every run.
+ * words [5] int64: words[0] is the error word, set to ~0 (-1) by the caller BEFORE the call; the call writes words[1 .. 4] = n_sampled,
+ * n_train, n_test, split_timestamp (0 in mode 0 and where no row is sampled).  A negative key does atomicMin (1 << 32 | row) into the
+ * error word; every kernel returns at once when the word is not ~0, so the lists and the other four words then hold no result.
+ * The workspace is sprk_split_plan_workspace_bytes of n, 16-byte aligned (0 for an n the call rejects).
+ * 0 <= n < 2^31 - 1, key_kind 0 / 1 / 2, mode 0 / 1, thresholds <= 2^53, 0 <= train <= 1, no NULL (but key at key_kind 0 and timestamp in
+ * mode 0) or misaligned pointer, a sufficient workspace (the message names the bytes needed): anything else returns SPRK_EINVAL BEFORE
+ * any device call.
+ *
+ * sprk_take_rows: dst[j] = src[index[j]], j in [0, n_index), for each of n_cols columns.  A column is a sprk_split_col: its source (row
+ * i at src + i * src_stride bytes, so a column of a wider matrix is taken where it lies), the bytes of a row (a positive multiple of
+ * 4) and a dense destination of n_index rows.  A thread makes 16 bytes of a destination, stored as one 128-bit word where the
+ * destination is 16-byte aligned and loaded as one where row_bytes, src and src_stride are multiples of 16.  n_rows = the rows of the
+ * sources: an index outside [0, n_rows) leaves its destination row unwritten.  Pointers 4-byte aligned, src_stride a multiple of 4 and
+ * >= 0, 0 <= n_index, n_rows < 2^31 - 1, else SPRK_EINVAL BEFORE any device call.  No workspace.
+ *
+ * Both are asynchronous on `stream`: no synchronisation, no memory owned by the library; all index arithmetic in 64 bits; the loops
+ * stride by sprk_segments_grid's grid. */
+typedef struct {
+    const void* src;
+    int64_t src_stride;                /* bytes from a source row to the next */
+    int32_t row_bytes;                 /* a multiple of 4 */
+    int32_t reserved;                  /* 0 */
+    void* dst;
+} sprk_split_col;
+size_t sprk_split_plan_workspace_bytes(int64_t n);
+int sprk_split_plan(const void* key, int32_t key_kind, const int64_t* timestamp, int64_t n, uint64_t seed, uint64_t t_sample, uint64_t t_train,
+                    double train, int32_t mode, int32_t* index_train, int32_t* index_test, int64_t* words,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int sprk_take_rows(const sprk_split_col* cols, int32_t n_cols, const int32_t* index, int64_t n_index, int64_t n_rows, void* stream);
+
 /* ---- the movie catalogue on the device: average ratings, sorted lists, candidates and the default similarity ranker ----
  * The arithmetic of the reference's DataManager and SimilarMovieProcess (Movie.java:93-98, DataManager.java:253-283,
  * SimilarMovieProcess.java:39-83 and :145-159).  The definition, rule by rule, is sparrowrecsys_amd/catalog.py catalog_host / similar_host

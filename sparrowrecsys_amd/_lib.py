@@ -41,6 +41,7 @@ EXPORTED_SYMBOLS = [
     "sprk_feature_eng_workspace_bytes", "sprk_feature_eng", "sprk_store_update_workspace_bytes", "sprk_store_update", "sprk_segments_grid",
     "sprk_user_emb_workspace_bytes", "sprk_user_emb",
     "sprk_lsh_hash", "sprk_lsh_build_workspace_bytes", "sprk_lsh_build", "sprk_lsh_query",
+    "sprk_split_plan_workspace_bytes", "sprk_split_plan", "sprk_take_rows",
     "sprk_catalog_build_workspace_bytes", "sprk_catalog_build", "sprk_catalog_similar",
     "sprk_als_workspace_bytes", "sprk_als_fit", "sprk_als_predict", "sprk_als_topk_workspace_bytes", "sprk_als_topk",
     "sprk_item_sequences_workspace_bytes", "sprk_item_sequences", "sprk_item_walks_workspace_bytes", "sprk_item_walks",
@@ -81,6 +82,11 @@ class ExactAucResult(C.Structure):
     """sprk_exact_auc_result (include/sparrow_hip.h): seven 8-byte words."""
     _fields_ = [("n", C.c_int64), ("n_pos", C.c_int64), ("n_groups", C.c_int64), ("roc_numerator", C.c_uint64),
                 ("pr_sum", C.c_double), ("area_under_roc", C.c_double), ("area_under_pr", C.c_double)]
+
+
+class SplitCol(C.Structure):
+    """sprk_split_col (include/sparrow_hip.h): a column of sprk_take_rows -- source, bytes between source rows, bytes of a row, 0, destination."""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int64), ("row_bytes", C.c_int32), ("reserved", C.c_int32), ("dst", C.c_void_p)]
 
 
 TRAIN_MAX_COLS, TRAIN_MAX_LAYERS, TRAIN_MAX_X, TRAIN_MAX_WIDTH = 16, 8, 256, 256
@@ -329,6 +335,11 @@ def load_library():
         lib.sprk_lsh_build.argtypes = [vp, C.c_int64, i32, vp, vp, vp, sz, vp]                         # buckets, n, T, the index, workspace, stream
         lib.sprk_lsh_query.argtypes = [vp, vp, C.c_int64, i32, i32, vp, i32, C.c_double, vp, vp, vp,     # sprk_lsh_hash's first eight, buckets, the index
                                        vp, vp, i32, i32, i32, vp, vp, vp, vp]                           # queries, query_has, Q, query_stride, K, dist, rows, count, stream
+        lib.sprk_split_plan_workspace_bytes.argtypes = [C.c_int64]
+        lib.sprk_split_plan_workspace_bytes.restype = sz
+        lib.sprk_split_plan.argtypes = [vp, i32, vp, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, i32,   # key, key_kind, timestamp, n, seed, T(sample), T(train), train, mode
+                                        vp, vp, vp, vp, sz, vp]                                                   # the two index lists, the five words, workspace, stream
+        lib.sprk_take_rows.argtypes = [C.POINTER(SplitCol), i32, vp, C.c_int64, C.c_int64, vp]                    # columns, n_cols, index, n_index, n_rows, stream
         lib.sprk_catalog_build_workspace_bytes.argtypes = [C.c_int64, i32, C.c_int64]
         lib.sprk_catalog_build_workspace_bytes.restype = sz
         lib.sprk_catalog_build.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, vp, vp, i32,                  # ratings, sizes, movie table, n_genres

@@ -37,6 +37,10 @@ New ratings are applied to an existing store by :func:`update_host` (the definit
 csrc/k_store_update.h): the store's tables afterwards are byte for byte the tables built from all ratings applied so far, given
 that a user's new ratings are not older than the user's latest.  They keep a :class:`StoreState`.
 
+The held-out split between ``build`` and ``model.fit`` -- the reference's 10 % sample cut 80 / 20 at random or at the 0.8 quantile of
+the timestamps (FeatureEngForRecModel.scala:176-205) -- is :func:`split_host` (the definition, integers only), :func:`split_device` and
+:meth:`DeviceSamples.split` (``sprk_split_plan`` + ``sprk_take_rows``, csrc/k_split.h): DESIGN.md section 5.17.
+
 Out of scope: feeding the device-resident samples straight into ``evaluate_device`` (use ``.to_host()``).
 """
 from __future__ import annotations
@@ -348,9 +352,19 @@ class DeviceSamples:
     """What :func:`build` returns: the sample columns as device tensors (``columns``: the dict of :func:`samples_host`, every tensor cut to
     ``n_samples`` rows) and the feature store's tables, which were written by the same call and never left the device."""
 
-    def __init__(self, columns, n_samples, hist_len, store_tensors, device):
+    def __init__(self, columns, n_samples, hist_len, store_tensors, device, n_sampled=None, split_timestamp=None):
         self.columns, self.n_samples, self.hist_len, self.device = columns, int(n_samples), int(hist_len), device
         self._store_tensors = store_tensors
+        self.n_sampled, self.split_timestamp = n_sampled, split_timestamp      # (set on the two parts of a split)
+
+    def split(self, mode: str = "random", sample: float = 0.1, train: float = 0.8, seed: int = 0, key="source_row"):
+        """-> ``(train, test)``: :func:`split_device` over ``columns``, as two :class:`DeviceSamples` whose columns are exactly ``n_train`` /
+        ``n_test`` rows long and which carry ``n_sampled`` and ``split_timestamp``.  Both share this build's store tables: the reference's
+        store is built from all samples.  ``model.fit(train.columns)`` and ``model.evaluate_device(test.columns)`` take them as they are."""
+        res = split_device(self.columns, mode=mode, sample=sample, train=train, seed=seed, key=key, device=self.device)
+        part = lambda cols: DeviceSamples(cols, len(next(iter(cols.values()))) if cols else 0, self.hist_len, self._store_tensors, self.device,
+                                          res.n_sampled, res.split_timestamp)
+        return part(res.train), part(res.test)
 
     def to_host(self) -> dict:
         """The dict :func:`samples_host` returns, bit for bit."""
@@ -627,3 +641,174 @@ def update_device(state: StoreState, ratings) -> int:
         raise ValueError(_error_message((err >> 32) & 0xffffffff, err & 0xffffffff))
     state.n_ratings += n
     return n
+
+
+# ---- the held-out split: a sample, cut at random or at a time quantile ----
+SplitResult = namedtuple("SplitResult", "train test n_sampled split_timestamp")
+SPLIT_MODES = {"random": 0, "time": 1}
+STREAM_SAMPLE, STREAM_SPLIT = 0, 1
+_MASK64 = (1 << 64) - 1
+
+
+def split_threshold(f: float) -> int:
+    """``T(f)``: ``floor(f * 2^53)`` for ``f < 1`` and ``2^53`` for ``f = 1`` -- one exact float64 scaling.  A draw ``u`` succeeds where ``u < T(f)``."""
+    import math
+    f = float(f)
+    if not 0.0 <= f <= 1.0:                                                  # (NaN fails both comparisons)
+        raise ValueError("a fraction of %r is outside [0, 1]" % f)
+    return int(math.floor(math.ldexp(f, 53)))
+
+
+def split_draws(seed: int, keys, stream: int) -> np.ndarray:
+    """The 53-bit draws of the rows with the non-negative integer ``keys`` on ``stream`` (0 = sample, 1 = split) as uint64: splitmix64's
+    finalizer over ``seed + 0x9E3779B97F4A7C15 (2 k + s + 1)``, all modulo 2^64.  A function of (seed, key, stream) alone."""
+    k = np.asarray(keys).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        x = np.uint64(int(seed) & _MASK64) + np.uint64(0x9E3779B97F4A7C15) * (k * np.uint64(2) + np.uint64(int(stream) + 1))
+        x ^= x >> np.uint64(30)
+        x *= np.uint64(0xBF58476D1CE4E5B9)
+        x ^= x >> np.uint64(27)
+        x *= np.uint64(0x94D049BB133111EB)
+        x ^= x >> np.uint64(31)
+    return x >> np.uint64(11)
+
+
+def _split_arguments(mode, sample, train):
+    """-> T(sample), T(train); the ``ValueError`` of a bad fraction or mode."""
+    if mode not in SPLIT_MODES:
+        raise ValueError("mode = %r (\"random\" or \"time\")" % (mode,))
+    return split_threshold(sample), split_threshold(train)
+
+
+def _split_rows(columns, mode, key, dtype_of):
+    """The row count of a dict of equal-length columns; the ``ValueError`` of unequal lengths, too many rows, a missing key column or,
+    in time mode, a missing or non-int64 ``timestamp``.  ``dtype_of``: a column's dtype by name ("int64", ...)."""
+    lengths = {int(v.shape[0]) if getattr(v, "ndim", 1) else -1 for v in columns.values()}
+    if len(lengths) > 1 or -1 in lengths:
+        raise ValueError("the columns differ in length")
+    n = lengths.pop() if lengths else 0
+    if n >= _ID_LIMIT:
+        raise ValueError("at most 2^31 - 2 rows")
+    if mode == "time" and ("timestamp" not in columns or dtype_of(columns["timestamp"]) != "int64"):
+        raise ValueError("mode \"time\" needs an int64 timestamp column")
+    if key is not None:
+        if key not in columns:
+            raise ValueError("no key column %r" % (key,))
+        if dtype_of(columns[key]) not in ("int8", "int16", "int32", "int64", "uint8", "uint16", "uint32", "uint64"):
+            raise ValueError("the key column %r must hold integers" % (key,))
+    return n
+
+
+def split_host(samples, mode: str = "random", sample: float = 0.1, train: float = 0.8, seed: int = 0, key="source_row") -> SplitResult:
+    """The definition of the held-out split (FeatureEngForRecModel.scala:176-205: a 10 % sample, cut 80 / 20), in numpy and integers.
+
+    ``samples``: a dict of equal-length columns (what :func:`samples_host` returns) -> ``SplitResult(train, test, n_sampled,
+    split_timestamp)``; ``train`` / ``test`` are dicts of the same keys and dtypes, their rows in input order.  ``sample`` and ``train``
+    default to the reference's 0.1 and 0.8.
+
+    The generator is the project's own, not Spark's ``XORShiftRandom``: a row's draws are :func:`split_draws` of ``seed``, the row's
+    value in the ``key`` column (``key=None``: the row's position) and a stream number, and of nothing else -- not of the row's position
+    nor of which other rows exist, so a rating keeps its side when ratings are appended and the samples rebuilt.  A row is sampled where
+    its stream-0 draw is below ``T(sample)`` (:func:`split_threshold`); ``n_sampled`` counts these rows.
+
+    ``mode="random"``: a sampled row is training where its stream-1 draw is below ``T(train)``, otherwise test; ``split_timestamp`` is None.
+
+    ``mode="time"`` (needs an int64 ``timestamp`` column): with ``r = ceil(float64(train) * float64(n_sampled))`` -- one product, one ceil
+    -- ``split_timestamp`` is the sampled rows' timestamp at ascending position ``max(r, 1) - 1``; sampled rows with ``timestamp <=
+    split_timestamp`` are training (ties too, the reference's ``<=``), the others test; no sampled row gives two empty parts and None.
+    Deviation: this is the EXACT quantile where the reference takes ``approxQuantile(..., 0.05)``, which may return any value whose rank
+    lies within 0.05 n of 0.8 n; the exact quantile is one of those values.
+
+    ``ValueError``, before anything is computed: ``sample`` or ``train`` outside [0, 1] or not finite, an unknown mode, ``"time"`` without
+    an int64 timestamp, a missing or negative key, columns of unequal length, 2^31 - 1 rows or more."""
+    t_sample, t_train = _split_arguments(mode, sample, train)
+    cols = {k: _host_column(v) for k, v in samples.items()}
+    n = _split_rows(cols, mode, key, lambda a: a.dtype.name)
+    keys = np.arange(n, dtype=np.int64) if key is None else cols[key]
+    if key is not None and keys.dtype.kind == "i" and n and int(keys.min()) < 0:
+        raise ValueError("row %d: negative key" % int(np.flatnonzero(keys < 0)[0]))
+    sampled = split_draws(seed, keys, STREAM_SAMPLE) < np.uint64(t_sample)
+    n_sampled = int(sampled.sum())
+    split_timestamp = None
+    if mode == "random":
+        to_train = sampled & (split_draws(seed, keys, STREAM_SPLIT) < np.uint64(t_train))
+    elif n_sampled == 0:
+        to_train = sampled
+    else:
+        ts = cols["timestamp"]
+        r = int(np.ceil(np.float64(train) * np.float64(n_sampled)))
+        split_timestamp = int(np.sort(ts[sampled])[max(r, 1) - 1])
+        to_train = sampled & (ts <= split_timestamp)
+    to_test = sampled & ~to_train
+    return SplitResult({k: v[to_train] for k, v in cols.items()}, {k: v[to_test] for k, v in cols.items()}, n_sampled, split_timestamp)
+
+
+def _matrix_groups(cols) -> list:
+    """The columns' names in groups: a run of columns that are the adjacent columns of ONE row-major matrix (``DeviceSamples.columns``'
+    genre, history and numeric columns) is one group, taken as one row-wide column; every other column is a group of its own."""
+    groups, last = [], None
+    for k, v in cols.items():
+        where = (v.untyped_storage().data_ptr(), v.dtype, v.stride(0))
+        if last is not None and where == last[0] and v.stride(0) > len(groups[-1]) and v.storage_offset() == last[1] + 1:
+            groups[-1].append(k)
+        else:
+            groups.append([k])
+        last = (where, v.storage_offset())
+    return groups
+
+
+def split_device(columns, mode: str = "random", sample: float = 0.1, train: float = 0.8, seed: int = 0, key="source_row", device=None,
+                 group_matrices: bool = True) -> SplitResult:
+    """:func:`split_host` on the device, byte for byte: ``columns`` is a dict of equal-length one-dimensional columns of 4- or 8-byte
+    elements -- device tensors (``DeviceSamples.columns``; strided views are read where they are) or numpy arrays, which are uploaded --
+    and ``train`` / ``test`` are dicts of dense device tensors exactly ``n_train`` / ``n_test`` rows long.  ``sprk_split_plan`` writes the
+    two index lists and five words; one host synchronisation reads the words; then one ``sprk_take_rows`` per part.  Columns that are
+    adjacent columns of one matrix are taken as one row-wide column, and come back as the columns of a dense matrix of their own
+    (``group_matrices=False`` takes every column singly, into a dense vector: the same values; docs/split_results.md has both).  Errors are
+    :func:`split_host`'s; a negative key in a device column is found by the plan and raised after the synchronisation."""
+    import ctypes as C
+
+    import torch
+
+    from . import _lib as L
+    t_sample, t_train = _split_arguments(mode, sample, train)
+    lib = L.load_library()
+    if not torch.cuda.is_available():
+        raise RuntimeError("featureeng.split_device needs a HIP device: no HIP device is visible (split_host is the host definition)")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    cols = {k: (v.detach().to(dev) if hasattr(v, "detach") else torch.from_numpy(np.ascontiguousarray(_host_column(v))).to(dev)) for k, v in columns.items()}
+    n = _split_rows(cols, mode, key, lambda t: str(t.dtype).replace("torch.", ""))
+    for k, v in cols.items():
+        if v.ndim != 1 or v.element_size() % 4:
+            raise ValueError("column %r: split_device takes one-dimensional columns of 4- or 8-byte elements" % (k,))
+    key_kind, key_col = 0, None
+    if key is not None:
+        key_col = cols[key] if cols[key].dtype in (torch.int32, torch.int64) else cols[key].to(torch.int64)
+        key_col, key_kind = key_col.contiguous(), 1 if key_col.dtype == torch.int32 else 2
+    ts_col = cols["timestamp"].contiguous() if mode == "time" else None
+    with torch.cuda.device(dev):
+        rows = max(n, 1)
+        index = torch.empty((2, rows), dtype=torch.int32, device=dev)
+        words = torch.tensor([-1, 0, 0, 0, 0], dtype=torch.int64, device=dev)  # the error word (~0), n_sampled, n_train, n_test, split_timestamp
+        ws_bytes = lib.sprk_split_plan_workspace_bytes(n)
+        ws = torch.empty(max(ws_bytes, 16) // 8 + 2, dtype=torch.int64, device=dev)   # (torch's allocations are 512-byte aligned)
+        p = lambda x: C.c_void_p(None if x is None else x.data_ptr())
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L.check(lib.sprk_split_plan(p(key_col), key_kind, p(ts_col), n, int(seed) & _MASK64, t_sample, t_train, float(train), SPLIT_MODES[mode],
+                                    p(index[0]), p(index[1]), p(words), p(ws), ws.numel() * 8, stream))
+        err, n_sampled, n_train, n_test, split_timestamp = (int(v) for v in words.cpu().numpy())     # the one synchronisation
+        if err != -1:
+            raise ValueError("row %d: negative key" % (err & 0xffffffff))
+        groups = _matrix_groups(cols) if group_matrices else [[k] for k in cols]
+        parts = []
+        for which, count in ((0, n_train), (1, n_test)):
+            out, desc = {}, []
+            for names in groups:
+                first = cols[names[0]]
+                block = torch.empty((count, len(names)), dtype=first.dtype, device=dev)
+                desc.append(L.SplitCol(first.data_ptr(), first.stride(0) * first.element_size(), len(names) * first.element_size(), 0, block.data_ptr()))
+                for j, k in enumerate(names):
+                    out[k] = block[:, j]
+            L.check(lib.sprk_take_rows((L.SplitCol * len(desc))(*desc), len(desc), p(index[which]), count, n, stream))
+            parts.append({k: out[k] for k in cols})
+    return SplitResult(parts[0], parts[1], n_sampled, split_timestamp if mode == "time" and n_sampled else None)
