@@ -722,6 +722,52 @@ int sprk_split_plan(const void* key, int32_t key_kind, const int64_t* timestamp,
                     void* workspace, size_t workspace_bytes, void* stream);
 int sprk_take_rows(const sprk_split_col* cols, int32_t n_cols, const int32_t* index, int64_t n_index, int64_t n_rows, void* stream);
 
+/* ---- ranking metrics on the device: top-K lists against held-out (user, item) pairs ----
+ * Spark's RankingMetrics (precisionAt, recallAt, ndcgAt, meanAveragePrecisionAt) plus hit rate and reciprocal rank, the lists first
+ * cleared of what the user has already seen.  The definition, rule by rule, is sparrowrecsys_amd/rankeval.py rank_eval_host (DESIGN.md
+ * section 5.18); this call gives the same bytes.
+ *
+ * In, device memory: pred [n_queries][pred_stride] int32 of which list_len per row are read -- item ids, best first, a negative entry
+ * is no entry; query_user [n_queries] int32 (NULL: query q is user q's); the truth pairs truth_user / truth_item [n_truth] and the seen
+ * pairs seen_user / seen_item [n_seen] int32, in any order, duplicates allowed (n_seen 0: nothing is dropped); gain [1024] and
+ * gain_sum [1025] float64, the CALLER's: gain[i] = 1.0 / log(i + 2) and gain_sum[c] = gain[0] + .. + gain[c - 1] added in order from
+ * +0.0, made on the host (rankeval.py gain_table) -- no logarithm is taken on the device.  In, HOST memory: ks [n_ks] int32, the cut-offs.
+ *
+ * Per query q of user u: T = the distinct truth items of u, R = |T|; E = pred[q] in order without negative entries and without the
+ * entries among u's seen items, L = len(E).  A truth item that is also seen stays in T; duplicate entries of pred each count.  For a
+ * cut-off k, with n = min(L, k) and the hits = the places i < n with E[i] in T:
+ *   precision = hits / k;  recall = hits / R;  ndcg = dcg / gain_sum[min(R, k)], dcg = the sum of gain[i] over the hits in list order
+ *   from +0.0;  ap = (the sum over the hits, in order, of cnt_i / (i + 1)) / min(R, k), cnt_i = the running hit count;  hit = 1.0 where
+ *   hits > 0;  rr = 1 / (i0 + 1) for the first hit i0, else 0.0.
+ * All float64, every operation rounded on its own (no fused multiply-add), `/` correctly rounded.  A query with R == 0 scores +0.0 six
+ * times and is not counted in counts[1].
+ * Out, device memory: per_query [n_queries][n_ks][6] float64 in the order above; n_relevant [n_queries] (R) and n_ranked [n_queries]
+ * (L) int32; sums [n_ks][6] float64 -- per (k, metric) the partial sums over 256 consecutive queries from +0.0 in query order, then the
+ * partials in order from +0.0; counts [2] int64 = (n_queries, the queries with R > 0).  No float or double atomics and no cross-lane
+ * float reduction: every output is a function of the input alone.
+ *
+ * The error word is set to ~0 by the caller BEFORE the call.  A truth row (kind 1) or a seen row (kind 2) whose user lies outside
+ * [0, n_users) or whose item is negative, and a query (kind 3) whose user lies outside [0, n_users), do atomicMin (kind << 32 | row)
+ * into it; when it is not ~0 as the metrics start, none of the five outputs is written.
+ *
+ * Stages: per side, counts per user, the scan, a scatter and the segment sort by (item, input row) (in LDS up to 4096 rows,
+ * SPRK_FE_SORT_CAP as for sprk_feature_eng; chunked sort + merge passes beyond); one wave per query -- rounds of 64 entries, two
+ * binary searches a lane, two ballots, the float64 terms added in list order by a walk over the hit mask; the two-level sums.  The
+ * workspace is sprk_rank_eval_workspace_bytes(n_truth, n_seen, n_users, n_queries) bytes, 16-byte aligned (0 for sizes the call rejects).
+ *
+ * 0 <= n_truth, n_seen, n_users < 2^31 - 1, n_queries >= 0, 1 <= list_len <= 65536, pred_stride >= list_len, 1 <= n_ks <= 8, every k in
+ * [1, 1024] (independent of list_len), no NULL (but query_user; the truth or seen columns of an empty side; pred and the per-query
+ * outputs at n_queries 0) or misaligned pointer, a sufficient workspace (the message names the bytes needed): anything else returns
+ * SPRK_EINVAL BEFORE any device call.  Asynchronous on `stream`: no synchronisation, no memory owned by the library; all index
+ * arithmetic in 64 bits; the loops stride by sprk_segments_grid's grid. */
+size_t sprk_rank_eval_workspace_bytes(int64_t n_truth, int64_t n_seen, int32_t n_users, int32_t n_queries);
+int sprk_rank_eval(const int32_t* pred, int32_t n_queries, int32_t list_len, int32_t pred_stride, const int32_t* query_user,
+                   const int32_t* truth_user, const int32_t* truth_item, int64_t n_truth,
+                   const int32_t* seen_user, const int32_t* seen_item, int64_t n_seen, int32_t n_users,
+                   const int32_t* ks, int32_t n_ks, const double* gain, const double* gain_sum,
+                   double* per_query, int32_t* n_relevant, int32_t* n_ranked, double* sums, int64_t* counts,
+                   uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- the movie catalogue on the device: average ratings, sorted lists, candidates and the default similarity ranker ----
  * The arithmetic of the reference's DataManager and SimilarMovieProcess (Movie.java:93-98, DataManager.java:253-283,
  * SimilarMovieProcess.java:39-83 and :145-159).  The definition, rule by rule, is sparrowrecsys_amd/catalog.py catalog_host / similar_host

@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "sprk_user_emb_workspace_bytes", "sprk_user_emb",
     "sprk_lsh_hash", "sprk_lsh_build_workspace_bytes", "sprk_lsh_build", "sprk_lsh_query",
     "sprk_split_plan_workspace_bytes", "sprk_split_plan", "sprk_take_rows",
+    "sprk_rank_eval_workspace_bytes", "sprk_rank_eval",
     "sprk_catalog_build_workspace_bytes", "sprk_catalog_build", "sprk_catalog_similar",
     "sprk_als_workspace_bytes", "sprk_als_fit", "sprk_als_predict", "sprk_als_topk_workspace_bytes", "sprk_als_topk",
     "sprk_item_sequences_workspace_bytes", "sprk_item_sequences", "sprk_item_walks_workspace_bytes", "sprk_item_walks",
@@ -340,6 +341,11 @@ def load_library():
         lib.sprk_split_plan.argtypes = [vp, i32, vp, C.c_int64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_double, i32,   # key, key_kind, timestamp, n, seed, T(sample), T(train), train, mode
                                         vp, vp, vp, vp, sz, vp]                                                   # the two index lists, the five words, workspace, stream
         lib.sprk_take_rows.argtypes = [C.POINTER(SplitCol), i32, vp, C.c_int64, C.c_int64, vp]                    # columns, n_cols, index, n_index, n_rows, stream
+        lib.sprk_rank_eval_workspace_bytes.argtypes = [C.c_int64, C.c_int64, i32, i32]
+        lib.sprk_rank_eval_workspace_bytes.restype = sz
+        lib.sprk_rank_eval.argtypes = [vp, i32, i32, i32, vp, vp, vp, C.c_int64, vp, vp, C.c_int64, i32,   # lists, Q, list_len, stride, query_user, truth, seen, n_users
+                                       C.POINTER(i32), i32, vp, vp, vp, vp, vp, vp, vp,                    # ks (host), n_ks, gain, gain_sum, the five outputs
+                                       vp, vp, sz, vp]                                                    # error word, workspace, stream
         lib.sprk_catalog_build_workspace_bytes.argtypes = [C.c_int64, i32, C.c_int64]
         lib.sprk_catalog_build_workspace_bytes.restype = sz
         lib.sprk_catalog_build.argtypes = [vp, vp, C.c_int64, i32, vp, vp, vp, vp, vp, i32,                  # ratings, sizes, movie table, n_genres
@@ -374,7 +380,7 @@ def load_library():
         lib.sprk_train_fm_workspace_bytes.restype = sz
         lib.sprk_train_fm_fit.argtypes = [C.POINTER(TrainFmModel)] + lib.sprk_train_fit.argtypes[1:]             # sprk_train_fit's argument list
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_segments_grid", "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_lsh_build_workspace_bytes", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_segments_grid", "sprk_rank_eval_workspace_bytes", "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_lsh_build_workspace_bytes", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib

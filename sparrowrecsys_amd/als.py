@@ -424,6 +424,22 @@ class ALSModel:
         """``recommendForAllItems(k)``: the same with the sides exchanged."""
         return self._recommend(self.item_factors, self.item_has, self.user_factors, self.user_has, items, k)
 
+    def evaluate_ranking(self, test, train=None, ks=(10,), list_len: Optional[int] = None, min_rating: float = 3.5):
+        """The ranking metrics of this model's recommendations against held-out ratings (``rankeval.evaluate``): for every user with a
+        ``test`` row of ``rating >= min_rating``, the ``list_len`` best movies (default ``min(1024, n_items)``) by
+        :meth:`recommend_for_users`, cleared of the movies the user rated in ``train``, against the user's truth at the cut-offs ``ks``.
+        ``test`` / ``train``: a CSV path or rating columns, numpy arrays or device tensors.  -> ``rankeval.RankEval`` of device tensors,
+        one query per such user in ascending user id; no list leaves HBM."""
+        import torch
+
+        from . import rankeval as RE
+        u, m, r = _columns(test, self.device)
+        held_out = {"userId": u, "movieId": m, "rating": r}
+        users = torch.unique(u[(r >= float(min_rating)) & (u >= 0)])
+        k = min(MAX_K, self.n_items) if list_len is None else int(list_len)
+        lists = self.recommend_for_users(users, k).ids
+        return RE.evaluate(lists, users, held_out, train, ks=ks, min_rating=min_rating, device=self.device)
+
 
 def fit(ratings, rank: int = 10, reg: float = 0.01, iters: int = 5, seed: int = 0, init_user=None, device=None,
         n_users: Optional[int] = None, n_items: Optional[int] = None) -> ALSModel:

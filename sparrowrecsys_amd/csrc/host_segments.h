@@ -1,5 +1,5 @@
 // host_segments.h -- the host side of k_segments.h, shared by the entry points of sparrow_feature_eng.hip (api_feature_eng.h, api_store_update.h,
-// api_user_emb.h, api_catalog.h, api_als.h, api_item2vec.h): the sort capacity and the grids, the workspace carver and the workspace check, seg_scan
+// api_user_emb.h, api_catalog.h, api_als.h, api_item2vec.h, api_lsh.h, api_split.h, api_rank_eval.h): the sort capacity and the grids, the workspace carver and the workspace check, seg_scan
 // (counts -> offsets) and seg_sort (every segment of one side by its key).  Everything is enqueued on the caller's stream.
 namespace {
 // LDS sort capacity: FE_SORT_CAP, or SPRK_FE_SORT_CAP = a power of two in [64, FE_SORT_CAP], read at each call (tests: the long path at small sizes)

@@ -7,6 +7,7 @@
 //   ALS (k_als.h)                          segments per user and per movie
 //   item2vec (k_item2vec.h)                segments per user, key (timestamp, input row); per `prev` item, key (next, place); per row of
 //                                          syn0 / syn1, key (centre, context or depth)
+//   ranking metrics (k_rank_eval.h)        segments per user of the truth pairs and of the seen pairs, key (item, input row)
 // The kernels keep the names they got in feature engineering, where they were written first: k_fe_* are the names in rocprof traces,
 // in the timing tables of docs/*_results.md, in DESIGN.md sections 5.7-5.10 and in the GPU tests' docstrings.
 //   k_fe_scan_*     exclusive scan over ids of len (and, KEPT, of kept = max(0, len - 2)): three launches

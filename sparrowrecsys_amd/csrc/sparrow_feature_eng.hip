@@ -6,6 +6,7 @@
 //   item2vec: rating sequences and the skip-gram trainer       k_item2vec.h, api_item2vec.h: sprk_item_sequences / sprk_item_walks / sprk_skipgram_fit and their *_workspace_bytes
 //   embedding LSH: buckets, a sorted index, approximate top-K  k_lsh.h, api_lsh.h: sprk_lsh_hash / sprk_lsh_build / sprk_lsh_query and sprk_lsh_build_workspace_bytes
 //   samples -> a training and a test part, at random or by time  k_split.h, api_split.h: sprk_split_plan_workspace_bytes / sprk_split_plan / sprk_take_rows
+//   top-K lists + held-out pairs -> ranking metrics            k_rank_eval.h, api_rank_eval.h: sprk_rank_eval_workspace_bytes / sprk_rank_eval
 // and the unit that keeps the first one's store current:
 //   new ratings -> the feature store's rows, in place          k_store_update.h, api_store_update.h: sprk_store_update_workspace_bytes / sprk_store_update
 // The ratings pipelines count per id, scan, scatter into per-id segments and sort every segment, and the LSH index sorts one segment per
@@ -37,6 +38,7 @@
 #include "k_item2vec.h"
 #include "k_lsh.h"
 #include "k_split.h"
+#include "k_rank_eval.h"
 
 }  // namespace sprk_dev
 #pragma GCC visibility pop
@@ -51,3 +53,4 @@ using namespace sprk_dev;
 #include "api_item2vec.h"
 #include "api_lsh.h"
 #include "api_split.h"
+#include "api_rank_eval.h"
