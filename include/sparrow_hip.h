@@ -1031,6 +1031,32 @@ int sprk_train_fm_fit(const sprk_train_fm_model* model, const int32_t* ids, cons
                       int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
                       float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Training DIN: an attention unit ([h - c | h | c | h c] -> Dense -> PReLU(alpha[slot]) -> Dense(1) -> sigmoid) shared over hist_len history
+ * slots, weighted sum pooling, a PReLU tail, one sigmoid; the rules of the trainers above, sparrowrecsys_amd/trainer_din.py's train_host is the
+ * definition of every bit.  sprk_train_din_model: the id columns (vocab; genre != 0: ids may be -1 = no row; table:
+ * the table the column reads -- column 0 is the candidate, columns 1 .. hist_len the history, all of table 0; tables are numbered 0 .. without a
+ * gap and the columns of one table agree in vocab and genre), emb_dim, att_hidden, per input row k of fc0 its source xsrc (an id column
+ * outside the history, -1 = a numeric, -2 = the pooled vector) and xsub (the element), the tail's widths.  params / m / v: one float vector each
+ * -- the tables in table order ([vocab][emb_dim]), att0 kernel ([4 emb_dim][att_hidden]) and bias, the attention PReLU's alpha
+ * ([hist_len][att_hidden]), att1 kernel and bias, per tail layer kernel ([in][out]), bias and alpha, the head's kernel and bias -- trained in place.
+ * Every other argument, the error word and the enqueue-only contract are those of sprk_train_fit.  n x n_cols must stay below 2^31 - 1 and
+ * batch at or below 2^28 (a schedule key holds position x 16 + column in 32 bits); one workgroup's LDS (trainer_din.lds_bytes) must fit 160 KB. */
+#define SPRK_TRAIN_DIN_MAX_COLS 16
+#define SPRK_TRAIN_DIN_MAX_LAYERS 8
+#define SPRK_TRAIN_DIN_MAX_X 256
+#define SPRK_TRAIN_DIN_MAX_WIDTH 256
+#define SPRK_TRAIN_DIN_MAX_EMB 64
+typedef struct {
+    int32_t n_cols, n_dense, emb_dim, hist_len, att_hidden, n_x, n_layers;
+    int32_t vocab[SPRK_TRAIN_DIN_MAX_COLS], genre[SPRK_TRAIN_DIN_MAX_COLS], table[SPRK_TRAIN_DIN_MAX_COLS];
+    int32_t width[SPRK_TRAIN_DIN_MAX_LAYERS];
+    int32_t xsrc[SPRK_TRAIN_DIN_MAX_X], xsub[SPRK_TRAIN_DIN_MAX_X];
+} sprk_train_din_model;
+size_t sprk_train_din_workspace_bytes(const sprk_train_din_model* model, int64_t n, int32_t batch, int32_t tile);
+int sprk_train_din_fit(const sprk_train_din_model* model, const int32_t* ids, const float* dense, const float* labels, const int32_t* order, int64_t n,
+                       int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
+                       float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 const char* sprk_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)

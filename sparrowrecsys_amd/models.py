@@ -577,7 +577,11 @@ class CTRModel:
         from . import trainer
         if type(self) is DeepFMv2:                                 # the FM graph has a trainer of its own
             from . import trainer_fm as trainer
-        fam = trainer.family_of(self)
+        return self._fit_with(trainer, trainer.family_of(self), x, y, batch_size, epochs, learning_rate, order, tile)
+
+    def _fit_with(self, trainer, fam, x, y, batch_size, epochs, learning_rate, order, tile):
+        """``fit`` behind the choice of the trainer: ``trainer`` is the module (``trainer``, ``trainer_fm``; ``trainer_din.fit`` passes
+        itself) whose ``train_device`` runs and ``fam`` its ``family_of(self)``."""
         import torch
         if not torch.cuda.is_available():
             raise RuntimeError("fit needs a HIP device: no HIP device is visible (%s.train_host is the host definition)" % trainer.__name__.rsplit(".", 1)[-1])

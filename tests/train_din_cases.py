@@ -1,0 +1,125 @@
+"""Shared cases of tests/test_train_din.py (the DIN trainer's definition against independent implementations, no GPU) and
+tests/test_gpu_train_din.py (``trainer_din.train_device`` against ``train_host``, byte for byte): small ``DIN`` models, weights, data,
+the torch restatement of the graph and the planted-structure data of the learning test."""
+import numpy as np
+
+from sparrowrecsys_amd import models as M
+from sparrowrecsys_amd import trainer_din as TD
+from tests import train_cases as TC
+
+F = np.float32
+same_bits = TC.same_bits
+
+REFERENCE_SHAPE = dict(hist_len=5, emb_dim=10, att_hidden=32, hidden=(128, 64), movies=30, users=40)
+ODD_SHAPE = dict(hist_len=3, emb_dim=3, att_hidden=5, hidden=(17, 1), movies=7, users=7)
+
+
+def model(hist_len=3, emb_dim=3, att_hidden=5, hidden=(5,), movies=7, users=5, seed=0):
+    """A ``DIN`` over tiny vocabularies (the two genre tables keep their 19 rows)."""
+    return M.DIN(seed=seed, emb_dim=emb_dim, hist_len=hist_len, att_hidden=att_hidden, hidden=hidden, movie_buckets=movies, user_buckets=users)
+
+
+def family(**kw):
+    return TD.family_of(model(**kw))
+
+
+def weights(fam, seed=0, scale=1.0):
+    """Glorot-sized kernels, small biases, table rows of unit scale, PReLU slopes on both sides of zero."""
+    rng = np.random.default_rng(seed)
+    w = {}
+    for k, shape in TD.param_shapes(fam).items():
+        if k.startswith("emb/"):
+            w[k] = (rng.standard_normal(shape) / np.sqrt(shape[1]) * scale).astype(F)
+        elif k.endswith("/kernel"):
+            lim = np.sqrt(6.0 / (shape[0] + shape[1]))
+            w[k] = (rng.uniform(-lim, lim, size=shape) * scale).astype(F)
+        elif k.endswith("/alpha"):
+            w[k] = (rng.uniform(-0.3, 0.5, size=shape) * scale).astype(F)
+        else:
+            w[k] = (rng.uniform(-0.1, 0.1, size=shape) * scale).astype(F)
+    return w
+
+
+def data(fam, n, seed=0, none_rate=0.25):
+    """``train_cases.data``: ids uniform (history id 0 included), genre columns -1 at ``none_rate``, numerics standard normal, labels fair coins."""
+    return TC.data(fam, n, seed, none_rate)
+
+
+def small(n, seed=0, **kw):
+    fam = family(**kw)
+    return (fam, weights(fam, seed)) + data(fam, n, seed)
+
+
+def torch_logit(fam, p, ids_t, dn, dtype, parts=None):
+    """The graph in torch from a dict of tensors ``p``: -> the logit ``[n]``.  PReLU as ``relu(x) - alpha relu(-x)`` (Keras' form)."""
+    import torch
+    import torch.nn.functional as Fn
+    T = fam.hist_len
+    prelu = lambda z, al: Fn.relu(z) - al * Fn.relu(-z)
+    rows = []
+    for c in range(len(fam.columns)):
+        ok = (ids_t[:, c] >= 0).to(dtype)[:, None]
+        rows.append(Fn.embedding(ids_t[:, c].clamp(min=0), p[fam.tables[fam.table_of[c]]]) * ok)
+    c = rows[0]
+    h = torch.stack(rows[1:T + 1], dim=1)
+    cr = c[:, None, :].expand_as(h)
+    a = torch.cat([h - cr, h, cr, h * cr], dim=2)
+    u = torch.matmul(a, p["att0/kernel"]) + p["att0/bias"]
+    ya = prelu(u, p["att_prelu/alpha"][None])
+    s = torch.sigmoid(torch.matmul(ya, p["att1/kernel"])[:, :, 0] + p["att1/bias"][0])
+    pooled = (h * s[:, :, None]).sum(dim=1)
+    x = torch.stack([dn[:, sub] if src == TD.SRC_NUMERIC else pooled[:, sub] if src == TD.SRC_POOLED else rows[src][:, sub]
+                     for src, sub in zip(fam.xsrc, fam.xsub)], dim=1)
+    for i in range(len(fam.hidden)):
+        x = prelu(Fn.linear(x, p["fc%d/kernel" % i].t(), p["fc%d/bias" % i]), p["fc%d_prelu/alpha" % i][None])
+    if parts is not None:
+        parts.update(u=u, s=s, pooled=pooled)
+    return Fn.linear(x, p["head/kernel"].t(), p["head/bias"])[:, 0]
+
+
+def torch_gradients(fam, w, ids, dense, labels, dtype):
+    """Mean binary cross-entropy through the logit, autograd in ``dtype`` on the CPU.  -> ``({name: gradient as float64 numpy}, p)``."""
+    import torch
+    import torch.nn.functional as Fn
+    p = {k: torch.tensor(np.asarray(v, dtype=np.float64), dtype=dtype, requires_grad=True) for k, v in w.items()}
+    logit = torch_logit(fam, p, torch.from_numpy(np.asarray(ids, dtype=np.int64)), torch.tensor(np.asarray(dense, dtype=np.float64), dtype=dtype), dtype)
+    loss = Fn.binary_cross_entropy_with_logits(logit, torch.tensor(np.asarray(labels, dtype=np.float64), dtype=dtype), reduction="mean")
+    loss.backward()
+    return {k: (v.grad.detach().numpy().astype(np.float64) if v.grad is not None else np.zeros(v.shape)) for k, v in p.items()}, torch.sigmoid(logit).detach().numpy()
+
+
+def torch_sample_terms(fam, w, ids, dense, labels, name):
+    """The float64 run's terms of one tensor's gradient: ``[n, *shape]``, sample ``i``'s own contribution ``d(loss_i / n) / d tensor``."""
+    import torch
+    import torch.nn.functional as Fn
+    p = {k: torch.tensor(np.asarray(v, dtype=np.float64), dtype=torch.float64, requires_grad=True) for k, v in w.items()}
+    logit = torch_logit(fam, p, torch.from_numpy(np.asarray(ids, dtype=np.int64)), torch.tensor(np.asarray(dense, dtype=np.float64)), torch.float64)
+    each = Fn.binary_cross_entropy_with_logits(logit, torch.tensor(np.asarray(labels, dtype=np.float64)), reduction="none") / len(labels)
+    return np.stack([torch.autograd.grad(each[i], p[name], retain_graph=True)[0].numpy() for i in range(len(labels))])
+
+
+# ---- the learning test: 24 movies in 6 clusters (id mod 6), 5 history slots and a candidate drawn uniformly; the label is a Bernoulli of 0.95
+# ---- where the candidate's cluster is among the history's clusters and of 0.05 where it is not.  Which movies a user has seen says nothing
+# ---- by itself and the candidate says nothing by itself: only the comparison of the candidate with every slot does.  Users, genres and the seven
+# ---- numerics are noise.  8 192 training and 2 048 held-out rows; one seed.
+PLANTED_SEED, PLANTED_MOVIES, PLANTED_CLUSTERS, PLANTED_USERS, PLANTED_TRAIN, PLANTED_TEST = 31415, 24, 6, 50, 8192, 2048
+
+
+def planted():
+    """-> ``(train, test)``, each ``(ids [n, 9] int32, dense [n, 7] float32, labels [n] float32)``."""
+    rng = np.random.default_rng(PLANTED_SEED)
+    n = PLANTED_TRAIN + PLANTED_TEST
+    movies = rng.integers(0, PLANTED_MOVIES, size=(n, 6))
+    match = (movies[:, 1:] % PLANTED_CLUSTERS == movies[:, :1] % PLANTED_CLUSTERS).any(axis=1)
+    y = (rng.random(n) < np.where(match, 0.95, 0.05)).astype(F)
+    ids = np.concatenate([movies, rng.integers(0, PLANTED_USERS, size=(n, 1)), rng.integers(-1, 19, size=(n, 2))], axis=1).astype(np.int32)
+    dense = rng.standard_normal((n, 7)).astype(F)
+    k = PLANTED_TRAIN
+    return (ids[:k], dense[:k], y[:k]), (ids[k:], dense[k:], y[k:])
+
+
+def planted_model(seed=0):
+    """DIN at the reference widths (T 5, D 10, H 32, tail (128, 64)) over the planted vocabularies, the reference initialisers."""
+    mo = M.DIN(seed=seed, movie_buckets=PLANTED_MOVIES, user_buckets=PLANTED_USERS)
+    mo.set_weights(mo.init_weights(seed, trained_like=False))
+    return mo
