@@ -1057,6 +1057,29 @@ int sprk_train_din_fit(const sprk_train_din_model* model, const int32_t* ids, co
                        int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
                        float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Training Wide&Deep: EmbeddingMLP's graph (sprk_train_fit's) plus a wide term in the head whose parameter row is FingerprintCat64(0xDECAFCAFFE,
+ * ids[cross_a], ids[cross_b]) mod cross_buckets; the rules of the trainers above, sparrowrecsys_amd/trainer_wide.py's train_host is the definition
+ * of every bit.  sprk_train_wide_model: sprk_train_model's fields, where the LAST id column (cross_b = n_cols - 1) has a
+ * vocabulary and no table and no input row names it, and cross_a < cross_b names a column with a table; cross_dim == 0: the cross is an indicator
+ * and its cross_buckets weights are rows [H, H + cross_buckets) of the head's kernel (H = the last hidden width); cross_dim > 0: the cross reads a
+ * table [cross_buckets][cross_dim] of its own and the head's kernel has H + cross_dim rows.  params / m / v: one float vector each -- the tables of
+ * columns 0 .. n_cols - 2 ([vocab][emb_dim]), per hidden layer its kernel ([in][out]) and bias, the head's BIAS, the head's kernel, then (cross_dim
+ * > 0) the cross table -- trained in place.  Every other argument, the error word and the enqueue-only contract are those of sprk_train_fit.
+ * n x n_cols and (all tables' rows + cross_buckets) must stay below 2^31 - 1; tile x (n_x + the widths + 2 x the widest + cross_dim) floats must
+ * fit 160 KB. */
+#define SPRK_TRAIN_WIDE_MAX_CROSS_DIM 64
+typedef struct {
+    int32_t n_cols, n_dense, emb_dim, n_x, n_layers;
+    int32_t vocab[SPRK_TRAIN_MAX_COLS], genre[SPRK_TRAIN_MAX_COLS];
+    int32_t width[SPRK_TRAIN_MAX_LAYERS];
+    int32_t xcol[SPRK_TRAIN_MAX_X], xsub[SPRK_TRAIN_MAX_X];
+    int32_t cross_a, cross_b, cross_buckets, cross_dim;
+} sprk_train_wide_model;
+size_t sprk_train_wide_workspace_bytes(const sprk_train_wide_model* model, int64_t n, int32_t batch, int32_t tile);
+int sprk_train_wide_fit(const sprk_train_wide_model* model, const int32_t* ids, const float* dense, const float* labels, const int32_t* order, int64_t n,
+                        int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
+                        float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 const char* sprk_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)

@@ -1,0 +1,377 @@
+"""``trainer_wide.train_device`` (``sprk_train_wide_fit``, csrc/k_train_wide.h) against its definition ``trainer_wide.train_host``: every
+weight, every ``m``, every ``v``, every ``p`` of the last epoch, accuracy and both AUCs of every epoch byte for byte, the loss within
+``max(N, 64) 2^-50`` relative (``-m gpu``).  Tiny vocabularies and at most 300 rows, but for the end-to-end test's few thousand ratings."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from sparrowrecsys_amd import _lib as L
+from sparrowrecsys_amd import models as M
+from sparrowrecsys_amd import trainer as T
+from sparrowrecsys_amd import trainer_wide as TW
+from tests import metrics_cases as MC
+from tests import train_wide_cases as TWC
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+same = TWC.same_bits
+FORMS = [0, 3]                                                         # cross_dim: the indicator form and the embedding form
+
+
+@pytest.fixture(scope="module")
+def torch():
+    import torch as t
+    assert t.cuda.is_available(), "gpu tests need a HIP device"
+    return t
+
+
+def host_of(d):
+    return {k: v.cpu().numpy() for k, v in d.items()}
+
+
+def both(fam, w, ids, dense, y, **kw):
+    """Host and device fits of one input: asserts the equalities of the module docstring, -> the host's result."""
+    want = TW.train_host(fam, w, ids, dense, y, **kw)
+    got = TW.train_device(fam, w, ids, dense, y, **kw)
+    assert got.step == want.step and len(got.history) == len(want.history)
+    for name, g, h in (("weight", got.weights, want.weights), ("m", got.m, want.m), ("v", got.v, want.v)):
+        g = host_of(g)
+        for k in TW.param_names(fam):
+            assert same(g[k], h[k]), (name, k, np.flatnonzero(g[k].reshape(-1).view(np.uint32) != h[k].reshape(-1).view(np.uint32))[:8])
+    p = got.p.cpu().numpy()
+    assert same(p, want.p), np.flatnonzero(p.view(np.uint32) != want.p.view(np.uint32))[:8]
+    for e, (a, b) in enumerate(zip(got.history, want.history)):
+        assert a[1:] == b[1:] or (np.isnan(a[2:]).all() and np.isnan(b[2:]).all() and a[1] == b[1]), (e, a, b)
+        assert abs(a[0] - b[0]) <= MC.loss_bound(len(y)) * abs(b[0]), (e, a[0], b[0])
+    return want
+
+
+def wide_rows(fam, d):
+    """The cross's trained rows of a dict of arrays: ``head/kernel[H:]`` or ``emb/cross``."""
+    return d["emb/cross"] if fam.cross_dim else d["head/kernel"][fam.widths[-1]:]
+
+
+# ---------------------------------------------------------------- rows and batches
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+@pytest.mark.parametrize("n,batch,tile", [(1, 4, 8), (7, 16, 8), (8, 16, 8), (9, 16, 8), (50, 12, 8), (23, 1, 8), (40, 12, 32), (33, 32, 32)])
+def test_row_counts_and_batching(torch, n, batch, tile, cross_dim):
+    """N = 1, tile - 1, tile, tile + 1; B no multiple of the tile; a short last batch; B = 1; one batch only; three epochs; both forms."""
+    fam, w, ids, dense, y = TWC.small(n, seed=n, cross_dim=cross_dim)
+    want = both(fam, w, ids, dense, y, batch_size=batch, epochs=3, tile=tile)
+    assert want.step == 3 * ((n + batch - 1) // batch)
+    assert not same(wide_rows(fam, want.weights), wide_rows(fam, w))
+
+
+@pytest.mark.parametrize("as_tensor", [False, True])
+def test_order(torch, as_tensor):
+    fam, w, ids, dense, y = TWC.small(50, seed=4)
+    order = np.random.default_rng(1).permutation(50)
+    want = TW.train_host(fam, w, ids, dense, y, batch_size=12, epochs=3, tile=8, order=order)
+    plain = TW.train_host(fam, w, ids, dense, y, batch_size=12, epochs=3, tile=8)
+    assert not same(want.weights["head/kernel"], plain.weights["head/kernel"])
+    dev = lambda a: torch.from_numpy(a).cuda()
+    got = TW.train_device(fam, w, dev(ids), dev(dense), dev(y), batch_size=12, epochs=3, tile=8, order=dev(order) if as_tensor else order)
+    assert all(same(host_of(got.weights)[k], want.weights[k]) for k in want.weights)
+    assert same(got.p.cpu().numpy(), want.p) and [h[1:] for h in got.history] == [h[1:] for h in want.history]
+    with pytest.raises(ValueError, match="permutation"):
+        TW.train_device(fam, w, ids, dense, y, order=dev(np.zeros(50, dtype=np.int64)) if as_tensor else np.zeros(50, dtype=np.int64))
+
+
+# ---------------------------------------------------------------- the cross
+
+@pytest.mark.parametrize("cross_dim", [0, 1, 3, 4, 32, TW.MAX_CROSS_DIM])
+def test_cross_widths(torch, cross_dim):
+    fam, w, ids, dense, y = TWC.small(40, seed=20 + cross_dim, cross_dim=cross_dim)
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+@pytest.mark.parametrize("buckets", [1, 2, 11, 65537])
+def test_cross_buckets(torch, buckets, cross_dim):
+    """1: every sample shares the row, a run as long as the batch; 65 537: nearly every row is untouched -- its bit in the bitmap is
+    clear -- and keeps its initial bits with zero moments (the next test runs the same rows under a capped grid)."""
+    fam, w, ids, dense, y = TWC.small(40, seed=30 + buckets % 7, cross_buckets=buckets, cross_dim=cross_dim)
+    want = both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+    hit = np.zeros(buckets, dtype=bool)
+    hit[TW.buckets_of(fam, ids)] = True
+    assert hit.all() if buckets <= 2 else not hit.all()
+    assert same(wide_rows(fam, want.weights)[~hit], wide_rows(fam, w)[~hit]) and not wide_rows(fam, want.m)[~hit].any()
+    assert wide_rows(fam, want.v)[hit].all()
+
+
+def test_cross_adam_grid_goes_past_one_round(torch, monkeypatch):
+    """65 537 x 3 cross elements under a grid capped at 64 workgroups of 256 threads: the cross Adam's grid-stride loop goes round."""
+    monkeypatch.setenv("SPRK_FE_MAX_GRID", "64")
+    fam, w, ids, dense, y = TWC.small(40, seed=31, cross_buckets=65537, cross_dim=3)
+    assert 65537 * 3 > 64 * 256
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+
+
+# ---------------------------------------------------------------- ids
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+def test_every_genre_id_none(torch, cross_dim):
+    fam, w, ids, dense, y = TWC.small(40, seed=3, cross_dim=cross_dim)
+    genre = [c for c, (_, kind, _) in enumerate(fam.columns) if kind == "genre"]
+    assert len(genre) == 8
+    ids[:, genre] = -1
+    got = both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+    for c in genre:
+        assert same(got.weights[fam.tables[c]], w[fam.tables[c]]) and not got.v[fam.tables[c]].any()
+    assert not same(got.weights["emb/userId"], w["emb/userId"])
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+def test_one_movie_in_every_column(torch, cross_dim):
+    """All samples carry movie 3 as ``movieId`` and as ``userRatedMovie1``: one bucket, one cross run per batch; ``userRatedMovie1 ==
+    movieId`` throughout."""
+    fam, w, ids, dense, y = TWC.small(48, seed=2, cross_dim=cross_dim)
+    ids[:, fam.cross_a] = ids[:, fam.cross_b] = 3
+    got = both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+    b = int(TW.cross_bucket_host(np.array([3]), np.array([3]), 11)[0])
+    keep = np.arange(11) != b
+    assert same(wide_rows(fam, got.weights)[keep], wide_rows(fam, w)[keep]) and not same(wide_rows(fam, got.weights)[b], wide_rows(fam, w)[b])
+    keep = np.arange(7) != 3
+    assert same(got.weights["emb/movieId"][keep], w["emb/movieId"][keep])
+
+
+def test_rated_movie_equal_to_the_movie(torch):
+    fam, w, ids, dense, y = TWC.small(40, seed=5)
+    ids[:, fam.cross_b] = ids[:, fam.cross_a]
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+
+
+# ---------------------------------------------------------------- arithmetic edges
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+@pytest.mark.parametrize("bias", [100.0, -100.0])
+def test_a_saturated_head(torch, bias, cross_dim):
+    fam, w, ids, dense, y = TWC.small(40, seed=7, cross_dim=cross_dim)
+    w["head/bias"][0] = bias
+    got = both(fam, w, ids, dense, y, batch_size=16, epochs=1, tile=8)
+    assert set(np.unique(got.p).tolist()) <= ({1.0} if bias > 0 else {0.0}) and set(y.tolist()) == {0.0, 1.0}
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+@pytest.mark.parametrize("scale", [1e-20, 1e-39])
+def test_tiny_and_subnormal_weights(torch, scale, cross_dim):
+    fam, w, ids, dense, y = TWC.small(40, seed=8, hidden=(6, 4), cross_dim=cross_dim)
+    w = {k: (v.astype(np.float64) * scale).astype(F) for k, v in w.items()}
+    tiny = np.finfo(F).tiny
+    got = both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+    sub = lambda d: any(((np.abs(a) > 0) & (np.abs(a) < tiny)).any() for a in d.values())
+    assert sub(got.m) if scale == 1e-20 else sub(w)
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+def test_batches_beyond_the_lds_sort_capacity(torch, monkeypatch, cross_dim):
+    """SPRK_FE_SORT_CAP=64: a batch's 40 x 11 entries, the cross entries among them, take the chunked sort and the merge passes."""
+    monkeypatch.setenv("SPRK_FE_SORT_CAP", "64")
+    fam, w, ids, dense, y = TWC.small(100, seed=9, cross_dim=cross_dim)
+    both(fam, w, ids, dense, y, batch_size=40, epochs=2, tile=8)
+
+
+@pytest.mark.parametrize("grid", ["3", "1"])
+def test_grids_capped(torch, monkeypatch, grid):
+    """SPRK_FE_MAX_GRID 3 and 1 at 300 rows of the reference shape: every grid-stride loop of the buckets, the schedule and the three Adam
+    kernels goes round."""
+    monkeypatch.setenv("SPRK_FE_MAX_GRID", grid)
+    fam, w, ids, dense, y = TWC.small(300, seed=10, **TWC.REFERENCE_SHAPE)
+    assert len(y) > 256 and fam.cross_buckets > 3 * 256
+    both(fam, w, ids, dense, y, batch_size=128, epochs=1, tile=8)
+
+
+# ---------------------------------------------------------------- the C ABI: errors, memory, streams
+
+GUARD = 64
+
+
+def raw_fit(torch, fam, w, ids, dense, y, batch, tile, epochs, stream=None):
+    """``sprk_train_wide_fit`` itself: parameters, moments, p and the workspace each inside guard bands of a fixed pattern, the workspace
+    exactly as large as ``sprk_train_wide_workspace_bytes`` reports.  -> (rc, params, m, v, p, error word, guards intact)."""
+    lib = L.load_library()
+    dev = torch.device("cuda")
+    n = len(y)
+    flat = TW._flatten(fam, w, dev)
+    ms = TW._model_struct(fam)
+    need = int(lib.sprk_train_wide_workspace_bytes(C.byref(ms), n, batch, tile))
+    assert need > 0 and need % 16 == 0
+
+    def banded(count, dtype, fill=None):
+        buf = torch.full((count + 2 * GUARD,), 0x5A if dtype == torch.uint8 else -7, dtype=dtype, device=dev)
+        if fill is not None:
+            buf[GUARD:GUARD + count] = fill
+        return buf
+    params, m, v = banded(flat.numel(), torch.float32, flat), banded(flat.numel(), torch.float32, 0.0), banded(flat.numel(), torch.float32, 0.0)
+    p = banded(max(epochs, 1) * n, torch.float32, 0.0)
+    ws = banded(need, torch.uint8)
+    steps = (n + batch - 1) // batch
+    alphas = torch.from_numpy(np.array([T.adam_alpha(0.001, t + 1) for t in range(epochs * steps)] + [0.0], dtype=F)).to(dev)
+    word = torch.full((1,), -1, dtype=torch.int64, device=dev)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    t_ids, t_dense, t_y = up(ids), up(dense), up(y)
+    c1, c2, eps = T.adam_constants()
+    at = lambda b, size: C.c_void_p(b.data_ptr() + GUARD * size)
+    rc = lib.sprk_train_wide_fit(C.byref(ms), C.c_void_p(t_ids.data_ptr()), C.c_void_p(t_dense.data_ptr()), C.c_void_p(t_y.data_ptr()), None,
+                                 n, batch, tile, epochs, C.c_void_p(alphas.data_ptr()), float(c1), float(c2), float(eps), at(params, 4), at(m, 4), at(v, 4), at(p, 4),
+                                 C.c_void_p(word.data_ptr()), at(ws, 1), need, C.c_void_p(stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream))
+    (stream or torch.cuda.current_stream()).synchronize()
+    intact = all(bool((b[:GUARD] == b[0]).all()) and bool((b[-GUARD:] == b[0]).all()) and (float(b[0]) in (-7.0, 90.0)) for b in (params, m, v, p, ws))
+    cut = lambda b: b[GUARD:-GUARD].cpu().numpy()
+    return rc, cut(params), cut(m), cut(v), cut(p), int(word.cpu()[0]), intact
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+def test_guard_bands_side_stream_exact_workspace(torch, cross_dim):
+    fam, w, ids, dense, y = TWC.small(50, seed=10, cross_dim=cross_dim)
+    want = TW.train_host(fam, w, ids, dense, y, batch_size=12, epochs=2, tile=8)
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    rc, params, m, v, p, word, intact = raw_fit(torch, fam, w, ids, dense, y, 12, 8, 2, stream=side)
+    assert rc == 0 and word == -1 and intact
+    flat = lambda d: np.concatenate([d[k].reshape(-1) for k in TW.param_names(fam)])
+    assert same(params, flat(want.weights)) and same(m, flat(want.m)) and same(v, flat(want.v))
+    assert same(p[50:], want.p)
+    lib = L.load_library()
+    ms = TW._model_struct(fam)
+    need = int(lib.sprk_train_wide_workspace_bytes(C.byref(ms), 50, 12, 8))
+    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    word_t = torch.full((1,), -1, dtype=torch.int64, device="cuda")
+    f = torch.zeros(TW._flatten(fam, w, torch.device("cuda")).numel(), device="cuda")
+    z = C.c_void_p(f.data_ptr())
+    rc = lib.sprk_train_wide_fit(C.byref(ms), z, z, z, None, 50, 12, 8, 1, z, 0.1, 0.001, 1e-7, z, z, z, z, C.c_void_p(word_t.data_ptr()), C.c_void_p(ws.data_ptr()), need - 1, None)
+    assert rc == L.EINVAL and b"sprk_train_wide_workspace_bytes" in lib.sprk_last_error()
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+def test_each_error_word_and_no_parameter_moves(torch, cross_dim):
+    fam, w, ids, dense, y = TWC.small(40, seed=11, cross_dim=cross_dim)
+    flat0 = np.concatenate([w[k].reshape(-1) for k in TW.param_names(fam)])
+
+    def check(kind, row, message, ids=ids, dense=dense, y=y):
+        rc, params, m, v, p, word, intact = raw_fit(torch, fam, w, ids, dense, y, 16, 8, 2)
+        assert rc == 0 and intact and word == (kind << 32 | row), (word >> 32, word & 0xffffffff)
+        assert same(params, flat0) and not m.any() and not v.any() and not p.any()
+        for fit in (TW.train_device, TW.train_host):
+            with pytest.raises(ValueError, match=message):
+                fit(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+    movie, genre = fam.cross_a, 0
+    assert fam.columns[genre][1] == "genre"
+    bad = ids.copy(); bad[30, movie] = 7; bad[12, movie] = -1; bad[20, genre] = -2
+    check(T.ERR_ID, 12, "samples row 12: an id outside", ids=bad)
+    bad = ids.copy(); bad[25, fam.cross_b] = 7; bad[9, fam.cross_b] = -1
+    check(T.ERR_ID, 9, "samples row 9: an id outside", ids=bad)
+    bad = ids.copy(); bad[25, fam.cross_b] = 7
+    check(T.ERR_ID, 25, "samples row 25: an id outside", ids=bad)
+    bad = dense.copy(); bad[9, 1] = np.inf; bad[3, 0] = np.nan
+    check(T.ERR_NUMERIC, 3, "samples row 3: a numeric", dense=bad)
+    bad = y.copy(); bad[7] = np.nan; bad[39] = -np.inf
+    check(T.ERR_LABEL, 7, "samples row 7: the label", y=bad)
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+def test_two_fits_give_the_same_bytes_and_a_fit_continues(torch, cross_dim):
+    fam, w, ids, dense, y = TWC.small(200, seed=12, hidden=(65, 7), cross_dim=cross_dim)
+    a = TW.train_device(fam, w, ids, dense, y, batch_size=48, epochs=2, tile=8)
+    b = TW.train_device(fam, w, ids, dense, y, batch_size=48, epochs=2, tile=8)
+    for x, z in ((a.weights, b.weights), (a.m, b.m), (a.v, b.v)):
+        assert all(same(x[k].cpu().numpy(), z[k].cpu().numpy()) for k in x)
+    assert same(a.p.cpu().numpy(), b.p.cpu().numpy()) and a.history == b.history
+    one = TW.train_device(fam, w, ids, dense, y, batch_size=48, epochs=1, tile=8)
+    two = TW.train_device(fam, one.weights, ids, dense, y, batch_size=48, epochs=1, tile=8, state=(one.m, one.v, one.step))
+    assert two.step == a.step and all(same(two.weights[k].cpu().numpy(), a.weights[k].cpu().numpy()) and same(two.v[k].cpu().numpy(), a.v[k].cpu().numpy()) for k in w)
+    none = TW.train_device(fam, w, ids, dense, y, epochs=0)
+    assert none.step == 0 and none.history == [] and all(same(none.weights[k].cpu().numpy(), w[k]) for k in w)
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+def test_lds_refusal_in_words(torch, cross_dim):
+    fam, w, ids, dense, y = TWC.small(20, seed=13, cross_dim=cross_dim)
+    top = TW.LDS_BYTES // TW.lds_bytes(fam, 1)
+    assert TW.lds_bytes(fam, top) <= TW.LDS_BYTES < TW.lds_bytes(fam, top + 1)
+    with pytest.raises(ValueError, match="tile = %d needs %d bytes of LDS" % (top + 1, TW.lds_bytes(fam, top + 1))):
+        TW.train_device(fam, w, ids, dense, y, batch_size=20, epochs=1, tile=top + 1)
+
+
+@pytest.mark.parametrize("cross_dim", [0, 32])
+def test_a_step_of_more_than_48_kb_of_lds(torch, cross_dim):
+    """The reference shape at tile 32: above the 48 KB a kernel gets without asking."""
+    fam, w, ids, dense, y = TWC.small(40, seed=14, cross_dim=cross_dim, **TWC.REFERENCE_SHAPE)
+    assert 48 * 1024 < TW.lds_bytes(fam, 32) <= TW.LDS_BYTES
+    both(fam, w, ids, dense, y, batch_size=40, epochs=2, tile=32)
+
+
+# ---------------------------------------------------------------- trainer_wide.fit
+
+def _ratings_model(cross_dim=0, buckets=1000):
+    from tests import featureeng_cases as cases
+    return M.WideNDeep(seed=3, movie_buckets=cases.N_MOVIES, user_buckets=cases.N_USERS, hidden=(32, 16), cross_buckets=buckets, cross_dim=cross_dim)
+
+
+@pytest.mark.parametrize("cross_dim", [0, 4])
+def test_fit_on_a_dict_and_on_batches(torch, cross_dim):
+    """``trainer_wide.fit`` on a dict of host columns and on an iterable of ``(features, labels)`` batches: the history and the weights
+    are ``train_host``'s, and ``predict`` serves the trained weights; ``WideNDeep.fit`` itself still refuses."""
+    from sparrowrecsys_amd import featureeng as FE
+    from tests import featureeng_cases as cases
+    cols = FE.samples_host(cases.synthetic_ratings(), cases.synthetic_movies(), 5, n_users=cases.N_USERS, n_movies=cases.N_MOVIES)
+    y = np.asarray(cols["label"], dtype=F)
+    a, b, ref = _ratings_model(cross_dim), _ratings_model(cross_dim), _ratings_model(cross_dim)
+    ids, dense = ref.pack(cols)
+    want = TW.train_host(TW.family_of(ref), ref.weights, ids, dense, y, batch_size=128, epochs=1, learning_rate=0.01)
+    h_a = TW.fit(a, cols, batch_size=128, epochs=1, learning_rate=0.01)
+    half = len(y) // 2
+    feats = {k: v for k, v in cols.items() if k != "label"}
+    h_b = TW.fit(b, [({k: v[:half] for k, v in feats.items()}, y[:half]), ({k: v[half:] for k, v in feats.items()}, y[half:])], batch_size=128, epochs=1, learning_rate=0.01)
+    for model, h in ((a, h_a), (b, h_b)):
+        assert all(same(model.weights[k], want.weights[k]) for k in want.weights)
+        assert [e[1:] for e in h] == [e[1:] for e in want.history] and abs(h[0][0] - want.history[0][0]) <= MC.loss_bound(len(y)) * want.history[0][0]
+    assert not same(a.weights["head/kernel"], ref.weights["head/kernel"]) and a._fit_state[2] == want.step
+    before, served = ref.predict(cols)[:, 0], a.predict(cols)[:, 0]
+    ref.set_weights(want.weights)
+    assert same(served, ref.predict(cols)[:, 0]) and not same(served, before)
+    with pytest.raises(NotImplementedError, match=r"NeuralCF\(arch=1\) and EmbeddingMLP"):
+        a.fit(cols)
+
+
+def test_ratings_to_recommendations(torch):
+    """3 000 structured ratings (tests/train_wide_cases.py): featureeng.build -> split(mode="time") -> trainer_wide.fit(train.columns) ->
+    evaluate_device(test.columns) -> recommend.  The weights are ``train_host``'s and the held-out AUC after the fit exceeds the one
+    before it (the host definition goes 0.50 -> 0.90 on these rows).  A second fit continues; run at a learning rate of 1e-9 -- under
+    which Adam moves a weight by at most 3.2e-9 a step, below what changes a probability by 1e-6 -- its epoch's ``p`` are the training
+    forward's probabilities under the served weights, and ``predict`` on the same rows agrees with them within 1e-4, the bound the
+    forward engine is held to against the float32 graph."""
+    from sparrowrecsys_amd import featureeng as FE
+    from tests import featureeng_cases as cases
+    built = FE.build(TWC.structured_ratings(), cases.synthetic_movies(), 5, n_users=cases.N_USERS, n_movies=cases.N_MOVIES)
+    train, test = built.split(mode="time", sample=1.0)
+    model, other = _ratings_model(), _ratings_model()
+    start = {k: v.copy() for k, v in model.weights.items()}
+    auc_before = model.evaluate_device(test.columns)[2]
+    history = TW.fit(model, train.columns, batch_size=128, epochs=3, learning_rate=0.01)
+    tcols = train.to_host()
+    ids, dense = other.pack(tcols)
+    y = np.asarray(tcols["label"], dtype=F)
+    fam = TW.family_of(other)
+    want = TW.train_host(fam, start, ids, dense, y, batch_size=128, epochs=3, learning_rate=0.01)
+    assert len(y) > 2000 and all(same(model.weights[k], want.weights[k]) for k in want.weights)
+    assert not same(model.weights["head/kernel"][16:], start["head/kernel"][16:])
+    assert [h[1:] for h in history] == [h[1:] for h in want.history] and len(history) == 3
+    other.set_weights(want.weights)
+    after = model.evaluate_device(test.columns)
+    print("held-out AUC %.4f -> %.4f over %d training rows" % (auc_before, after[2], len(y)))
+    assert after == other.evaluate_device(test.columns) and after[2] > auc_before
+    store = built.store()
+    users, cand = np.array([30, 12, 8, 1, 17]), np.arange(1, 116, 2)
+    got = model.recommend(store, users, cand, 10)
+    assert got == other.recommend(store, users, cand, 10) and len(got[0]) == 10
+    served = model.predict(tcols)[:, 0]
+    still = TW.train_device(fam, model.weights, ids, dense, y, batch_size=128, epochs=1, learning_rate=1e-9, state=model._fit_state)
+    gap = float(np.abs(served.astype(np.float64) - still.p.cpu().numpy()).max())
+    print("max |predict - the epoch's p| = %.3e" % gap)
+    assert gap <= 1e-4
+    again = TW.fit(model, train.columns, batch_size=128, epochs=1, learning_rate=0.01)
+    cont = TW.train_host(fam, want.weights, ids, dense, y, batch_size=128, epochs=1, learning_rate=0.01, state=(want.m, want.v, want.step))
+    assert all(same(model.weights[k], cont.weights[k]) for k in cont.weights) and again[0][1:] == cont.history[0][1:]
