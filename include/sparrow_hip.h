@@ -1080,6 +1080,36 @@ int sprk_train_wide_fit(const sprk_train_wide_model* model, const int32_t* ids, 
                         int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
                         float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
 
+/* trainer_pair.fit for the pair-dot DeepFM (the reference's DeepFM.py): first-order weights that are rows of the head's kernel, n_pairs explicit dots
+ * of FM table rows, a deep stack over deep-only tables (or the FM tables: shared != 0) and the numerics, one sigmoid; the rules of the trainer above,
+ * sparrowrecsys_amd/trainer_pair.py's train_host is the definition of every bit.
+ * sprk_train_pair_model: the fields (vocab; genre != 0: ids may be -1 = no row; fo_off: the field's first row in the head's kernel -- the blocks tile
+ * its first sum(vocab) rows), the pairs (pair_a[p], pair_b[p]: field indices, the same one twice is legal), deep_col[j] = the field of deep table j
+ * (distinct), the hidden widths, and per row k < n_x of the first deep kernel xsrc[k] = the deep table it reads (-1: a numeric) and xsub[k] = the
+ * element of that table's row or the numeric's index: every element of every deep table's row and every numeric once, n_x = n_deep emb_dim + n_dense.
+ * params / m / v: one float vector each -- the FM tables in field order ([vocab][emb_dim]), the deep tables in deep_col order (absent when shared),
+ * per hidden layer its kernel ([in][out]) and bias, the head's BIAS, then the head's kernel ([sum(vocab) + n_pairs + last width]) -- trained in
+ * place.  Every other argument, the error word and the enqueue-only contract are those of sprk_train_fit.  n x n_fields must stay below 2^31 - 1;
+ * one workgroup's LDS (trainer_pair.lds_bytes) must fit 160 KB.  A NaN that reaches p, a parameter, m or v is stored as 0x7fc00000. */
+#define SPRK_TRAIN_PAIR_MAX_FIELDS 8
+#define SPRK_TRAIN_PAIR_MAX_PAIRS 32
+#define SPRK_TRAIN_PAIR_MAX_LAYERS 8
+#define SPRK_TRAIN_PAIR_MAX_WIDTH 256
+#define SPRK_TRAIN_PAIR_MAX_X 256
+#define SPRK_TRAIN_PAIR_MAX_DIM 64
+typedef struct {
+    int32_t n_fields, n_dense, emb_dim, n_pairs, n_deep, shared, n_x, n_layers;
+    int32_t vocab[SPRK_TRAIN_PAIR_MAX_FIELDS], genre[SPRK_TRAIN_PAIR_MAX_FIELDS], fo_off[SPRK_TRAIN_PAIR_MAX_FIELDS];
+    int32_t pair_a[SPRK_TRAIN_PAIR_MAX_PAIRS], pair_b[SPRK_TRAIN_PAIR_MAX_PAIRS];
+    int32_t deep_col[SPRK_TRAIN_PAIR_MAX_FIELDS];
+    int32_t width[SPRK_TRAIN_PAIR_MAX_LAYERS];
+    int32_t xsrc[SPRK_TRAIN_PAIR_MAX_X], xsub[SPRK_TRAIN_PAIR_MAX_X];
+} sprk_train_pair_model;
+size_t sprk_train_pair_workspace_bytes(const sprk_train_pair_model* model, int64_t n, int32_t batch, int32_t tile);
+int sprk_train_pair_fit(const sprk_train_pair_model* model, const int32_t* ids, const float* dense, const float* labels, const int32_t* order, int64_t n,
+                        int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
+                        float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 const char* sprk_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)

@@ -567,6 +567,7 @@ class CTRModel:
         defaults) on the device, from the model's CURRENT weights (``init_weights(seed, trained_like=False)`` gives the reference
         initialisers), for ``NeuralCF(arch=1)`` and ``EmbeddingMLP``; ``trainer.train_host`` defines every bit (DESIGN.md section 5.12);
         and for ``DeepFMv2``, through ``trainer_fm`` with a ``train_host`` of its own under the same rules (section 5.13).
+        The pair-dot ``DeepFM`` is trained through ``trainer_pair.fit(model, x, ...)``, which takes these arguments (section 5.21).
         ``x`` is what ``evaluate`` takes: a dict of columns with ``"label"`` (or ``y``) -- ``featureeng.DeviceSamples.columns`` straight
         from HBM --, or an iterable of ``(features, labels)`` batches, which are concatenated.  Deviations from the reference's script:
         ``batch_size`` defaults to 4096, not 12 (12 works: it is a sequential chain of 1.6 M steps per epoch), and rows are taken in

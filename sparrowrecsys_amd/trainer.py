@@ -15,6 +15,8 @@ repeat exactly.  DESIGN.md section 5.12 has the rules and the deviations from Ke
   from ``+0``; an embedding row's gradient likewise over the samples that carry its id in that column;
 * Adam runs over every element of every parameter on every step (Keras' Adam, not LazyAdam), ``alpha_t`` in doubles on the host;
 * ids outside the vocabulary and non-finite numerics or labels are errors, found before the first step (Keras would train on NaN).
+
+The pair-dot ``DeepFM`` is trained under these rules by :mod:`trainer_pair`, whose entry is ``trainer_pair.fit(model, x, ...)``.
 """
 from __future__ import annotations
 
