@@ -230,6 +230,62 @@ template <class Ok> static bool every_batch(int32_t n_batches, Ok ok) {
 }
 }  // extern "C++"
 
+// DeepFM_v2, a call of more batches than one kernel-argument table holds: the table goes to device memory and ONE launch of
+// k_deepfm_v2_joint_many_tab scores the whole call (host_engine.h: V2JTable).  *done = false: not this way (the caller launches groups).
+static int launch_v2j_table(sprk_handle h, int32_t n_batches, const int32_t* const* ids, const float* const* dense, float* const* out, int32_t B,
+                            hipStream_t st, bool* done) {
+    *done = false;
+    const int ntpb = (B + 15) / 16;
+    long long grid = ((long long)n_batches * ntpb + V2_WAVES - 1) / V2_WAVES;
+    if (grid > h->v2_grid_cap) grid = h->v2_grid_cap;
+    // task indices are 32-bit in the kernel, and a wave looks four strides past its last task
+    if ((long long)n_batches * ntpb + 4 * grid * V2_WAVES >= (1LL << 31)) return SPRK_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); return SPRK_OK; }
+    if (cap != hipStreamCaptureStatusNone) return SPRK_OK;       // a captured launch would replay whatever the slot holds by then
+    const size_t n = (size_t)n_batches;
+    int slot = h->v2j_table_last;
+    bool same = slot >= 0 && h->v2j_table[slot].n == n && h->v2j_table[slot].stream == st;
+    if (same) {
+        const V2JBatch* last = h->v2j_table[slot].stage;
+        for (size_t i = 0; i < n && same; ++i) same = last[i].ids == ids[i] && last[i].dense == dense[i] && last[i].out == out[i];
+    }
+    if (!same) {
+        slot = h->v2j_table_last == 0 ? 1 : 0;
+        sprk_engine::V2JTable& t = h->v2j_table[slot];
+        if (!t.busy) HIP_TRY(hipEventCreateWithFlags(&t.busy, hipEventDisableTiming));
+        if (t.used) HIP_TRY(hipEventSynchronize(t.busy));        // the slot's last reader (its upload, too) has finished
+        if (t.cap < n) {
+            // (room for 4 096 batches from the start, doubling beyond: pinning host memory and hipFree cost about half a millisecond, which
+            // a caller's first long call must not pay again because a shorter one came first)
+            size_t want = t.cap ? 2 * t.cap : 4096;
+            if (want < n) want = n;
+            if (t.stage) (void)hipHostFree(t.stage);
+            if (t.dev) (void)hipFree(t.dev);
+            t.stage = nullptr; t.dev = nullptr; t.cap = 0; t.n = 0;
+            HIP_TRY(hipHostMalloc((void**)&t.stage, want * sizeof(V2JBatch), hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void**)&t.dev, want * sizeof(V2JBatch)));
+            t.cap = want;
+        }
+        t.n = 0;                                                   // (a failure below leaves no table to compare with)
+        for (size_t i = 0; i < n; ++i) t.stage[i] = V2JBatch{ids[i], dense[i], out[i], nullptr};
+        HIP_TRY(hipMemcpyAsync(t.dev, t.stage, n * sizeof(V2JBatch), hipMemcpyHostToDevice, st));
+        t.n = n;
+        t.stream = st;
+        h->v2j_table_last = slot;
+    }
+    sprk_engine::V2JTable& t = h->v2j_table[slot];
+    V2JRun jr = h->v2j_run;
+    jr.flags = 0;
+    const V2JManyTab m = {t.dev, n_batches, ntpb};
+    hipLaunchKernelGGL(kV2JVariants[h->v2j_variant].fn_many_tab, dim3((int)grid), dim3(V2_WAVES * 64), h->v2j_lds_bytes, st, jr, m, B, h->dev_err, h->v2_image);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(t.busy, st));
+    t.used = true;
+    *done = true;
+    return SPRK_OK;
+}
+
 // `many_batches` / `many_streams`: batches per launch and helper streams of THIS call (the handle itself is not touched)
 static int forward_many_impl(sprk_handle h, int32_t n_batches, const int32_t* const* ids, const float* const* dense,
                              float* const* out, int32_t B, void* workspace, size_t workspace_bytes, void* stream,
@@ -258,6 +314,12 @@ static int forward_many_impl(sprk_handle h, int32_t n_batches, const int32_t* co
         const V2JVariant& jv = kV2JVariants[h->v2j_variant];
         V2JRun jr = h->v2j_run;
         jr.flags = 0;
+        // more batches than one launch's kernel-argument table takes: one launch for the whole call, the table in device memory
+        if (n_batches > many_batches) {
+            bool done = false;
+            SPRK_TRY(launch_v2j_table(h, n_batches, ids, dense, out, B, st, &done));
+            if (done) return SPRK_OK;
+        }
         return launch_groups<V2JMany>(n_batches, many_batches, ids, dense, out, [&](V2JMany& m, int) {
             m.ntpb = ntpb;
             long long grid = ((long long)m.n * ntpb + V2_WAVES - 1) / V2_WAVES;
@@ -512,6 +574,12 @@ void sprk_destroy(sprk_handle h) {
     for (size_t i = 0; i < h->slot_ptr.size(); ++i) free_slot(h, i);
     for (const sprk_engine::DevAlloc& a : h->allocs) release(a);
     if (h->v2j_tab) (void)hipFree(h->v2j_tab);
+    for (sprk_engine::V2JTable& t : h->v2j_table) {
+        if (t.used) (void)hipEventSynchronize(t.busy);
+        if (t.stage) (void)hipHostFree(t.stage);
+        if (t.dev) (void)hipFree(t.dev);
+        if (t.busy) (void)hipEventDestroy(t.busy);
+    }
     for (int i = 0; i < 4; ++i) { if (h->many_stream[i]) (void)hipStreamDestroy(h->many_stream[i]); if (h->many_join[i]) (void)hipEventDestroy(h->many_join[i]); }
     if (h->many_fork) (void)hipEventDestroy(h->many_fork);
     delete h;

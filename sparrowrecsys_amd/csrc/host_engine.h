@@ -12,6 +12,7 @@ enum class Stage { None, DinPool, DinCols, DinFusedAttn, DienSeq, DienSeqMfma };
 // exactly that pointer (set_max_lds) and the launch paths hand it to hipLaunchKernelGGL: the compiler checks every launch against the kernel.
 typedef void (*V2JKernel)(const V2JRun, const int*, const float*, float*, int, int*, const float*);        // k_deepfm_v2_joint, k_deepfm_v2_joint1
 typedef void (*V2JManyKernel)(const V2JRun, const V2JMany, int, int*, const float*);
+typedef void (*V2JManyTabKernel)(const V2JRun, const V2JManyTab, int, int*, const float*);                 // k_deepfm_v2_joint_many_tab
 typedef void (*RowsKernel)(const RowsRun, const int*, const float*, float*, int, int*, const float*);       // k_rows_chain, k_rows_chain1
 typedef void (*RowsManyKernel)(const RowsRun, const RowsMany, int, int*, const float*);
 typedef void (*V1Kernel)(const V1Run, const int*, const float*, float*, int, int*);                         // k_deepfm_pairs, k_deepfm_pairs1
@@ -136,6 +137,21 @@ struct sprk_engine {
     float* v2j_tab = nullptr;      // small fields' LDS rows (device image)
     size_t v2j_lds_bytes = 0;
     float* v2j_big = nullptr;      // HALF: split-half rows of the big fields (device)
+    // The per-batch pointer table of a one-launch sprk_forward_many call (k_deepfm_v2_joint_many_tab; api_forward.h: launch_v2j_table).
+    // `stage` is the pinned host copy the upload reads and, afterwards, the record of what `dev` holds: a call whose pointers equal the
+    // table uploaded last on the same stream (a replayed prepared run) launches without an upload.  Two slots in alternation, and `busy`
+    // is recorded behind every launch that reads a slot: a new table waits for the slot's last reader before it overwrites either copy.
+    struct V2JTable {
+        V2JBatch* stage = nullptr;
+        V2JBatch* dev = nullptr;
+        size_t cap = 0;                   // entries both copies hold
+        size_t n = 0;                     // entries of the table in them (0: none yet)
+        hipStream_t stream = nullptr;     // the stream the upload was enqueued on
+        hipEvent_t busy = nullptr;
+        bool used = false;                // `busy` has been recorded
+    };
+    V2JTable v2j_table[2];
+    int v2j_table_last = -1;              // the slot uploaded last
     // every device allocation of finalize (dev_alloc / table_alloc below); the pointers above are views into them.  vmm_size != 0: a
     // hipMemCreate allocation mapped at a reserved range, else hipMalloc's
     struct DevAlloc { void* p; size_t vmm_size; hipMemGenericAllocationHandle_t handle; };

@@ -23,9 +23,11 @@ struct V2JVariant {
     bool half;                            // big fields on split-f16 MFMA
     V2JKernel fn;
     V2JManyKernel fn_many;
+    V2JManyTabKernel fn_many_tab;         // the per-batch pointers in device memory: any number of batches
 };
 #define V2J_VARIANT(G_BIG, NJF, HALF) \
-    {G_BIG, NJF, 1, HALF, &k_deepfm_v2_joint<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>, &k_deepfm_v2_joint_many<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>}
+    {G_BIG, NJF, 1, HALF, &k_deepfm_v2_joint<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>, &k_deepfm_v2_joint_many<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>, \
+     &k_deepfm_v2_joint_many_tab<G_BIG, NJF, 1, 2, 1, V2_WAVES, HALF>}
 #define V2J_BOTH(G_BIG, NJF) V2J_VARIANT(G_BIG, NJF, true), V2J_VARIANT(G_BIG, NJF, false)
 const V2JVariant kV2JVariants[] = {
     V2J_BOTH(3, 3),    // BASELINE config 2: movieId, userId, userRatedMovie1 + a joint table of the three genre fields
@@ -267,6 +269,7 @@ int setup_v2_joint(sprk_engine* h) {
     h->v2j_lds_bytes = vv.lds_bytes + small_floats * sizeof(float);
     SPRK_TRY(set_max_lds(kV2JVariants[variant].fn, h->v2j_lds_bytes));
     SPRK_TRY(set_max_lds(kV2JVariants[variant].fn_many, h->v2j_lds_bytes));
+    SPRK_TRY(set_max_lds(kV2JVariants[variant].fn_many_tab, h->v2j_lds_bytes));
     h->v2j_variant = variant;
     // the one-task-per-wave shape for strict one-batch launches (k_chain_v2j1.h); SPRK_V2J_ONE=0: looped kernel only
     if (half && h->tune.v2j_one) {

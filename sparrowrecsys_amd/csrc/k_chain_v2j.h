@@ -71,6 +71,30 @@ struct V2JMany {
     int n;                                // batches in this launch
     int ntpb;                             // tasks per batch = ceil(B / 16)
 };
+// The same table in DEVICE memory (an engine-owned buffer, host_engine.h: V2JTable): no cap on n, so a sprk_forward_many call of more than
+// V2J_MB batches is ONE launch instead of one per V2J_MB.  The kernel-argument form pays a launch boundary, a prologue and a tail per group:
+// 7.8 us per launch at B = 65 536, measured as the intercept of launch time over batches per launch (docs/v2_one_launch_results.md).  One
+// 32-byte entry per batch: ids and dense are one scalar load when the task's ids are requested, out another at its gather.
+struct V2JBatch {
+    const int* ids;
+    const float* dense;
+    float* out;
+    void* pad_;
+};
+struct V2JManyTab {
+    const V2JBatch* batch;                // [n], device memory, never written while a launch that reads it is in flight
+    int n;
+    int ntpb;
+};
+struct V2JOne {};                         // one batch per launch: no table at all
+__device__ __forceinline__ const int* v2j_ids(const V2JMany& m, int b) { return m.ids[b]; }
+__device__ __forceinline__ const float* v2j_dense(const V2JMany& m, int b) { return m.dense[b]; }
+__device__ __forceinline__ float* v2j_out(const V2JMany& m, int b) { return m.out[b]; }
+// (the table is read through the constant address space: a wave-uniform load from there is a scalar load whatever the kernel stores elsewhere)
+typedef const __attribute__((address_space(4))) V2JBatch* V2JBatchCP;
+__device__ __forceinline__ const int* v2j_ids(const V2JManyTab& m, int b) { return ((V2JBatchCP)(uintptr_t)m.batch + b)->ids; }
+__device__ __forceinline__ const float* v2j_dense(const V2JManyTab& m, int b) { return ((V2JBatchCP)(uintptr_t)m.batch + b)->dense; }
+__device__ __forceinline__ float* v2j_out(const V2JManyTab& m, int b) { return ((V2JBatchCP)(uintptr_t)m.batch + b)->out; }
 
 // x*scale -> (hi, lo) halfs with hi + lo == x*scale to 22 bits
 __device__ __forceinline__ void split_half4(f32x4 w, float scale, f16x4& hi, f16x4& lo) {
@@ -208,6 +232,7 @@ struct V2JSet {
     int so[NJF];          // small fields: LDS float offset of this sample's row
     f32x4 xn;             // numerics: x[4q .. 4q+3]; HALF: {x[q], x[q+4]} only (K = 8 as two MFMA steps)
     float w1a;            // per-id logit terms fetched by this lane
+    float* dst;           // where this lane's score goes (lanes q == 0 of rows inside the batch; nullptr: nowhere)
 };
 
 // Task pipeline: TWO gather sets per wave (A, B), each the direct operand of its scoring stage.  A wave's
@@ -217,10 +242,12 @@ struct V2JSet {
 // score(A), gather(A'), score(B), gather(B') with ids fetched two tasks ahead, i.e. one gather is
 // always in flight under a scoring stage.  Loads are unconditional (task indices are clamped, the tail
 // re-gathers a valid task and drops the result) so that the in-order vmcnt waits stay exact.
-template <int G_BIG, int NJF, int KPC, int H0C, int H1C, int WAVES, bool HALF, bool MB>
+// Many: V2JOne (ids / dense / out are the batch), V2JMany or V2JManyTab (several batches: the table says whose task is whose).
+template <int G_BIG, int NJF, int KPC, int H0C, int H1C, int WAVES, bool HALF, class Many>
 __device__ __forceinline__ void v2j_body(const V2JRun& A, const int* __restrict__ ids, const float* __restrict__ dense,
                                          float* __restrict__ out, int B, int* __restrict__ err,
-                                         const float* __restrict__ image, const V2JMany* __restrict__ Mp) {
+                                         const float* __restrict__ image, const Many* __restrict__ Mp) {
+    constexpr bool MB = !std::is_same<Many, V2JOne>::value;
     constexpr int G_EMB = G_BIG + NJF;
     using LD = V2Lds<G_EMB, 4, KPC, H0C, H1C, true>;          // the weight image is the FOLD image of the whole model
     using Set = V2JSet<G_BIG, NJF>;
@@ -235,38 +262,35 @@ __device__ __forceinline__ void v2j_body(const V2JRun& A, const int* __restrict_
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, q = lane >> 4;
     const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
-    const int m_ntpb = MB ? Mp->ntpb : 0;
-    const int ntasks = MB ? Mp->n * m_ntpb : (B + 15) >> 4;
+    int m_ntpb = 0, ntasks = (B + 15) >> 4;
+    if constexpr (MB) { m_ntpb = Mp->ntpb; ntasks = Mp->n * m_ntpb; }
     const int task_stride = gridDim.x * WAVES;
     const int wave_global = blockIdx.x * WAVES + wave;
-    // MB: (batch, task inside the batch) of launch task tk (wave-uniform), and that batch's buffers
-    auto batch_of = [&](int tk, int& tl) {
-        if constexpr (MB) {
-            const int b = __builtin_amdgcn_readfirstlane(tk / m_ntpb);
-            tl = tk - b * m_ntpb;
-            return b;
-        } else {
-            tl = tk;
-            return 0;
-        }
+    // Where a launch task lives (wave-uniform: SGPRs).  Its batch is looked up ONCE, when its ids are requested (ld_raw: the one division),
+    // and the batch index is carried to its gather and its store; the index inside the batch follows from it.  (At B = 65 536 a wave's
+    // successive tasks, 2 048 apart, change batch every second task: there is no "same batch as before" to exploit, only the repeated
+    // look-ups to drop.  The batch index, not the pointers, is what a task keeps: one SGPR instead of six.)
+    auto batch_of = [&](int tk) -> int {
+        if constexpr (MB) return __builtin_amdgcn_readfirstlane(tk / m_ntpb);
+        else return 0;
     };
+    auto in_batch = [&](int tk, int b) -> int { return MB ? tk - b * m_ntpb : tk; };
     float* stage = smem + LD::total_pad + wave * LD::stage_floats;
     const float* small_s = smem + LD::total_pad + WAVES * LD::stage_floats;   // small fields' rows
     const float* wq = smem + 4 * q;
     bool bad = false;
     const bool aligned = !(A.flags & 1);
     auto clampt = [&](int tk) { return tk < ntasks ? tk : ntasks - 1; };
-    const int* const ids0 = ids;
-    const float* const dense0 = dense;
 
     // ---- gather stage ----
-    //   ld_raw : the task's contiguous ids / numerics blocks, one 16-B load per lane
+    //   ld_raw : the task's contiguous ids / numerics blocks, one 16-B load per lane; returns the task's batch
     //   gather : VGPR -> wave-private LDS slot -> the (r,q) lanes that need them, then the row gathers
-    auto ld_raw = [&](int tkg, f32x4& raw) {
-        int tk;
-        const int bi = batch_of(tkg, tk);
-        const int* ids_b = MB ? Mp->ids[bi] : ids;
-        const float* dense_b = MB ? Mp->dense[bi] : dense;
+    auto ld_raw = [&](int tkg, f32x4& raw) -> int {
+        const int b = batch_of(tkg);
+        const int tk = in_batch(tkg, b);
+        const int* ids_b = ids;
+        const float* dense_b = dense;
+        if constexpr (MB) { ids_b = v2j_ids(*Mp, b); dense_b = v2j_dense(*Mp, b); }
         if (aligned && tk * 16 + 16 <= B) {                       // wave-uniform
             const bool isid = lane < 32;
             const int j = isid ? lane : lane - 32;
@@ -275,19 +299,20 @@ __device__ __forceinline__ void v2j_body(const V2JRun& A, const int* __restrict_
                                     : dense_b + (size_t)tk * 16 * A.ND;
             raw = ld4(src + 4 * (j < n4 ? j : 0));
         }
+        return b;
     };
-    auto gather = [&](int tkg, const f32x4& raw, Set& S) {
-        int tk;
-        const int bi = batch_of(tkg, tk);
-        const int* ids = MB ? Mp->ids[bi] : ids0;
-        const float* dense = MB ? Mp->dense[bi] : dense0;
+    auto gather = [&](int tkg, int b, const f32x4& raw, Set& S) {
+        const int tk = in_batch(tkg, b);
         if (aligned && tk * 16 + 16 <= B) {
             const bool isid = lane < 32;
             const int j = isid ? lane : lane - 32;
             const int n4 = 4 * (isid ? A.F : A.ND);
             if (j < n4) st4(stage + (isid ? 0 : 128) + 4 * j, raw);
         } else {
-            stage_task_slow(stage, ids, dense, A.F, A.ND, tk, B, lane);
+            const int* ids_b = ids;                               // (an unaligned or partial task)
+            const float* dense_b = dense;
+            if constexpr (MB) { ids_b = v2j_ids(*Mp, b); dense_b = v2j_dense(*Mp, b); }
+            stage_task_slow(stage, ids_b, dense_b, A.F, A.ND, tk, B, lane);
         }
         // one wave: LDS operations complete in issue order, no barrier needed
         const int* sid_row = reinterpret_cast<const int*>(stage) + r * A.F;
@@ -331,6 +356,20 @@ __device__ __forceinline__ void v2j_body(const V2JRun& A, const int* __restrict_
             if (G_BIG > 1) so = q == 1 ? s1 : so;
             if (G_BIG > 2) so = q == 2 ? s2 : so;
             S.w1a = *reinterpret_cast<const float*>(tb + (so + 4u * KP));
+        }
+        // the score's address, worked out here: the store after the scoring stage needs no look-up and no scalar load of its own
+        {
+            float* out_b;
+            if constexpr (MB) {
+                out_b = v2j_out(*Mp, b);
+                // (through an empty asm as an SGPR pair: left visible, the table read sinks under the q == 0 mask as a per-lane vector load,
+                // and the wait for it drains every row load just issued)
+                asm("" : "+s"(out_b));
+            } else {
+                out_b = out;
+            }
+            const int m = tk * 16 + r;
+            S.dst = (q == 0 && m < B) ? out_b + m : nullptr;
         }
     };
 
@@ -503,24 +542,23 @@ __device__ __forceinline__ void v2j_body(const V2JRun& A, const int* __restrict_
         z = rows4_sum(z);
         return sigmoidf_fast(z + A.h0w * A.fo_bias + A.head_bias);
     };
-    auto store = [&](int tkg, float score) {
-        int tk;
-        const int bi = batch_of(tkg, tk);
-        float* out_b = MB ? Mp->out[bi] : out;
-        const int m = tk * 16 + r;
-        if (q == 0 && m < B) out_b[m] = score;
+    auto store = [&](const Set& S, float score) {
+        // (device memory, said so: behind the asm above the compiler no longer sees where the pointer came from and would issue a flat store)
+        if (S.dst) *(__attribute__((address_space(1))) float*)(uintptr_t)S.dst = score;
     };
 
     // ---- prologue: ids of the first two tasks and the weight image are requested together (the image
-    //      is L2-hot and lands inside the ids' memory latency), one barrier, weights -> registers, then
-    //      both gather sets back to back.  Straight-line code up to the loop: every s_waitcnt vmcnt the
-    //      compiler places is exact, so score(A) starts when A's rows are in, B's still streaming. ----
+    //      is L2-hot and lands inside the ids' memory latency), both gather sets back to back (at most two
+    //      tasks per wave: A before the barrier, B behind it), one barrier, weights -> registers.  Straight-line
+    //      code up to the loop: every s_waitcnt vmcnt the compiler places is exact, so score(A) starts when
+    //      A's rows are in, B's still streaming. ----
     Set SA, SB;
     f32x4 rawA = zero, rawB = zero;
     int tA = wave_global, tB = wave_global + task_stride;
+    int nA = 0, nB = 0;                                       // batch of the task whose ids are in rawA / rawB (gathered next)
     if (ntasks > 0) {
-        ld_raw(clampt(tA), rawA);
-        ld_raw(clampt(tB), rawB);
+        nA = ld_raw(clampt(tA), rawA);
+        nB = ld_raw(clampt(tB), rawB);
     }
     // weight image -> LDS by LDS-DMA (no VGPRs, no ds_write pass): 1-KB pieces, wave w takes w, w+WAVES, ...
 #pragma unroll 1
@@ -535,38 +573,45 @@ __device__ __forceinline__ void v2j_body(const V2JRun& A, const int* __restrict_
     // needs the ids only, and vmcnt retires in order, so "at most NG loads outstanding" means this wave's
     // DMA pieces (older) have landed while its NG row loads (younger) may still fly; gather B follows the
     // barrier (issuing it before as well measured the same, 9.2 us, at 12 more live registers).
+    // More than two tasks per wave (every several-batches launch of full batches): BOTH gathers and the next two
+    // tasks' ids are requested before the barrier, after this wave's ids and DMA pieces have landed (vmcnt(0), as
+    // before), so the rows travel while the workgroup meets at the barrier and load_weights() fills the registers
+    // (40 LDS reads and the f16 splits of W0) instead of being requested after them.  The gathers touch the
+    // wave-private staging slot only, never the image.
     const bool two = tA < ntasks && ntasks <= 2 * task_stride;        // workgroup-uniform except for idle waves
     constexpr int NG = G_BIG + 1;                                     // VMEM loads per gather: rows + row scalar
     static_assert(NG < 16, "s_waitcnt immediate below encodes vmcnt < 16");
     if (two) {
-        gather(tA, rawA, SA);
+        gather(tA, nA, rawA, SA);
         __builtin_amdgcn_s_waitcnt(0x0F70 | NG);                      // s_waitcnt vmcnt(NG)
     } else {
         __builtin_amdgcn_s_waitcnt(0x0F70);                           // s_waitcnt vmcnt(0): ids and DMA
+        if (tA < ntasks) {
+            gather(tA, nA, rawA, SA);
+            nA = ld_raw(clampt(tA + 2 * task_stride), rawA);
+            gather(clampt(tB), nB, rawB, SB);
+            nB = ld_raw(clampt(tB + 2 * task_stride), rawB);
+        }
     }
     __builtin_amdgcn_s_barrier();                             // every wave's pieces of the image are in LDS
     load_weights();
     if (tA >= ntasks) {
         // a wave without work leaves after the barrier
     } else if (two) {
-        gather(clampt(tB), rawB, SB);
-        store(tA, compute(SA));
-        if (tB < ntasks) store(tB, compute(SB));
+        gather(clampt(tB), nB, rawB, SB);
+        store(SA, compute(SA));
+        if (tB < ntasks) store(SB, compute(SB));
     } else {
-        gather(tA, rawA, SA);
-        ld_raw(clampt(tA + 2 * task_stride), rawA);
-        gather(clampt(tB), rawB, SB);
-        ld_raw(clampt(tB + 2 * task_stride), rawB);
         for (;;) {
-            store(tA, compute(SA));
+            store(SA, compute(SA));
             tA += 2 * task_stride;
-            gather(clampt(tA), rawA, SA);                     // (past the end: re-gathers the last task, never scored)
-            ld_raw(clampt(tA + 2 * task_stride), rawA);
+            gather(clampt(tA), nA, rawA, SA);                 // (past the end: re-gathers the last task, never scored)
+            nA = ld_raw(clampt(tA + 2 * task_stride), rawA);
             if (tB >= ntasks) break;
-            store(tB, compute(SB));
+            store(SB, compute(SB));
             tB += 2 * task_stride;
-            gather(clampt(tB), rawB, SB);
-            ld_raw(clampt(tB + 2 * task_stride), rawB);
+            gather(clampt(tB), nB, rawB, SB);
+            nB = ld_raw(clampt(tB + 2 * task_stride), rawB);
             if (tA >= ntasks) break;
         }
     }
@@ -579,12 +624,18 @@ template <int G_BIG, int NJF, int KPC, int H0C, int H1C, int WAVES, bool HALF>
 __global__ __launch_bounds__(WAVES * 64, 2) void k_deepfm_v2_joint(const V2JRun A, const int* __restrict__ ids,
                                                                    const float* __restrict__ dense, float* __restrict__ out, int B,
                                                                    int* __restrict__ err, const float* __restrict__ image) {
-    v2j_body<G_BIG, NJF, KPC, H0C, H1C, WAVES, HALF, false>(A, ids, dense, out, B, err, image, nullptr);
+    v2j_body<G_BIG, NJF, KPC, H0C, H1C, WAVES, HALF, V2JOne>(A, ids, dense, out, B, err, image, nullptr);
 }
 // Several batches per launch (sprk_set_many_batches): the table travels in the kernarg segment (+0.05 us of host time per
 // launch, no device-side cost: scripts/ubench/launch_floor.hip).
 template <int G_BIG, int NJF, int KPC, int H0C, int H1C, int WAVES, bool HALF>
 __global__ __launch_bounds__(WAVES * 64, 2) void k_deepfm_v2_joint_many(const V2JRun A, const V2JMany M, int B, int* __restrict__ err,
                                                                         const float* __restrict__ image) {
-    v2j_body<G_BIG, NJF, KPC, H0C, H1C, WAVES, HALF, true>(A, nullptr, nullptr, nullptr, B, err, image, &M);
+    v2j_body<G_BIG, NJF, KPC, H0C, H1C, WAVES, HALF, V2JMany>(A, nullptr, nullptr, nullptr, B, err, image, &M);
+}
+// ... with the table in device memory: any number of batches, one launch for a whole sprk_forward_many call (api_forward.h)
+template <int G_BIG, int NJF, int KPC, int H0C, int H1C, int WAVES, bool HALF>
+__global__ __launch_bounds__(WAVES * 64, 2) void k_deepfm_v2_joint_many_tab(const V2JRun A, const V2JManyTab M, int B, int* __restrict__ err,
+                                                                            const float* __restrict__ image) {
+    v2j_body<G_BIG, NJF, KPC, H0C, H1C, WAVES, HALF, V2JManyTab>(A, nullptr, nullptr, nullptr, B, err, image, &M);
 }
