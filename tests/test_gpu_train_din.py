@@ -1,6 +1,8 @@
 """``trainer_din.train_device`` (``sprk_train_din_fit``, csrc/k_train_din.h) against its definition ``trainer_din.train_host``: every weight,
 every ``m``, every ``v``, every ``p`` of the last epoch, accuracy and both AUCs of every epoch byte for byte, the loss within
-``max(N, 64) 2^-50`` relative (``-m gpu``).  Tiny vocabularies and at most 300 rows."""
+``max(N, 64) 2^-50`` relative (``-m gpu``).  Tiny vocabularies and tens to a few hundred rows, then the step shape ``trainer_din.fit`` ships
+with: batch 4096 at the default tile, the tiles below it, the stated maxima, tables, Dense parameters and schedules beyond one round of a grid
+(docs/train_shapes_results.md)."""
 import ctypes as C
 
 import numpy as np
@@ -386,3 +388,123 @@ def test_the_other_fits_are_what_they_were(torch):
     history = model.fit(cols, batch_size=128, epochs=1, learning_rate=0.01)
     want = TF.train_host(fam, start, ids, dense, y, batch_size=128, epochs=1, learning_rate=0.01)
     assert all(same(model.weights[k], want.weights[k]) for k in want.weights) and [h[1:] for h in history] == [h[1:] for h in want.history]
+
+
+# ---------------------------------------------------------------- the step shape trainer_din.fit ships with (docs/train_shapes_results.md)
+
+ROUND = 2048 * 256                                                     # FE_MAX_GRID workgroups of 256 threads: what one trip of a strided loop covers
+
+
+def strides(items):
+    """A loop over ``items`` elements, launched with fe_grid_capped(items) workgroups, makes a second trip (tests/test_gpu_grid_rounds.py)."""
+    return items > L.load_library().sprk_segments_grid(items) * 256
+
+
+@pytest.mark.parametrize("kw", [TDC.REFERENCE_SHAPE, dict(TDC.REFERENCE_SHAPE, hist_len=12)])
+def test_batch_4096_at_the_default_tile(torch, kw):
+    """The reference shape, and the same with T = 12, N = 4096 + 77, one epoch: one full batch of ``DEFAULT_BATCH`` rows (1 024 tiles of 4: 128
+    trips of k_tr_dense_adam's unrolled partial sum) and a short one of 20 tiles."""
+    fam, w, ids, dense, y = TDC.small(TD.DEFAULT_BATCH + 77, seed=21, **kw)
+    assert TD.default_tile(fam) == TD.DEFAULT_TILE == 4
+    want = both(fam, w, ids, dense, y, epochs=1)
+    assert want.step == 2
+
+
+@pytest.mark.parametrize("tile", [None, 3])
+def test_the_default_tile_falls_to_what_the_lds_holds(torch, tile):
+    """T = 12, H = 256: tiles 1, 2 and 3 fit the LDS and ``DEFAULT_TILE`` = 4 does not, so ``default_tile`` halves to 2.  A fit that names no
+    tile, and tile 3, the largest that fits."""
+    fam, w, ids, dense, y = TDC.small(40, seed=22, hist_len=12, att_hidden=256)
+    assert [TD.lds_bytes(fam, t) <= TD.LDS_BYTES for t in (1, 2, 3, 4)] == [True, True, True, False] and TD.default_tile(fam) == 2 < TD.DEFAULT_TILE
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=tile)
+
+
+def test_tile_one(torch):
+    """Tile 1 on 23 rows in batches of 7: every tile's partial sum is one sample's term."""
+    fam, w, ids, dense, y = TDC.small(23, seed=23)
+    both(fam, w, ids, dense, y, batch_size=7, epochs=2, tile=1)
+
+
+@pytest.mark.parametrize("batch", [56, 64, 72, 120, 128, 136])
+def test_tile_counts_around_the_unrolled_partial_sum(torch, batch):
+    """Tile 8: 7, 8, 9, 15, 16 and 17 tiles -- k_tr_dense_adam adds eight partials at a time, then the rest -- and a last batch of 5 rows."""
+    fam, w, ids, dense, y = TDC.small(batch + 5, seed=batch)
+    assert batch // 8 in (7, 8, 9, 15, 16, 17)
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=8)
+
+
+@pytest.mark.parametrize("kw", [dict(), dict(hist_len=1, att_hidden=1, hidden=(1,))])
+def test_a_tile_wider_than_the_workgroup(torch, kw):
+    """A tile of more than 256 samples: every per-sample loop of k_td_step goes round.  The tile is 300 or the largest that ``lds_bytes`` lets
+    into 160 KB: 257 for the default small shape (163 792 B), 300 for T = H = 1 with a tail of (1,).  N = batch = 650: three tiles."""
+    fam, w, ids, dense, y = TDC.small(650, seed=24, **kw)
+    once = TD.lds_bytes(fam, 0)
+    tile = min(300, (TD.LDS_BYTES - once) // (TD.lds_bytes(fam, 1) - once))
+    assert tile > 256 and TD.lds_bytes(fam, tile) <= TD.LDS_BYTES
+    both(fam, w, ids, dense, y, batch_size=650, epochs=2, tile=tile)
+
+
+@pytest.mark.parametrize("kw,tile,round_", [(dict(emb_dim=49), 8, False), (dict(hist_len=12, att_hidden=256), 3, False), (dict(hidden=(256,) * 8), 8, False),
+                                            (dict(emb_dim=49, hidden=(256,) * 8), 4, True)])
+def test_the_stated_maxima(torch, kw, tile, round_):
+    """``emb_dim`` 49, the largest the DIN class lays out (252 of ``fc0``'s 256 input rows); H = 256 at T = 12; eight tail layers of 256 units;
+    and the widest ``fc0`` under the deepest tail, whose 528 623 Dense floats send k_tr_dense_adam past one round of its grid.  28 rows."""
+    fam, w, ids, dense, y = TDC.small(28, seed=25, **kw)
+    assert TD.lds_bytes(fam, tile) <= TD.LDS_BYTES and strides(TDC.dense_floats(fam)) == round_
+    if "emb_dim" in kw:
+        assert fam.fan0 == 252
+        with pytest.raises(ValueError):
+            TDC.family(**dict(kw, emb_dim=50))
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=tile)
+
+
+def test_a_table_beyond_one_round_of_the_grid(torch):
+    """60 000 movies x 10: 600 000 floats of ``emb/movie`` at the head of the parameter vector, more than the 524 288 one round of
+    k_td_table_adam's grid covers.  Step 1 hits rows 0 and 52 428 through the candidate and rows 52 429 and 59 999 through a history slot:
+    elements 524 280 .. 524 299 lie on both sides of the round's end.  Those rows move; rows never hit keep their bits and zero moments; a row
+    hit in step 1 only still moves in step 3."""
+    fam, w, ids, dense, y = TDC.small(40, seed=26, movies=60000, emb_dim=10)
+    mv, T = "emb/movie", fam.hist_len
+    assert TD.param_names(fam)[0] == mv and w[mv].shape == (60000, 10) and strides(TDC.table_floats(fam))
+    assert 52428 * 10 < ROUND <= 52429 * 10
+    first = np.array([0, 52428, 52429, 59999])
+    ids[:, :T + 1] = np.random.default_rng(26).integers(100, 50000, (40, T + 1))
+    ids[:16, 0] = first[np.arange(16) % 2]
+    ids[:16, 2] = first[2 + np.arange(16) % 2]
+    one = both(fam, w, ids[:16], dense[:16], y[:16], batch_size=16, epochs=1, tile=8)
+    two = both(fam, w, ids[:32], dense[:32], y[:32], batch_size=16, epochs=1, tile=8)
+    three = both(fam, w, ids, dense, y, batch_size=16, epochs=1, tile=8)
+    assert three.step == 3
+    for row in first:
+        assert not same(one.weights[mv][row], w[mv][row])
+        assert not same(three.weights[mv][row], two.weights[mv][row])                                   # hit in step 1 only: still moving
+    never = np.ones(60000, dtype=bool)
+    never[ids[:, :T + 1]] = False
+    assert never.sum() > 59800 and same(three.weights[mv][never], w[mv][never]) and not three.m[mv][never].any() and not three.v[mv][never].any()
+    rest = np.ones(60000, dtype=bool)
+    rest[ids[:16, :T + 1]] = False
+    assert same(one.weights[mv][rest], w[mv][rest]) and not one.v[mv][rest].any()
+
+
+@pytest.mark.parametrize("batch,tile", [(4096, 32), (76000, 128)])
+def test_the_schedule_beyond_one_round_of_the_grid(torch, batch, tile):
+    """Seven id columns, N = 76 000: 532 000 entries, so k_tr_count and k_td_scatter make a second trip; in batches of 4 096 and as one batch,
+    whose positions pass 65 535 (a key holds position x 16 + column)."""
+    fam, w, ids, dense, y = TDC.small(76000, seed=27)
+    assert strides(ids.size) and TD.lds_bytes(fam, tile) <= TD.LDS_BYTES and (batch == 4096 or batch == len(y) > 65536)
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=tile)
+
+
+def test_the_error_word_beyond_one_round_of_the_grid(torch):
+    """N = 524 288 + 600: bad labels at rows 524 300 and 524 500, both in k_tr_check's second trip.  The library and both routes name row
+    524 300 and no parameter moves."""
+    fam, w, ids, dense, y = TDC.small(ROUND + 600, seed=28)
+    assert strides(len(y))
+    y[524500], y[524300] = np.nan, np.inf
+    flat0 = np.concatenate([w[k].reshape(-1) for k in TD.param_names(fam)])
+    rc, params, m, v, p, word, intact = raw_fit(torch, fam, w, ids, dense, y, 65536, 16, 1)
+    assert rc == 0 and intact and word == (T.ERR_LABEL << 32 | 524300), (word >> 32, word & 0xffffffff)
+    assert same(params, flat0) and not m.any() and not v.any()
+    for fit in (TD.train_device, TD.train_host):
+        with pytest.raises(ValueError, match="samples row 524300: the label"):
+            fit(fam, w, ids, dense, y, batch_size=65536, epochs=1, tile=16)

@@ -1,7 +1,8 @@
 """``trainer_pair.train_device`` (``sprk_train_pair_fit``, csrc/k_train_pair.h) against its definition ``trainer_pair.train_host``: every
 weight, every ``m``, every ``v``, every ``p`` of the last epoch, accuracy and both AUCs of every epoch byte for byte, the loss within
-``max(N, 64) 2^-50`` relative (``-m gpu``).  Tiny vocabularies and at most 300 rows, but for the one table that has to exceed a capped grid
-and the end-to-end test's few thousand ratings."""
+``max(N, 64) 2^-50`` relative (``-m gpu``).  Tiny vocabularies and tens to a few hundred rows, the one table that has to exceed a capped grid
+and the end-to-end test's few thousand ratings, then the step shape ``trainer_pair.fit`` ships with: batch 4096 at the default tile, every
+stated maximum, and tables, Dense parameters and schedules beyond one round of a grid (docs/train_shapes_results.md)."""
 import ctypes as C
 
 import numpy as np
@@ -425,3 +426,110 @@ def test_ratings_to_recommendations(torch, shared):
     assert all(same(model.weights[k], cont.weights[k]) for k in cont.weights) and again[0][1:] == cont.history[0][1:]
     with pytest.raises(NotImplementedError, match=r"NeuralCF\(arch=1\) and EmbeddingMLP"):
         model.fit(tcols)
+
+
+# ---------------------------------------------------------------- the step shape trainer_pair.fit ships with (docs/train_shapes_results.md)
+
+ROUND = 2048 * 256                                                     # FE_MAX_GRID workgroups of 256 threads: what one trip of a strided loop covers
+MORE_PAIRS = TPC.EIGHT_PAIRS + [("f0", "f0"), ("f3", "f3"), ("f7", "f1"), ("f5", "f5")]      # 32: all 28, then a reversed one and three (a, a)
+
+
+def strides(items):
+    """A loop over ``items`` elements, launched with fe_grid_capped(items) workgroups, makes a second trip (tests/test_gpu_grid_rounds.py)."""
+    return items > L.load_library().sprk_segments_grid(items) * 256
+
+
+@pytest.mark.parametrize("shared", SHARED)
+@pytest.mark.parametrize("kw", [dict(), dict(fields=TPC.SIX, pairs=TPC.SIX_PAIRS, emb_dim=10)], ids=["reference", "config2"])
+def test_batch_4096_at_the_default_tile(torch, kw, shared):
+    """The reference's four pairs and config 2's eight over six fields x 10, N = 4096 + 77, one epoch: one full batch of ``DEFAULT_BATCH`` rows
+    (512 tiles of 8: 64 trips of k_tp_dense_adam's unrolled partial sum) and a short one of 10 tiles."""
+    fam, w, ids, dense, y = TPC.small(TP.DEFAULT_BATCH + 77, seed=21, shared=shared, **kw)
+    assert TP.default_tile(fam) == TP.DEFAULT_TILE == 8
+    want = both(fam, w, ids, dense, y, epochs=1)
+    assert want.step == 2
+
+
+@pytest.mark.parametrize("shared", SHARED)
+def test_tile_one(torch, shared):
+    """Tile 1 on 23 rows in batches of 7: every tile's partial sum is one sample's term."""
+    fam, w, ids, dense, y = TPC.small(23, seed=23, shared=shared)
+    both(fam, w, ids, dense, y, batch_size=7, epochs=2, tile=1)
+
+
+@pytest.mark.parametrize("shared", SHARED)
+def test_thirty_two_pairs(torch, shared):
+    """``MAX_PAIRS`` = 32 over eight small fields: all 28 pairs, one of them again in reverse, three of the form ``(a, a)``."""
+    fam, w, ids, dense, y = TPC.small(40, seed=37, fields=TPC.EIGHT, pairs=MORE_PAIRS, deep_emb=("f0", "f2"), shared=shared)
+    assert len(fam.pairs) == TP.MAX_PAIRS and len(fam.fields) == TP.MAX_FIELDS
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+
+
+def test_every_maximum_at_once(torch):
+    """Eight fields, 32 pairs, ``emb_dim`` 64 and eight hidden layers of 256 units at the default tile: 104 672 B of LDS, and no wider legal
+    shape exists, so ``default_tile`` never falls below 8 for this trainer (docs/train_shapes_results.md).  28 rows, no tile named."""
+    fam, w, ids, dense, y = TPC.small(28, seed=38, fields=TPC.EIGHT, pairs=MORE_PAIRS, deep_emb=("f0", "f2"), emb_dim=TP.MAX_DIM, hidden=(TP.MAX_WIDTH,) * TP.MAX_LAYERS)
+    assert TP.default_tile(fam) == TP.DEFAULT_TILE and 48 * 1024 < TP.lds_bytes(fam, TP.DEFAULT_TILE) <= TP.LDS_BYTES
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2)
+
+
+def test_dense_parameters_beyond_one_round_of_the_grid(torch):
+    """Four deep tables of ``emb_dim`` 62 and seven numerics -- 255 of the 256 deep inputs -- under eight layers of 256: 526 341 floats in
+    k_tp_dense_adam's loop, the hole of the first-order rows among them, so it goes past one round of its grid.  28 rows."""
+    fam, w, ids, dense, y = TPC.small(28, seed=39, deep_emb=("movieId", "userId", "userGenre1", "movieGenre1"), emb_dim=62, hidden=(TP.MAX_WIDTH,) * TP.MAX_LAYERS)
+    assert len(fam.xsrc) == 255 and strides(TPC.dense_floats(fam)) and TP.lds_bytes(fam, 8) <= TP.LDS_BYTES
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+
+
+@pytest.mark.parametrize("shared", SHARED)
+def test_a_table_beyond_one_real_round_of_the_grid(torch, shared):
+    """60 000 movies x 10: 600 000 floats of ``emb/movieId`` at the head of the parameter vector, more than the 524 288 one round of
+    k_tp_table_adam's grid covers; ``deep_emb/movieId`` and the first-order rows of ``head/kernel`` lie wholly beyond it.  Step 1 hits rows 0,
+    52 428, 52 429 and 59 999: elements 524 280 .. 524 299 lie on both sides of the round's end.  Those rows move in all three places; rows
+    never hit keep their bits and zero moments; a row hit in step 1 only still moves in step 3."""
+    fields = [("movieId", "id", 60000), ("userId", "id", 5), ("userGenre1", "genre", 4), ("movieGenre1", "genre", 3)]
+    fam, w, ids, dense, y = TPC.small(40, seed=26, fields=fields, emb_dim=10, shared=shared)
+    assert TP.param_names(fam)[0] == "emb/movieId" and strides(TPC.table_floats(fam)) and 52428 * 10 < ROUND <= 52429 * 10
+    places = [("emb/movieId", 0), ("head/kernel", fam.fo_off[0])] + ([] if shared else [("deep_emb/movieId", 0)])
+    first = np.array([0, 52428, 52429, 59999])
+    ids[:16, 0] = first[np.arange(16) % 4]
+    ids[16:, 0] = np.random.default_rng(26).integers(100, 50000, 24)
+    one = both(fam, w, ids[:16], dense[:16], y[:16], batch_size=16, epochs=1, tile=8)
+    two = both(fam, w, ids[:32], dense[:32], y[:32], batch_size=16, epochs=1, tile=8)
+    three = both(fam, w, ids, dense, y, batch_size=16, epochs=1, tile=8)
+    assert three.step == 3
+    never = np.ones(60000, dtype=bool)
+    never[ids[:, 0]] = False
+    rest = np.setdiff1d(np.arange(60000), first)
+    assert never.sum() > 59900
+    for name, r0 in places:
+        for row in first:
+            assert not same(one.weights[name][r0 + row], w[name][r0 + row]), (name, row)
+            assert not same(three.weights[name][r0 + row], two.weights[name][r0 + row]), (name, row)    # hit in step 1 only: still moving
+        rows = slice(r0, r0 + 60000)
+        assert same(three.weights[name][rows][never], w[name][rows][never]) and not three.m[name][rows][never].any() and not three.v[name][rows][never].any()
+        assert same(one.weights[name][r0 + rest], w[name][r0 + rest])
+
+
+@pytest.mark.parametrize("batch,tile", [(4096, 32), (66000, 128)])
+def test_the_schedule_beyond_one_round_of_the_grid(torch, batch, tile):
+    """Eight fields, N = 66 000: 528 000 entries, so k_tr_count and k_tr_scatter make a second trip; in batches of 4 096 and as one batch,
+    whose positions pass 65 535."""
+    fam, w, ids, dense, y = TPC.small(66000, seed=27, fields=TPC.EIGHT, pairs=TPC.EIGHT_PAIRS, deep_emb=("f0", "f2"))
+    assert strides(ids.size) and TP.lds_bytes(fam, tile) <= TP.LDS_BYTES and (batch == 4096 or batch == len(y) > 65536)
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=tile)
+
+
+def test_the_error_word_beyond_one_round_of_the_grid(torch):
+    """N = 524 288 + 600: bad labels at rows 524 300 and 524 500, both in k_tr_check's second trip.  The library and both routes name row
+    524 300 and no parameter moves."""
+    fam, w, ids, dense, y = TPC.small(ROUND + 600, seed=28)
+    assert strides(len(y))
+    y[524500], y[524300] = np.nan, np.inf
+    flat0 = np.concatenate([w[k].reshape(-1) for k in TP.param_names(fam)])
+    rc, params, m, v, p, word, intact = raw_fit(torch, fam, w, ids, dense, y, 65536, 16, 1)
+    assert rc == 0 and intact and word == (T.ERR_LABEL << 32 | 524300), (word >> 32, word & 0xffffffff)
+    assert same(params, flat0) and not m.any() and not v.any() and not p.any()
+    for fit in (TP.train_device, TP.train_host):
+        with pytest.raises(ValueError, match="samples row 524300: the label"):
+            fit(fam, w, ids, dense, y, batch_size=65536, epochs=1, tile=16)

@@ -1,6 +1,8 @@
 """``trainer_wide.train_device`` (``sprk_train_wide_fit``, csrc/k_train_wide.h) against its definition ``trainer_wide.train_host``: every
 weight, every ``m``, every ``v``, every ``p`` of the last epoch, accuracy and both AUCs of every epoch byte for byte, the loss within
-``max(N, 64) 2^-50`` relative (``-m gpu``).  Tiny vocabularies and at most 300 rows, but for the end-to-end test's few thousand ratings."""
+``max(N, 64) 2^-50`` relative (``-m gpu``).  Tiny vocabularies and tens to a few hundred rows and the end-to-end test's few thousand ratings,
+then the step shape ``trainer_wide.fit`` ships with: batch 4096 at the default tile, the stated maxima, cross rows at the bitmap's word edges,
+and tables, cross rows, Dense parameters, buckets and schedules beyond one round of a grid (docs/train_shapes_results.md)."""
 import ctypes as C
 
 import numpy as np
@@ -375,3 +377,162 @@ def test_ratings_to_recommendations(torch):
     again = TW.fit(model, train.columns, batch_size=128, epochs=1, learning_rate=0.01)
     cont = TW.train_host(fam, want.weights, ids, dense, y, batch_size=128, epochs=1, learning_rate=0.01, state=(want.m, want.v, want.step))
     assert all(same(model.weights[k], cont.weights[k]) for k in cont.weights) and again[0][1:] == cont.history[0][1:]
+
+
+# ---------------------------------------------------------------- the step shape trainer_wide.fit ships with (docs/train_shapes_results.md)
+
+ROUND = 2048 * 256                                                     # FE_MAX_GRID workgroups of 256 threads: what one trip of a strided loop covers
+
+
+def strides(items):
+    """A loop over ``items`` elements, launched with fe_grid_capped(items) workgroups, makes a second trip (tests/test_gpu_grid_rounds.py)."""
+    return items > L.load_library().sprk_segments_grid(items) * 256
+
+
+@pytest.mark.parametrize("cross_dim", [0, 32])
+def test_batch_4096_at_the_default_tile(torch, cross_dim):
+    """The reference shape in both cross forms, N = 4096 + 77, one epoch: one full batch of ``DEFAULT_BATCH`` rows (1 024 tiles of 4: 128 trips
+    of k_tr_dense_adam's unrolled partial sum) and a short one of 20 tiles."""
+    fam, w, ids, dense, y = TWC.small(TW.DEFAULT_BATCH + 77, seed=21, cross_dim=cross_dim, **TWC.REFERENCE_SHAPE)
+    assert TW.default_tile(fam) == TW.TILE_WIDE == 4
+    want = both(fam, w, ids, dense, y, epochs=1)
+    assert want.step == 2
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+def test_tile_one(torch, cross_dim):
+    """Tile 1 on 23 rows in batches of 7: every tile's partial sum is one sample's term."""
+    fam, w, ids, dense, y = TWC.small(23, seed=23, cross_dim=cross_dim)
+    both(fam, w, ids, dense, y, batch_size=7, epochs=2, tile=1)
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+@pytest.mark.parametrize("batch", [56, 64, 72, 120, 128, 136])
+def test_tile_counts_around_the_unrolled_partial_sum(torch, batch, cross_dim):
+    """Tile 8: 7, 8, 9, 15, 16 and 17 tiles -- k_tr_dense_adam adds eight partials at a time, then the rest -- and a last batch of 5 rows."""
+    fam, w, ids, dense, y = TWC.small(batch + 5, seed=batch, cross_dim=cross_dim)
+    assert batch // 8 in (7, 8, 9, 15, 16, 17)
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=8)
+
+
+def test_a_tile_wider_than_the_workgroup(torch):
+    """Tile 300 > 256 threads: every per-sample loop of k_trw_step goes round; N = batch = 650 gives tiles of 300, 300 and 50."""
+    fam, w, ids, dense, y = TWC.small(650, seed=24, cross_dim=4)
+    assert TW.lds_bytes(fam, 300) <= TW.LDS_BYTES
+    both(fam, w, ids, dense, y, batch_size=650, epochs=2, tile=300)
+
+
+@pytest.mark.parametrize("kw,tile,round_", [(dict(hidden=(TW.MAX_WIDTH,) * TW.MAX_LAYERS), 8, False), (dict(emb_dim=24, cross_dim=3), 8, False),
+                                            (dict(emb_dim=24, hidden=(TW.MAX_WIDTH,) * TW.MAX_LAYERS, cross_dim=TW.MAX_CROSS_DIM), None, True)])
+def test_the_stated_maxima(torch, kw, tile, round_):
+    """Eight hidden layers of 256 units; ``emb_dim`` 24, the largest whose 247 input rows stay within 256; both with ``cross_dim`` 64, at the
+    tile a fit that names none gets: 4, which fits (no legal Wide&Deep shape makes ``default_tile`` fall: docs/train_shapes_results.md).  The
+    last has 524 353 Dense floats, so k_tr_dense_adam goes past one round of its grid.  28 rows."""
+    fam, w, ids, dense, y = TWC.small(28, seed=25, **kw)
+    assert TW.lds_bytes(fam, TW.default_tile(fam) if tile is None else tile) <= TW.LDS_BYTES and strides(TWC.dense_floats(fam)) == round_
+    if "emb_dim" in kw:
+        assert len(fam.xcol) == 247 and TW.default_tile(fam) == 4
+        with pytest.raises(ValueError):
+            TWC.family(**dict(kw, emb_dim=25))
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=tile)
+
+
+def test_a_table_beyond_one_round_of_the_grid(torch):
+    """60 000 movies x 10 among the deep tables: more floats than the 524 288 one round of k_tr_table_adam's grid covers, under this trainer's
+    own ``TrainDims``.  Step 1 hits ``emb/movieId``'s first and last rows and the two rows on either side of the round's end.  Those rows
+    move; rows never hit keep their bits and zero moments; a row hit in step 1 only still moves in step 3."""
+    fam, w, ids, dense, y = TWC.small(40, seed=26, movies=60000, emb_dim=10)
+    mv, col = "emb/movieId", fam.cross_a
+    shapes = TW.param_shapes(fam)
+    before = sum(int(np.prod(shapes[k])) for k in TW.param_names(fam)[:TW.param_names(fam).index(mv)])
+    edge = (ROUND - before) // 10                                       # the row that holds element 524 288 - 1 or ends just before it
+    assert fam.tables[col] == mv and strides(TWC.table_floats(fam)) and 0 < edge < 59998 and before + edge * 10 < ROUND <= before + (edge + 1) * 10
+    first = np.array([0, edge, edge + 1, 59999])
+    ids[:16, col] = first[np.arange(16) % 4]
+    ids[16:, col] = np.random.default_rng(26).integers(100, 50000, 24)
+    one = both(fam, w, ids[:16], dense[:16], y[:16], batch_size=16, epochs=1, tile=8)
+    two = both(fam, w, ids[:32], dense[:32], y[:32], batch_size=16, epochs=1, tile=8)
+    three = both(fam, w, ids, dense, y, batch_size=16, epochs=1, tile=8)
+    assert three.step == 3
+    for row in first:
+        assert not same(one.weights[mv][row], w[mv][row])
+        assert not same(three.weights[mv][row], two.weights[mv][row])                                   # hit in step 1 only: still moving
+    never = np.ones(60000, dtype=bool)
+    never[ids[:, col]] = False
+    assert never.sum() > 59900 and same(three.weights[mv][never], w[mv][never]) and not three.m[mv][never].any() and not three.v[mv][never].any()
+    rest = np.setdiff1d(np.arange(60000), first)
+    assert same(one.weights[mv][rest], w[mv][rest]) and not one.v[mv][rest].any()
+
+
+@pytest.mark.parametrize("buckets,cross_dim", [(600011, 0), (20011, 32)])
+def test_cross_rows_beyond_one_round_of_the_grid(torch, buckets, cross_dim):
+    """600 011 indicator rows, and 20 011 rows x 32 = 640 352 floats: k_trw_cross_adam makes a second trip without the switch.  A hit bucket
+    lies beyond element 524 288; hit rows move; rows the batch did not hash to keep their bits and zero moments."""
+    fam, w, ids, dense, y = TWC.small(40, seed=32, cross_buckets=buckets, cross_dim=cross_dim)
+    assert strides(TWC.cross_floats(fam))
+    hit = np.zeros(buckets, dtype=bool)
+    hit[TW.buckets_of(fam, ids)] = True
+    assert (np.flatnonzero(hit) * max(1, cross_dim) >= ROUND).any() and (np.flatnonzero(hit) * max(1, cross_dim) < ROUND).any()
+    want = both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=8)
+    assert same(wide_rows(fam, want.weights)[~hit], wide_rows(fam, w)[~hit]) and not wide_rows(fam, want.m)[~hit].any() and not wide_rows(fam, want.v)[~hit].any()
+    assert wide_rows(fam, want.v)[hit].all() and not same(wide_rows(fam, want.weights)[hit], wide_rows(fam, w)[hit])
+
+
+@pytest.mark.parametrize("cross_dim", FORMS)
+@pytest.mark.parametrize("buckets", [31, 32, 33, 63, 64, 65])
+def test_cross_buckets_at_the_bitmap_word_edges(torch, buckets, cross_dim):
+    """The bitmap of hit cross rows has 32 rows to a word: 31, 32, 33, 63, 64 and 65 buckets.  Three steps of 16 rows: step 1 hashes to bucket 0,
+    the last bucket and, where they exist, buckets 31 and 32, and to nothing else; step 2 to none of them; step 3 to them and to others.  So
+    each is hit in some step and missed in another, and in step 1 an odd row is hit whose even neighbour is not."""
+    fam, w, ids, dense, y = TWC.small(48, seed=40 + buckets, movies=30, rated=30, cross_buckets=buckets, cross_dim=cross_dim)
+    targets = sorted({0, buckets - 1} | ({31, 32} & set(range(buckets))))
+    a, b, bucket = TWC.cross_pairs(fam)
+    assert set(bucket.tolist()) == set(range(buckets))
+    rng = np.random.default_rng(buckets)
+    pick = lambda t: rng.choice(np.flatnonzero(bucket == t))
+    others = np.flatnonzero(~np.isin(bucket, targets))
+    rows = [pick(targets[i % len(targets)]) for i in range(16)] + list(rng.choice(others, 16)) + [pick(targets[i % len(targets)]) for i in range(8)] + list(rng.choice(others, 8))
+    ids[:, fam.cross_a], ids[:, fam.cross_b] = a[rows], b[rows]
+    got = TW.buckets_of(fam, ids)
+    steps = [set(got[s:s + 16].tolist()) for s in (0, 16, 32)]
+    for t in targets:
+        assert any(t in s for s in steps) and any(t not in s for s in steps), t
+    assert steps[0] == set(targets) and not steps[1] & set(targets)
+    assert buckets == 31 or any(t % 2 == 1 and t - 1 not in steps[0] for t in steps[0])
+    want = both(fam, w, ids, dense, y, batch_size=16, epochs=1, tile=8)
+    hit = np.zeros(buckets, dtype=bool)
+    hit[got] = True
+    assert same(wide_rows(fam, want.weights)[~hit], wide_rows(fam, w)[~hit]) and wide_rows(fam, want.v)[hit].all()
+
+
+@pytest.mark.parametrize("n,batch,tile", [(50000, 4096, 32), (70000, 70000, 128)])
+def test_the_schedule_beyond_one_round_of_the_grid(torch, n, batch, tile):
+    """Eleven id columns: 550 000 entries at N = 50 000 in batches of 4 096, 770 000 at N = 70 000 as one batch, whose positions pass 65 535;
+    k_trw_count and k_trw_scatter make a second trip."""
+    fam, w, ids, dense, y = TWC.small(n, seed=27, cross_dim=4)
+    assert strides(ids.size) and TW.lds_bytes(fam, tile) <= TW.LDS_BYTES and (batch == 4096 or batch == len(y) > 65536)
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=tile)
+
+
+def test_the_buckets_beyond_one_round_of_the_grid(torch):
+    """N = 524 288 + 600 rows that train: k_trw_buckets hashes one row per thread and makes a second trip, and the last batch reads the buckets
+    it wrote there.  Nine batches of 65 536 at tile 64; the host definition is most of this test's time."""
+    fam, w, ids, dense, y = TWC.small(ROUND + 600, seed=29, cross_dim=3)
+    assert strides(len(y))
+    want = both(fam, w, ids, dense, y, batch_size=65536, epochs=1, tile=64)
+    assert want.step == 9
+
+
+def test_the_error_word_beyond_one_round_of_the_grid(torch):
+    """N = 524 288 + 600: bad labels at rows 524 300 and 524 500, both in k_tr_check's second trip.  The library and both routes name row
+    524 300 and no parameter moves."""
+    fam, w, ids, dense, y = TWC.small(ROUND + 600, seed=28)
+    assert strides(len(y))
+    y[524500], y[524300] = np.nan, np.inf
+    flat0 = np.concatenate([w[k].reshape(-1) for k in TW.param_names(fam)])
+    rc, params, m, v, p, word, intact = raw_fit(torch, fam, w, ids, dense, y, 65536, 16, 1)
+    assert rc == 0 and intact and word == (T.ERR_LABEL << 32 | 524300), (word >> 32, word & 0xffffffff)
+    assert same(params, flat0) and not m.any() and not v.any() and not p.any()
+    for fit in (TW.train_device, TW.train_host):
+        with pytest.raises(ValueError, match="samples row 524300: the label"):
+            fit(fam, w, ids, dense, y, batch_size=65536, epochs=1, tile=16)

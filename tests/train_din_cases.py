@@ -50,6 +50,16 @@ def small(n, seed=0, **kw):
     return (fam, weights(fam, seed)) + data(fam, n, seed)
 
 
+def dense_floats(fam):
+    """The floats of every parameter that is no table: the items of ``k_tr_dense_adam``'s loop."""
+    return sum(int(np.prod(s)) for k, s in TD.param_shapes(fam).items() if k not in fam.tables)
+
+
+def table_floats(fam):
+    """The floats of all tables: the items of ``k_td_table_adam``'s loop."""
+    return sum(int(np.prod(s)) for k, s in TD.param_shapes(fam).items() if k in fam.tables)
+
+
 def torch_logit(fam, p, ids_t, dn, dtype, parts=None):
     """The graph in torch from a dict of tensors ``p``: -> the logit ``[n]``.  PReLU as ``relu(x) - alpha relu(-x)`` (Keras' form)."""
     import torch

@@ -48,6 +48,18 @@ def small(n, seed=0, **kw):
     return (fam, weights(fam, seed)) + data(fam, n, seed)
 
 
+def dense_floats(fam):
+    """The items of ``k_tp_dense_adam``'s loop: the deep layers, ``head/bias`` and ``head/kernel``'s tail ``[pairs + last width]``."""
+    s = TP.param_shapes(fam)
+    return sum(int(np.prod(s[k])) for k in s if k.startswith("deep") and not k.startswith("deep_emb/")) + 1 + len(fam.pairs) + fam.hidden[-1]
+
+
+def table_floats(fam):
+    """The items of ``k_tp_table_adam``'s loop: the floats of ``emb/*`` and ``deep_emb/*`` and ``head/kernel``'s first-order rows."""
+    s = TP.param_shapes(fam)
+    return sum(int(np.prod(s[k])) for k in s if k.startswith("emb/") or k.startswith("deep_emb/")) + fam.fo_total
+
+
 def torch_logit(fam, p, ids, dn, dtype):
     """The graph in torch from a dict of tensors ``p``: -> the logit ``[n]``."""
     import torch

@@ -49,6 +49,30 @@ def small(n, seed=0, **kw):
     return (fam, weights(fam, seed)) + data(fam, n, seed)
 
 
+def dense_floats(fam):
+    """The items of ``k_tr_dense_adam``'s loop: the hidden layers, ``head/bias`` and ``head/kernel[:H + cross_dim]``."""
+    s = TW.param_shapes(fam)
+    return sum(int(np.prod(s[name + "/kernel"])) + int(np.prod(s[name + "/bias"])) for name in fam.layers[:-1]) + 1 + fam.widths[-1] + fam.cross_dim
+
+
+def table_floats(fam):
+    """The items of ``k_tr_table_adam``'s loop: the floats of the ten deep tables."""
+    s = TW.param_shapes(fam)
+    return sum(int(np.prod(s[t])) for t in fam.tables)
+
+
+def cross_floats(fam):
+    """The items of ``k_trw_cross_adam``'s loop: ``cross_buckets`` rows of ``max(1, cross_dim)`` floats."""
+    return fam.cross_buckets * max(1, fam.cross_dim)
+
+
+def cross_pairs(fam):
+    """Every ``(movieId, userRatedMovie1)`` pair of the two vocabularies with its bucket: -> ``(a, b, bucket)``, flat arrays."""
+    a, b = np.meshgrid(np.arange(fam.columns[fam.cross_a][2]), np.arange(fam.columns[fam.cross_b][2]), indexing="ij")
+    a, b = a.reshape(-1), b.reshape(-1)
+    return a, b, TW.cross_bucket_host(a, b, fam.cross_buckets)
+
+
 def torch_logit(fam, p, ids, dn, dtype):
     """The graph in torch from a dict of tensors ``p``: -> the logit ``[n]``; the bucket from ``oracle.ctr_oracle.crossed_bucket_np``."""
     import torch
