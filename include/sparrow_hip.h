@@ -1057,6 +1057,28 @@ int sprk_train_din_fit(const sprk_train_din_model* model, const int32_t* ids, co
                        int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
                        float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Training DIEN: a Keras GRU (reset_after, gates z | r | h) over hist_len history slots that keeps its state and repeats its output at a slot whose
+ * id is 0, a per-slot gate sigmoid(Dense(1)(sigmoid(Dense(att_hidden)(g_t c)))) -- no PReLU and no softmax in the attention --, the reference's AUGRU
+ * (per gate r, z, h: Dense_out(Dense_in(g_t) + hid @ hid kernel); hs <- (1 - a_t r_t) hs + a_t r_t h~), a PReLU tail, one sigmoid; tanh is
+ * 2 sigmoid_def(2 z) - 1; the rules of the trainers above, sparrowrecsys_amd/trainer_dien.py's train_host is the definition of every bit (DESIGN.md
+ * section 5.22).  sprk_train_dien_model: sprk_train_din_model's fields with the same meaning, where xsrc -2 names the AUGRU's last state and column
+ * 0's genre must be 0.  params / m / v: one float vector each -- the tables in table order ([vocab][emb_dim]), the GRU's kernel and recurrent kernel
+ * ([emb_dim][3 emb_dim] each) and bias ([2][3 emb_dim]), att0 kernel ([emb_dim][att_hidden]) and bias, att1 kernel and bias, per gate r, z, h its
+ * in kernel ([emb_dim][emb_dim]), in bias, hid kernel, out kernel and out bias, the AUGRU's initial state ([emb_dim]), per tail layer kernel
+ * ([in][out]), bias and alpha, the head's kernel and bias -- trained in place.  Every other argument, the error word and the enqueue-only contract
+ * are those of sprk_train_fit; the workspace is laid out as sprk_train_din_fit's.  n x n_cols must stay below 2^31 - 1 and batch at or below 2^28;
+ * one workgroup's LDS (trainer_dien.lds_bytes) must fit 160 KB. */
+typedef struct {
+    int32_t n_cols, n_dense, emb_dim, hist_len, att_hidden, n_x, n_layers;
+    int32_t vocab[SPRK_TRAIN_DIN_MAX_COLS], genre[SPRK_TRAIN_DIN_MAX_COLS], table[SPRK_TRAIN_DIN_MAX_COLS];
+    int32_t width[SPRK_TRAIN_DIN_MAX_LAYERS];
+    int32_t xsrc[SPRK_TRAIN_DIN_MAX_X], xsub[SPRK_TRAIN_DIN_MAX_X];
+} sprk_train_dien_model;
+size_t sprk_train_dien_workspace_bytes(const sprk_train_dien_model* model, int64_t n, int32_t batch, int32_t tile);
+int sprk_train_dien_fit(const sprk_train_dien_model* model, const int32_t* ids, const float* dense, const float* labels, const int32_t* order, int64_t n,
+                        int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
+                        float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Training Wide&Deep: EmbeddingMLP's graph (sprk_train_fit's) plus a wide term in the head whose parameter row is FingerprintCat64(0xDECAFCAFFE,
  * ids[cross_a], ids[cross_b]) mod cross_buckets; the rules of the trainers above, sparrowrecsys_amd/trainer_wide.py's train_host is the definition
  * of every bit.  sprk_train_wide_model: sprk_train_model's fields, where the LAST id column (cross_b = n_cols - 1) has a

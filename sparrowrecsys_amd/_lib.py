@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "sprk_skipgram_workspace_bytes", "sprk_skipgram_fit",
     "sprk_train_workspace_bytes", "sprk_train_fit", "sprk_train_fm_workspace_bytes", "sprk_train_fm_fit", "sprk_train_din_workspace_bytes", "sprk_train_din_fit",
     "sprk_train_wide_workspace_bytes", "sprk_train_wide_fit", "sprk_train_pair_workspace_bytes", "sprk_train_pair_fit",
+    "sprk_train_dien_workspace_bytes", "sprk_train_dien_fit",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -120,6 +121,11 @@ class TrainDinModel(C.Structure):
                 ("n_layers", C.c_int32),
                 ("vocab", C.c_int32 * TRAIN_DIN_MAX_COLS), ("genre", C.c_int32 * TRAIN_DIN_MAX_COLS), ("table", C.c_int32 * TRAIN_DIN_MAX_COLS),
                 ("width", C.c_int32 * TRAIN_DIN_MAX_LAYERS), ("xsrc", C.c_int32 * TRAIN_DIN_MAX_X), ("xsub", C.c_int32 * TRAIN_DIN_MAX_X)]
+
+
+class TrainDienModel(C.Structure):
+    """sprk_train_dien_model (include/sparrow_hip.h): what trainer_dien.family_of gives, as the library takes it."""
+    _fields_ = list(TrainDinModel._fields_)
 
 
 TRAIN_WIDE_MAX_CROSS_DIM = 64
@@ -414,6 +420,9 @@ def load_library():
         lib.sprk_train_din_workspace_bytes.argtypes = [C.POINTER(TrainDinModel), C.c_int64, i32, i32]
         lib.sprk_train_din_workspace_bytes.restype = sz
         lib.sprk_train_din_fit.argtypes = [C.POINTER(TrainDinModel)] + lib.sprk_train_fit.argtypes[1:]           # sprk_train_fit's argument list
+        lib.sprk_train_dien_workspace_bytes.argtypes = [C.POINTER(TrainDienModel), C.c_int64, i32, i32]
+        lib.sprk_train_dien_workspace_bytes.restype = sz
+        lib.sprk_train_dien_fit.argtypes = [C.POINTER(TrainDienModel)] + lib.sprk_train_fit.argtypes[1:]         # sprk_train_fit's argument list
         lib.sprk_train_wide_workspace_bytes.argtypes = [C.POINTER(TrainWideModel), C.c_int64, i32, i32]
         lib.sprk_train_wide_workspace_bytes.restype = sz
         lib.sprk_train_wide_fit.argtypes = [C.POINTER(TrainWideModel)] + lib.sprk_train_fit.argtypes[1:]         # sprk_train_fit's argument list
@@ -421,7 +430,7 @@ def load_library():
         lib.sprk_train_pair_workspace_bytes.restype = sz
         lib.sprk_train_pair_fit.argtypes = [C.POINTER(TrainPairModel)] + lib.sprk_train_fit.argtypes[1:]         # sprk_train_fit's argument list
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_train_din_workspace_bytes", "sprk_train_wide_workspace_bytes", "sprk_train_pair_workspace_bytes","sprk_segments_grid", "sprk_rank_eval_workspace_bytes", "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_lsh_build_workspace_bytes", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_train_din_workspace_bytes", "sprk_train_dien_workspace_bytes", "sprk_train_wide_workspace_bytes", "sprk_train_pair_workspace_bytes","sprk_segments_grid", "sprk_rank_eval_workspace_bytes", "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_lsh_build_workspace_bytes", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib
