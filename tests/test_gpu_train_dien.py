@@ -1,7 +1,9 @@
 """``trainer_dien.train_device`` (``sprk_train_dien_fit``, csrc/k_train_dien.h) against its definition ``trainer_dien.train_host``: every
 weight, every ``m``, every ``v``, every ``p`` of the last epoch, accuracy and both AUCs of every epoch byte for byte, the loss within
 ``max(N, 64) 2^-50`` relative (``-m gpu``).  Tiny vocabularies and tens to a few hundred rows with about a third of the history ids 0, then
-one step at batch 4096 at the default tile and the chain from ratings to recommendations."""
+the step shape ``trainer_dien.fit`` ships with: batch 4096 at the default tile, the tiles below it and a tile wider than the workgroup, the
+stated maxima, a table, Dense parameters and schedules beyond one round of a grid (docs/train_dien_results.md section 4), and the chain from
+ratings to recommendations."""
 import ctypes as C
 
 import numpy as np
@@ -306,6 +308,166 @@ def test_batch_4096_at_the_default_tile(torch):
     assert TE.default_tile(fam) == TE.DEFAULT_TILE
     want = both(fam, w, ids, dense, y, epochs=1)
     assert want.step == 2
+
+
+ROUND = 2048 * 256                                                     # FE_MAX_GRID workgroups of 256 threads: what one trip of a strided loop covers
+
+
+def strides(items):
+    """A loop over ``items`` elements, launched with fe_grid_capped(items) workgroups, makes a second trip (tests/test_gpu_grid_rounds.py)."""
+    return items > L.load_library().sprk_segments_grid(items) * 256
+
+
+def top_tile(fam):
+    """The largest tile whose ``lds_bytes`` fit the LDS."""
+    once = TE.lds_bytes(fam, 0)
+    return (TE.LDS_BYTES - once) // (TE.lds_bytes(fam, 1) - once)
+
+
+def test_batch_4096_at_the_default_tile_with_twelve_slots(torch):
+    """The reference shape with T = 12, N = 4096 + 37, one epoch: ``default_tile`` is still 8 (143 312 B of LDS; 9 is the largest tile that
+    fits), 512 tiles and then 5."""
+    fam, w, ids, dense, y = TEC.small(TE.DEFAULT_BATCH + 37, seed=41, **dict(TEC.REFERENCE_SHAPE, hist_len=12))
+    assert TE.default_tile(fam) == TE.DEFAULT_TILE == 8 and TE.lds_bytes(fam, 8) == 143312 <= TE.LDS_BYTES and top_tile(fam) == 9
+    want = both(fam, w, ids, dense, y, epochs=1)
+    assert want.step == 2
+
+
+@pytest.mark.parametrize("tile", [None, 3])
+def test_the_default_tile_falls_to_what_the_lds_holds(torch, tile):
+    """T = 12, H = 256, D = 16 (the recurrent weights still staged): tiles 1, 2 and 3 fit the LDS (3 takes 145 032 B) and 4 does not, so
+    ``default_tile`` halves from 8 to 2.  A fit that names no tile, and tile 3, the largest that fits."""
+    fam, w, ids, dense, y = TEC.small(40, seed=42, hist_len=12, att_hidden=256, emb_dim=16)
+    assert [TE.lds_bytes(fam, t) <= TE.LDS_BYTES for t in (1, 2, 3, 4, 8)] == [True, True, True, False, False] and TE.lds_bytes(fam, 3) == 145032
+    assert TE.default_tile(fam) == 2 < TE.DEFAULT_TILE and top_tile(fam) == 3
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2, tile=tile)
+
+
+def test_the_default_tile_falls_to_one(torch):
+    """D = 64 at T = 12 and H = 256 (the movie columns alone): one sample takes 95 768 B and two do not fit, so a fit that names no tile
+    runs at tile 1, its recurrent weights read from L2."""
+    fam, w, ids, dense, y = TEC.small(40, seed=43, emb_dim=64, hist_len=12, att_hidden=256, others=False)
+    assert [TE.lds_bytes(fam, t) <= TE.LDS_BYTES for t in (1, 2, 4, 8)] == [True, False, False, False] and TE.lds_bytes(fam, 1) == 95768
+    assert TE.default_tile(fam) == 1 and TE.lds_bytes(fam, 0) == 0
+    both(fam, w, ids, dense, y, batch_size=16, epochs=2)
+
+
+def test_tile_one(torch):
+    """Tile 1 on 23 rows in batches of 7: every tile's partial sum is one sample's term."""
+    fam, w, ids, dense, y = TEC.small(23, seed=44)
+    both(fam, w, ids, dense, y, batch_size=7, epochs=2, tile=1)
+
+
+@pytest.mark.parametrize("batch", [56, 64, 72, 120, 128, 136])
+def test_tile_counts_around_the_unrolled_partial_sum(torch, batch):
+    """Tile 8: 7, 8, 9, 15, 16 and 17 tiles -- k_tr_dense_adam adds eight partials at a time, then the rest, here over the GRU's, the gate's
+    and the AUGRU's arrays in front of the tail -- and a last batch of 5 rows."""
+    fam, w, ids, dense, y = TEC.small(batch + 5, seed=batch)
+    assert batch // 8 in (7, 8, 9, 15, 16, 17) and batch % 8 == 0
+    want = both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=8)
+    assert want.step == 2
+
+
+@pytest.mark.parametrize("kw,tile", [(dict(hist_len=1, att_hidden=1, hidden=(1,)), 281), (dict(hist_len=1, att_hidden=1, hidden=(1,), emb_dim=1), 300)])
+def test_a_tile_wider_than_the_workgroup(torch, kw, tile):
+    """A tile of more than 256 samples: every per-sample loop of k_te_step (the head, ``da_t``, ``dl``, ...) goes round.  The tile is 300 or the
+    largest that ``lds_bytes`` lets into 160 KB: 281 for T = H = 1 with a tail of (1,) at D = 3 (580 B a sample and 684 B once), 300 at
+    D = 1.  N = batch = 650: three tiles, the last of 88 or 50 rows."""
+    fam, w, ids, dense, y = TEC.small(650, seed=45, **kw)
+    if fam.emb_dim == 3:
+        assert TE.lds_bytes(fam, 0) == 684 and TE.lds_bytes(fam, 1) - TE.lds_bytes(fam, 0) == 580
+    assert tile == min(300, top_tile(fam)) > 256 and TE.lds_bytes(fam, tile) <= TE.LDS_BYTES
+    want = both(fam, w, ids, dense, y, batch_size=650, epochs=2, tile=tile)
+    assert want.step == 2 and (650 + tile - 1) // tile == 3
+
+
+MAXIMA = [(dict(emb_dim=49), 8, 135904, None, False, 28, 16),
+          (dict(hist_len=12, att_hidden=256), 4, 113692, None, False, 28, 16),
+          (dict(hidden=(256,) * 8), 8, 157900, 468937, False, 28, 16),
+          (dict(emb_dim=64, hidden=(256,) * 8, others=False), 4, 155424, 560268, True, 28, 16),
+          (dict(emb_dim=64, hist_len=12, att_hidden=256, hidden=(256,) * 8, others=False), 1, 114072, 576834, True, 12, 8)]
+
+
+@pytest.mark.parametrize("kw,tile,lds,floats,round_,n,batch", MAXIMA)
+def test_the_stated_maxima(torch, kw, tile, lds, floats, round_, n, batch):
+    """``emb_dim`` 49, the largest that leaves room for the user and genre columns (252 of ``fc0``'s 256 input rows; 50 is refused); H = 256 at
+    T = 12 (the gate's loops run over 3 072 elements a sample); eight tail layers of 256 units, whose 468 937 Dense floats stay inside one round;
+    the same tail under D = 64, whose 560 268 Dense floats send k_tr_dense_adam past one round of its grid with the GRU's and the AUGRU's arrays
+    in front of the tail; and every maximum at once (576 834 Dense floats, the recurrent weights read from L2 at T = 12, one sample a tile)."""
+    fam, w, ids, dense, y = TEC.small(n, seed=46, **kw)
+    assert TE.lds_bytes(fam, tile) == lds <= TE.LDS_BYTES and strides(TEC.dense_floats(fam)) == round_
+    assert floats is None or TEC.dense_floats(fam) == floats
+    if kw == dict(emb_dim=49):
+        assert fam.fan0 == 252
+        with pytest.raises(ValueError, match="trainer_dien takes up to"):
+            TEC.family(emb_dim=50)
+    if "hist_len" in kw:
+        assert fam.hist_len * fam.att_hidden == 3072
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=2, tile=tile)
+
+
+def test_a_table_beyond_one_round_of_the_grid(torch):
+    """60 000 movies x 10: 600 000 floats of ``emb/movie`` at the head of the parameter vector, more than the 524 288 one round of
+    k_td_table_adam's grid covers.  Step 1 hits rows 0 and 52 428 through the candidate -- a history id 0 makes no entry, so row 0 has no
+    other way -- and rows 52 429 and 59 999 through a history slot: elements 524 280 .. 524 299 lie on both sides of the round's end.  Those
+    rows move; rows never hit keep their bits and zero moments; a row hit in step 1 only still moves in step 3; and with no candidate 0, the
+    samples whose first slot holds 0 leave row 0 as it was."""
+    fam, w, ids, dense, y = TEC.small(40, seed=47, movies=60000, emb_dim=10)
+    mv, T = "emb/movie", fam.hist_len
+    assert TE.param_names(fam)[0] == mv and w[mv].shape == (60000, 10) and strides(TEC.table_floats(fam))
+    assert 52428 * 10 < ROUND <= 52429 * 10
+    first = np.array([0, 52428, 52429, 59999])
+    ids[:, :T + 1] = np.random.default_rng(47).integers(100, 50000, (40, T + 1))
+    ids[5::7, 1] = 0                                                                                    # masked slots in every step
+    ids[:16, 0] = first[np.arange(16) % 2]
+    ids[:16, 2] = first[2 + np.arange(16) % 2]
+    assert (ids[16:, 0] != 0).all() and (ids[:16, 1] == 0).any() and (ids[16:32, 1] == 0).any() and (ids[32:, 1] == 0).any()
+    one = both(fam, w, ids[:16], dense[:16], y[:16], batch_size=16, epochs=1, tile=8)
+    two = both(fam, w, ids[:32], dense[:32], y[:32], batch_size=16, epochs=1, tile=8)
+    three = both(fam, w, ids, dense, y, batch_size=16, epochs=1, tile=8)
+    assert three.step == 3
+    for row in first:
+        assert not same(one.weights[mv][row], w[mv][row])
+        assert not same(three.weights[mv][row], two.weights[mv][row])                                   # hit in step 1 only: still moving
+    never = np.ones(60000, dtype=bool)
+    never[ids[:, :T + 1]] = False
+    assert never.sum() > 59800 and same(three.weights[mv][never], w[mv][never]) and not three.m[mv][never].any() and not three.v[mv][never].any()
+    rest = np.ones(60000, dtype=bool)
+    rest[ids[:16, :T + 1]] = False
+    assert same(one.weights[mv][rest], w[mv][rest]) and not one.v[mv][rest].any()
+    masked = ids[:16].copy()
+    masked[:, 0] = 52428
+    assert (masked[:, 1:T + 1] == 0).any() and (masked[:, 0] != 0).all()
+    none = both(fam, w, masked, dense[:16], y[:16], batch_size=16, epochs=1, tile=8)
+    assert same(none.weights[mv][0], w[mv][0]) and not none.m[mv][0].any() and not none.v[mv][0].any() and not same(none.weights[mv][52428], w[mv][52428])
+
+
+@pytest.mark.parametrize("batch,tile", [(4096, 32), (100000, 64)])
+def test_the_schedule_beyond_one_round_of_the_grid(torch, batch, tile):
+    """Seven id columns, N = 100 000: 700 000 elements for k_te_count and k_te_scatter to walk, of which the masked slots and the genre ids
+    -1 make no entry; the entries kept are still more than 524 288, so the sort's and the table kernel's view of them passes one round too.
+    In batches of 4 096 at tile 32 and as one batch at tile 64 (121 is the largest tile that fits), whose positions pass 65 535 in keys
+    that hold position x 16 + column."""
+    fam, w, ids, dense, y = TEC.small(100000, seed=48)
+    kept = TEC.kept_entries(fam, ids)
+    assert ids.size == 700000 and ROUND < kept < ids.size and strides(ids.size) and strides(kept)
+    assert TE.lds_bytes(fam, tile) <= TE.LDS_BYTES and top_tile(fam) == 121 and (batch == 4096 or batch == len(y) > 65536)
+    both(fam, w, ids, dense, y, batch_size=batch, epochs=1, tile=tile)
+
+
+def test_the_error_word_beyond_one_round_of_the_grid(torch):
+    """N = 524 288 + 600: bad labels at rows 524 300 and 524 500, both in k_tr_check's second trip.  The library and both routes name row
+    524 300 and no parameter moves."""
+    fam, w, ids, dense, y = TEC.small(ROUND + 600, seed=49)
+    assert strides(len(y))
+    y[524500], y[524300] = np.nan, np.inf
+    flat0 = np.concatenate([w[k].reshape(-1) for k in TE.param_names(fam)])
+    rc, params, m, v, p, word, intact = raw_fit(torch, fam, w, ids, dense, y, 65536, 16, 1)
+    assert rc == 0 and intact and word == (T.ERR_LABEL << 32 | 524300), (word >> 32, word & 0xffffffff)
+    assert same(params, flat0) and not m.any() and not v.any()
+    for fit in (TE.train_device, TE.train_host):
+        with pytest.raises(ValueError, match="samples row 524300: the label"):
+            fit(fam, w, ids, dense, y, batch_size=65536, epochs=1, tile=16)
 
 
 # ---------------------------------------------------------------- trainer_dien.fit

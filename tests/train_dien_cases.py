@@ -80,6 +80,23 @@ def small(n, seed=0, **kw):
     return (fam, weights(fam, seed)) + data(fam, n, seed)
 
 
+def dense_floats(fam):
+    """The floats of every parameter that is no table: the items of ``k_tr_dense_adam``'s loop."""
+    return sum(int(np.prod(s)) for k, s in TE.param_shapes(fam).items() if k not in fam.tables)
+
+
+def table_floats(fam):
+    """The floats of all tables: the items of ``k_td_table_adam``'s loop."""
+    return sum(int(np.prod(s)) for k, s in TE.param_shapes(fam).items() if k in fam.tables)
+
+
+def kept_entries(fam, ids):
+    """The entries of the device's schedule (``te_entry`` in csrc/k_train_dien.h): every id from 0, less the history slots that hold 0."""
+    ids = np.asarray(ids)
+    T = fam.hist_len
+    return int((ids >= 0).sum()) - int((ids[:, 1:T + 1] == 0).sum())
+
+
 def features(fam, ids, dense):
     """The feature dict ``oracle.ctr_oracle.dien_forward`` takes, from packed rows of a family with the user and genre columns."""
     T = fam.hist_len
