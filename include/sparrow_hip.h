@@ -1132,6 +1132,32 @@ int sprk_train_pair_fit(const sprk_train_pair_model* model, const int32_t* ids, 
                         int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
                         float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
 
+/* trainer_tower.fit for the two-tower NeuralCF (the reference's neural_cf_model_2): a Dense/ReLU tower over the movie row, one of the same widths over
+ * the user row, their dot -- the float32 dot of sprk_als_predict: from 0.0f in index order, every product and sum rounded on its own --, one Dense unit
+ * and a sigmoid; the rules of the trainer above, sparrowrecsys_amd/trainer_tower.py's train_host is the definition of every bit (DESIGN.md section
+ * 5.23).  sprk_train_tower_model: emb_dim, the hidden widths (both towers') and vocab = {movieId's, userId's}.  ids = [n][2] (movieId, userId); there
+ * are no numerics, so sprk_train_tower_fit takes sprk_train_fit's arguments less `dense`.  params / m / v: one float vector each -- the movie table,
+ * the user table ([vocab][emb_dim]), per layer of the item tower its kernel ([in][out]) and bias, the same of the user tower, the head's kernel, the
+ * head's bias -- trained in place.  The error word and the enqueue-only contract are those of sprk_train_fit.  n x 2 must stay below 2^31 - 1; one
+ * workgroup's LDS (trainer_tower.lds_bytes) must fit 160 KB.  A NaN that reaches p, a parameter, m or v is stored as 0x7fc00000.
+ * sprk_tower_rows: every row of table `side` (0 = movieId through the item tower, 1 = userId through the user tower) of such a parameter vector through
+ * its tower, by the fit's own forward statements: out[row x out_stride + j], j < the last width; the floats between are left alone.  `tile` rows per
+ * workgroup pass (2 x tile x the widest of emb_dim and the layers, in floats rounded up to 4, must fit 160 KB).  Enqueued on `stream`; SPRK_EINVAL
+ * before any device call for a bad argument. */
+#define SPRK_TRAIN_TOWER_MAX_LAYERS 8
+#define SPRK_TRAIN_TOWER_MAX_WIDTH 256
+#define SPRK_TRAIN_TOWER_MAX_DIM 128
+typedef struct {
+    int32_t emb_dim, n_layers;
+    int32_t vocab[2];
+    int32_t width[SPRK_TRAIN_TOWER_MAX_LAYERS];
+} sprk_train_tower_model;
+size_t sprk_train_tower_workspace_bytes(const sprk_train_tower_model* model, int64_t n, int32_t batch, int32_t tile);
+int sprk_train_tower_fit(const sprk_train_tower_model* model, const int32_t* ids, const float* labels, const int32_t* order, int64_t n,
+                         int32_t batch, int32_t tile, int32_t epochs, const float* alphas, float one_minus_beta1, float one_minus_beta2, float epsilon,
+                         float* params, float* m, float* v, float* p, uint64_t* error_key, void* workspace, size_t workspace_bytes, void* stream);
+int sprk_tower_rows(const sprk_train_tower_model* model, const float* params, int32_t side, int32_t tile, float* out, int64_t out_stride, void* stream);
+
 const char* sprk_last_error(void);
 
 #if defined(__GNUC__) || defined(__clang__)

@@ -49,7 +49,7 @@ EXPORTED_SYMBOLS = [
     "sprk_skipgram_workspace_bytes", "sprk_skipgram_fit",
     "sprk_train_workspace_bytes", "sprk_train_fit", "sprk_train_fm_workspace_bytes", "sprk_train_fm_fit", "sprk_train_din_workspace_bytes", "sprk_train_din_fit",
     "sprk_train_wide_workspace_bytes", "sprk_train_wide_fit", "sprk_train_pair_workspace_bytes", "sprk_train_pair_fit",
-    "sprk_train_dien_workspace_bytes", "sprk_train_dien_fit",
+    "sprk_train_dien_workspace_bytes", "sprk_train_dien_fit", "sprk_train_tower_workspace_bytes", "sprk_train_tower_fit", "sprk_tower_rows",
     "sprk_describe", "sprk_comm_unique_id", "sprk_comm_create", "sprk_comm_allgather_scores", "sprk_comm_destroy",
     "sprk_peer_create", "sprk_peer_connect", "sprk_peer_allgather_scores", "sprk_peer_check", "sprk_peer_memory_kind", "sprk_peer_destroy",
     "sprk_vtable_create", "sprk_vtable_export", "sprk_vtable_import", "sprk_vtable_info", "sprk_vtable_destroy", "sprk_upload_external",
@@ -146,6 +146,14 @@ class TrainPairModel(C.Structure):
                 ("vocab", C.c_int32 * TRAIN_PAIR_MAX_FIELDS), ("genre", C.c_int32 * TRAIN_PAIR_MAX_FIELDS), ("fo_off", C.c_int32 * TRAIN_PAIR_MAX_FIELDS),
                 ("pair_a", C.c_int32 * TRAIN_PAIR_MAX_PAIRS), ("pair_b", C.c_int32 * TRAIN_PAIR_MAX_PAIRS), ("deep_col", C.c_int32 * TRAIN_PAIR_MAX_FIELDS),
                 ("width", C.c_int32 * TRAIN_PAIR_MAX_LAYERS), ("xsrc", C.c_int32 * TRAIN_PAIR_MAX_X), ("xsub", C.c_int32 * TRAIN_PAIR_MAX_X)]
+
+
+TRAIN_TOWER_MAX_LAYERS, TRAIN_TOWER_MAX_WIDTH, TRAIN_TOWER_MAX_DIM = 8, 256, 128
+
+
+class TrainTowerModel(C.Structure):
+    """sprk_train_tower_model (include/sparrow_hip.h): what trainer_tower.family_of gives, as the library takes it."""
+    _fields_ = [("emb_dim", C.c_int32), ("n_layers", C.c_int32), ("vocab", C.c_int32 * 2), ("width", C.c_int32 * TRAIN_TOWER_MAX_LAYERS)]
 
 
 class Seg(C.Structure):
@@ -429,8 +437,13 @@ def load_library():
         lib.sprk_train_pair_workspace_bytes.argtypes = [C.POINTER(TrainPairModel), C.c_int64, i32, i32]
         lib.sprk_train_pair_workspace_bytes.restype = sz
         lib.sprk_train_pair_fit.argtypes = [C.POINTER(TrainPairModel)] + lib.sprk_train_fit.argtypes[1:]         # sprk_train_fit's argument list
+        lib.sprk_train_tower_workspace_bytes.argtypes = [C.POINTER(TrainTowerModel), C.c_int64, i32, i32]
+        lib.sprk_train_tower_workspace_bytes.restype = sz
+        a = lib.sprk_train_fit.argtypes
+        lib.sprk_train_tower_fit.argtypes = [C.POINTER(TrainTowerModel), a[1]] + a[3:]                          # sprk_train_fit's argument list less `dense`
+        lib.sprk_tower_rows.argtypes = [C.POINTER(TrainTowerModel), vp, i32, i32, vp, C.c_int64, vp]
         for name in EXPORTED_SYMBOLS:
-            if name not in ("sprk_train_din_workspace_bytes", "sprk_train_dien_workspace_bytes", "sprk_train_wide_workspace_bytes", "sprk_train_pair_workspace_bytes","sprk_segments_grid", "sprk_rank_eval_workspace_bytes", "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_lsh_build_workspace_bytes", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
+            if name not in ("sprk_train_tower_workspace_bytes", "sprk_train_din_workspace_bytes", "sprk_train_dien_workspace_bytes", "sprk_train_wide_workspace_bytes", "sprk_train_pair_workspace_bytes","sprk_segments_grid", "sprk_rank_eval_workspace_bytes", "sprk_exact_auc_workspace_bytes", "sprk_exact_auc_bin_bits", "sprk_lsh_build_workspace_bytes", "sprk_train_fm_workspace_bytes","sprk_train_workspace_bytes", "sprk_item_sequences_workspace_bytes", "sprk_item_walks_workspace_bytes", "sprk_skipgram_workspace_bytes", "sprk_als_workspace_bytes", "sprk_als_topk_workspace_bytes", "sprk_catalog_build_workspace_bytes", "sprk_last_error", "sprk_destroy", "sprk_workspace_bytes", "sprk_emb_topk_workspace_bytes", "sprk_metrics_state_bytes", "sprk_feature_eng_workspace_bytes", "sprk_user_emb_workspace_bytes", "sprk_comm_destroy", "sprk_peer_destroy", "sprk_peer_memory_kind", "sprk_vtable_destroy"):
                 getattr(lib, name).restype = C.c_int
         _lib = lib
         return lib
